@@ -10,6 +10,11 @@ owned position -> first record + record count) followed by the RCCL allgather of
 per-shard {first_vpos, count, exit} records that stitches the splits.
 
 Run: python bench.py --gpus N --steps K --warmup W   (N>1 under torch.distributed.run)
+
+A plain run generates the input, warms up, times the K steps and prints the result line.
+--full adds the side measurements and checks that take runs of their own (the CRC32 pass over
+the inflated shard, full_check, facade, e2e_h2d, cpu_baseline; each still has its --no-* switch).
+--dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy (dump_outputs).
 """
 import argparse
 import ctypes as C
@@ -73,6 +78,11 @@ def main():
                          "file's per-GPU shard at N=8 (12.5 GiB); D: long reads; E: adversarial (N=1 only)")
     ap.add_argument("--records-per-gpu", type=int, default=None,
                     help="~1.0 GiB compressed per GPU at level 6 (config B)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements and checks beside the headline figure: CRC32 of every "
+                         "inflated block, full_check, facade, e2e_h2d, cpu_baseline (off by default)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned as DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline sample budget")
     ap.add_argument("--cpu-threads", type=int, default=None,
                     help="CPU baseline threads (default: every host core this process may use)")
@@ -102,6 +112,10 @@ def main():
                     help="HBM bytes per launch of the dominant kernel (default: the committed "
                          "rocprofv3 --pmc summary, profiles/*_pmc_traffic.json)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:  # a plain run: nothing beside the timed steps
+        args.no_full = args.no_e2e = args.no_cpu_baseline = args.no_facade = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` outside a launcher: start the N ranks as a CHILD process
@@ -247,6 +261,15 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
 
+    sl = stream_last if streaming else split_last
+    if args.dump_outputs:
+        arrays = step_arrays(r["first_vpos"] if r["count"] else None, allr[rank][4], r, sl["split_status"],
+                             sl["split_first_vpos" if streaming else "split_vpos"], sl["split_count"])
+        if shard is not None:  # what the step left in HBM for its caller: the inflated bytes and the eager bitmap
+            f0 = max(0, shard.flat_bound(seg.file_offset)) if seg.file_offset else 0
+            arrays.update(resident_sample(shard, f0, shard.flat_bound(seg.own_end)))
+        dump_outputs(args.dump_outputs, rank, arrays)
+
     # ---- correctness of the stitched result (every rank) ----
     total_records = sum(x[1] for x in allr)
     total_true = sum(x[2] for x in allr)
@@ -260,11 +283,14 @@ def main():
     # every inflated block of the last step against its BGZF footer CRC32 (full-size
     # bit-exactness of the inflate), outside the timed region
     # (stream mode: every window's owned blocks were CRC-checked in the run, sbh_run_stream2)
-    crc_bad = shard.verify_crc()[0] if shard is not None else stream_last.get("crc_bad_blocks", 0)
-    sl = stream_last if streaming else split_last
+    # (resident shards: a pass of its own over the inflated bytes, so with --full only)
+    if shard is None:
+        crc_bad = stream_last.get("crc_bad_blocks", 0)
+    else:
+        crc_bad = shard.verify_crc()[0] if args.full else None
     split_ok = (int(np.count_nonzero(sl["split_status"])) == 0 and int(sl["split_count"].sum()) == r["count"])
-    ok = (total_records == expect and (total_true == expect or not cfg["fp_free"]) and stitch["ok"] and crc_bad == 0
-          and split_ok)
+    ok = (total_records == expect and (total_true == expect or not cfg["fp_free"]) and stitch["ok"]
+          and not crc_bad and split_ok)
     firsts = [x[0] for x in allr if x[1] > 0]
 
     stage_ms = stage_acc / args.steps
@@ -405,7 +431,7 @@ def main():
                              "counts_sum": int(sl["split_count"].sum()),
                              "note": "every owned Hadoop split's first-record vpos and count "
                                      "(sbh_split_starts) inside the timed step"},
-            "crc_bad_blocks_rank0": int(crc_bad),
+            "crc_bad_blocks_rank0": None if crc_bad is None else int(crc_bad),  # None: not checked (no --full)
             "records": int(total_records),
             "eager_true": int(total_true),
             "stages_ms_rank0": {"index": round(stage_ms[0], 3),
@@ -530,6 +556,10 @@ def main_strong(args, rank, world, local_rank, device, backend, xdev, coll, dist
         elapsed = float(tt.item())
     # per-split results -> the reference's splits (sliding2 over non-empty firsts) and counts
     r = last
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank,
+                     step_arrays(r["first_vpos"], -1 if r["exit_vpos"] is None else r["exit_vpos"], r,
+                                 r["split_status"], r["split_first_vpos"], r["split_count"]))
     part = sharded.RankPart(rank, a, [int(v) if c else None for v, c in zip(r["split_first_vpos"], r["split_count"])],
                             [int(c) for c in r["split_count"]], r["first_vpos"] if r["count"] else None, r["count"],
                             r["exit_vpos"])
@@ -602,6 +632,65 @@ def main_strong(args, rank, world, local_rank, device, backend, xdev, coll, dist
     if ranks_seen != args.gpus:
         log(f"ranks_seen {ranks_seen} != --gpus {args.gpus}")
         sys.exit(4)
+
+
+DUMP_MAX_BYTES = 64_000_000  # of .npy data per rank
+DUMP_CHUNKS, DUMP_CHUNK = 128, 32768  # the resident sample: positions per chunk (a multiple of 8)
+DUMP_SEED = 0x5B4DD0
+
+
+def _pos(v):
+    """An htsjdk virtual offset as (block position, offset in the block); (-1, -1) for none."""
+    return (-1, -1) if v is None or v < 0 else (int(v) >> 16, int(v) & 0xFFFF)
+
+
+def step_arrays(first_vpos, exit_vpos, r, split_status, split_vpos, split_count):
+    """What one timed step hands its caller, as float64 arrays (every value < 2^53, so exact):
+    result = [first record's block position, its offset, record count, eager-true positions, flat
+    bytes, the chain exit's block position, its offset]; per owned Hadoop split its status, first
+    record (block position, offset) and record count."""
+    v = np.asarray(split_vpos, dtype=np.uint64)
+    return {
+        "result": np.array([*_pos(first_vpos), r["count"], r["n_true"], r["flat_bytes"], *_pos(exit_vpos)],
+                           dtype=np.float64),
+        "split_status": np.asarray(split_status, dtype=np.float64),
+        "split_first_block_pos": (v >> np.uint64(16)).astype(np.float64),
+        "split_first_offset": (v & np.uint64(0xFFFF)).astype(np.float64),
+        "split_count": np.asarray(split_count, dtype=np.float64),
+    }
+
+
+def resident_sample(shard, f0, f1):
+    """A fixed, seeded sample of what the last run left resident over the owned flat range
+    [f0, f1): DUMP_CHUNKS chunks of DUMP_CHUNK positions (the whole range when it is smaller),
+    their inflated bytes and their bytes of the eager bitmap (8 positions per byte)."""
+    f0 = (f0 + 7) & ~7  # the bitmap is read at byte granularity
+    n = max(0, f1 - f0) // DUMP_CHUNK
+    if n <= DUMP_CHUNKS:
+        ranges = [(f0, f1)] if f1 > f0 else []
+    else:
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_CHUNKS, replace=False))
+        ranges = [(f0 + int(i) * DUMP_CHUNK, f0 + (int(i) + 1) * DUMP_CHUNK) for i in pick]
+    flat = [shard.read_flat(a, b - a) for a, b in ranges]
+    bits = [shard.eager_bits(a, b) for a, b in ranges]
+    return {
+        "sample_flat_begin": np.array([a for a, _ in ranges], dtype=np.float64),
+        "sample_flat_end": np.array([b for _, b in ranges], dtype=np.float64),
+        "sample_inflated_bytes": np.concatenate(flat or [np.zeros(0, np.uint8)]).astype(np.float32),
+        "sample_eager_bitmap_bytes": np.concatenate(bits or [np.zeros(0, np.uint8)]).astype(np.float32),
+    }
+
+
+def dump_outputs(dirname, rank, arrays):
+    """DIR/<name>.npy per array (rank 0; `<name>_rank<r>.npy` for the others), float32 or float64."""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES} byte limit")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(dirname, name + ("" if rank == 0 else f"_rank{rank}") + ".npy"), a)
+    log(f"[rank {rank}] wrote {len(arrays)} arrays ({total} bytes) under {dirname}")
 
 
 def facade_bench(sb, ctx, comp, file_size, contig_len, threads, torch, run, split_last, splits, value_ref,

@@ -4,7 +4,7 @@
 #   bash tools/gpu_round.sh round TAG              -m gpu suite, bench (config B), its rocprofv3 kernel
 #                                                  summary, bench lines for configs D and E
 #   bash tools/gpu_round.sh tests TAG FILE...      the -m gpu tests of the named files, verbose
-#   bash tools/gpu_round.sh bench TAG ARGS...      one bench.py line with ARGS
+#   bash tools/gpu_round.sh bench TAG ARGS...      one bench.py line with ARGS (--full: with the side measurements)
 #   bash tools/gpu_round.sh prof TAG ARGS...       rocprofv3 --kernel-trace --stats of bench.py ARGS
 #   bash tools/gpu_round.sh ab TAG CONFIG RECORDS V...   inflate A/B: in-tree vs spark-bam_amd/build/ab/lib_V.so
 #   bash tools/gpu_round.sh fullab TAG RECORDS V...      full-checker A/B (tools/full_ab.py), same variants
@@ -22,7 +22,7 @@ prof_env() { cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"; }
 case "$M" in
 round)
   timeout -k 10 900 $PYT tests -x -q > gpurun_out/${T}_pytest_gpu.log 2>&1 || exit 1
-  timeout -k 10 300 python -u bench.py > gpurun_out/${T}_bench.json 2> gpurun_out/${T}_bench.err || exit 2
+  bash "$0" bench "$T" --full || exit 2  # the line with its side measurements
   prof_env
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d /tmp/${T}_bprof -o run -- python3 bench.py --steps 5 --warmup 2 \
     --no-cpu-baseline --no-full --no-e2e --no-facade > gpurun_out/${T}_bprof.json 2> gpurun_out/${T}_bprof.log || exit 3

@@ -2,10 +2,10 @@
 # rocprofv3 counter passes over a short bench run (one pass per counter group: rocprofv3 does
 # not split groups over passes; at most 8 SQ / 4 TCC counters per pass on gfx950), then the
 # per-kernel summaries.  Usage (on the GPU box, from the repo root):
-#   bash tools/pmc_collect.sh gpurun_out/pmc "--no-cpu-baseline --no-e2e --steps 2 --warmup 1"
+#   bash tools/pmc_collect.sh OUTDIR "--full --no-cpu-baseline --no-e2e --steps 2 --warmup 1"
 set -euo pipefail
 OUT=${1:-gpurun_out/pmc}
-ARGS=${2:---no-cpu-baseline --no-e2e --no-facade --steps 2 --warmup 1}
+ARGS=${2:---full --no-cpu-baseline --no-e2e --no-facade --steps 2 --warmup 1}
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 cd - > /dev/null

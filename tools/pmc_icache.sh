@@ -11,7 +11,7 @@ pass() {  # name, counters...
   local name=$1
   shift
   timeout -s KILL 240 rocprofv3 --pmc "$@" -d "$OUT/$name" -o "$name" --output-format csv -- \
-    python3 bench.py --no-cpu-baseline --no-e2e --no-full --steps 2 --warmup 1 > "$OUT/$name.bench.json" 2> "$OUT/$name.log"
+    python3 bench.py --full --no-cpu-baseline --no-e2e --no-full --steps 2 --warmup 1 > "$OUT/$name.bench.json" 2> "$OUT/$name.log"
   local f
   f=$(find "$OUT/$name" -name "*counter_collection.csv" -print -quit)
   cp "$f" "$OUT/$name.csv"

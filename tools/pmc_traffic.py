@@ -39,7 +39,7 @@ def main(fetch, write):
         rd = 2 * f.get(k, 0.0) * 1024
         wr = w.get(k, 0.0) * 1024
         out[k] = {"read_bytes": int(rd), "write_bytes": int(wr), "hbm_bytes": int(rd + wr)}
-    json.dump({"source": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE over `bench.py --no-cpu-baseline "
+    json.dump({"source": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE over `bench.py --full --no-cpu-baseline "
                          "--steps 2 --warmup 1` (median launch; FETCH_SIZE doubled, gfx950)",
                "src_hash": src_hash(os.path.dirname(fetch)), "kernels": out}, sys.stdout, indent=1)
     print()
