@@ -161,6 +161,17 @@ int sbh_inflate(sbh_shard *sh, uint64_t *bad_block);
  * ISIZE, Stream.scala:47-54; SURVEY 8d asks for CRC32 as the in-run correctness check).
  * *n_bad = blocks whose CRC differs; *first_bad (optional) = the first one's file offset. */
 int sbh_verify_crc(sbh_shard *sh, uint64_t *n_bad, uint64_t *first_bad);
+/* Diagnostic (tests, performance triage; not part of the reference's interface): which decoder
+ * produced each of blocks [first, first + count), one byte per block in out.  Valid after
+ * sbh_inflate / sbh_run_shard (SBH_E_STATE otherwise).  The inflate path records nothing for it:
+ * the call runs the shard's Huffman stage again (not the LZ77 stage: the flat bytes stay as they
+ * are) and reads off which blocks the lane-parallel decoder hands on, so it costs about half an
+ * inflate.  Empty blocks and blocks below the lane-parallel decoder's size limit report
+ * SBH_PATH_SERIAL.  The block table (sbh_get_blocks) is unchanged by it. */
+#define SBH_PATH_PARALLEL 0 /* the lane-parallel Huffman decoder (with or without its tail kernel) */
+#define SBH_PATH_STORED 1   /* the payload is one stored deflate block: copied */
+#define SBH_PATH_SERIAL 2   /* the exact serial decoder */
+int sbh_inflate_paths(sbh_shard *sh, uint64_t first, uint64_t count, uint8_t *out);
 /* Copy flat bytes [flat, flat + n) to host memory. */
 int sbh_read_flat(sbh_shard *sh, uint64_t flat, uint64_t n, uint8_t *out);
 /* Device pointer of the flat bytes (read-only: the library keeps the zero pad past the flat

@@ -27,13 +27,14 @@ FULL_UNKNOWN = 0x40000000
 FULL_N_SHIFT = 20
 FULL_FLAGS_MASK = 0x7FFFF
 BLOCK_EMPTY, BLOCK_TRUNCATED = 1, 2
+PATH_PARALLEL, PATH_STORED, PATH_SERIAL = 0, 1, 2  # sbh_inflate_paths
 
 # Every symbol include/sparkbam.h declares (checked by tests/test_abi.py).
 EXPORTS = [
     "sbh_ctx_create", "sbh_ctx_destroy", "sbh_last_error", "sbh_last_error_detail", "sbh_ctx_set_stream",
     "sbh_ctx_synchronize", "sbh_version", "sbh_host_alloc", "sbh_host_free", "sbh_header_make", "sbh_shard_create",
     "sbh_shard_destroy", "sbh_shard_comp_device_ptr", "sbh_find_block_start", "sbh_index",
-    "sbh_get_blocks", "sbh_inflate", "sbh_read_flat", "sbh_flat_device_ptr", "sbh_flat_of",
+    "sbh_get_blocks", "sbh_inflate", "sbh_inflate_paths", "sbh_read_flat", "sbh_flat_device_ptr", "sbh_flat_of",
     "sbh_pos_of", "sbh_flat_bound", "sbh_set_contigs", "sbh_check_eager", "sbh_eager_bits", "sbh_check_full",
     "sbh_find_record_start", "sbh_count_records", "sbh_chain_from", "sbh_split", "sbh_split_starts",
     "sbh_check_records", "sbh_run_shard",
@@ -192,6 +193,7 @@ def lib():
         "sbh_get_blocks": [P, U64, U64, P],
         "sbh_inflate": [P, PU64],
         "sbh_read_flat": [P, U64, U64, P],
+        "sbh_inflate_paths": [P, U64, U64, P],
         "sbh_flat_of": [P, U64, U32, PU64],
         "sbh_pos_of": [P, U64, PU64, PU32],
         "sbh_flat_bound": [P, U64, PU64],

@@ -55,7 +55,6 @@ constexpr uint32_t LZ_THREADS = SBH_LZ_THREADS;
 #endif
 constexpr uint32_t LZ_SHORT = SBH_LZ_SHORT;  // longer matches get their pointers from the whole wave
 static_assert(LZ_SHORT <= 33, "k_lz finds a short match's start within 32 slots back");
-constexpr uint32_t NTOK_STORED = 0xffffffffu;  // ntok of a block whose payload is one stored deflate block
 constexpr uint32_t TOK_PAIR = 1u << 24;  // a literal token of two bytes (byte2 at [23:16])
 constexpr uint32_t TOK_MATCH = 0x80000000u;  // token: literal = byte << 8 (bit 31 clear); match = bit31 | len << 16 | dist
 
@@ -3356,27 +3355,32 @@ hipError_t launch_first_bad(const uint32_t *status, uint64_t n, unsigned long lo
 }
 
 hipError_t launch_huff(const uint8_t *comp, DevBlocks blocks, uint64_t nblocks, uint32_t *tok_buf, uint64_t tok_base,
-                       hipStream_t stream) {
+                       hipStream_t stream, uint32_t stages) {
   if (nblocks == 0) return hipSuccess;
   // the kernels index tokens by flat offset: tok[ustart_b] is block b's first token slot
   uint32_t *tok = reinterpret_cast<uint32_t *>(reinterpret_cast<uintptr_t>(tok_buf) - tok_base * 4);
-#ifdef SBH_HUFF_SERIAL
+#ifdef SBH_HUFF_SERIAL  // (the A/B baseline: no lane-parallel stage to run apart)
   const uint64_t grid = (nblocks + WAVES - 1) / WAVES;
-  hipLaunchKernelGGL(k_huff_serial<false>, dim3((uint32_t)grid), dim3(WAVES * WAVE), 0, stream, comp, blocks, nblocks,
-                     tok);
+  if (stages & HUFF_SERIAL)
+    hipLaunchKernelGGL(k_huff_serial<false>, dim3((uint32_t)grid), dim3(WAVES * WAVE), 0, stream, comp, blocks, nblocks,
+                       tok);
 #else
-  const dim3 hdr_grid((uint32_t)((nblocks + HDR_WAVES - 1) / HDR_WAVES)), hdr_wg(WAVE * HDR_WAVES);
-  hipLaunchKernelGGL(k_hdr<false>, hdr_grid, hdr_wg, 0, stream, comp, blocks, nblocks, tok);
-  hipLaunchKernelGGL(k_huff, dim3((uint32_t)nblocks), dim3(HT), 0, stream, comp, blocks, nblocks, tok);
+  if (stages & HUFF_FAST) {
+    const dim3 hdr_grid((uint32_t)((nblocks + HDR_WAVES - 1) / HDR_WAVES)), hdr_wg(WAVE * HDR_WAVES);
+    hipLaunchKernelGGL(k_hdr<false>, hdr_grid, hdr_wg, 0, stream, comp, blocks, nblocks, tok);
+    hipLaunchKernelGGL(k_huff, dim3((uint32_t)nblocks), dim3(HT), 0, stream, comp, blocks, nblocks, tok);
 #if SBH_TAIL
 #if SBH_TAIL_HDR
-  hipLaunchKernelGGL(k_hdr<true>, hdr_grid, hdr_wg, 0, stream, comp, blocks, nblocks, tok);
+    hipLaunchKernelGGL(k_hdr<true>, hdr_grid, hdr_wg, 0, stream, comp, blocks, nblocks, tok);
 #endif
-  hipLaunchKernelGGL(k_huff_tail, dim3((uint32_t)nblocks), dim3(TAIL_NT), 0, stream, comp, blocks, nblocks, tok);
+    hipLaunchKernelGGL(k_huff_tail, dim3((uint32_t)nblocks), dim3(TAIL_NT), 0, stream, comp, blocks, nblocks, tok);
 #endif
-  const uint64_t grid = (nblocks + WAVES - 1) / WAVES;
-  hipLaunchKernelGGL(k_huff_serial<true>, dim3((uint32_t)grid), dim3(WAVES * WAVE), 0, stream, comp, blocks, nblocks,
-                     tok);
+  }
+  if (stages & HUFF_SERIAL) {
+    const uint64_t grid = (nblocks + WAVES - 1) / WAVES;
+    hipLaunchKernelGGL(k_huff_serial<true>, dim3((uint32_t)grid), dim3(WAVES * WAVE), 0, stream, comp, blocks, nblocks,
+                       tok);
+  }
 #endif
   return hipGetLastError();
 }

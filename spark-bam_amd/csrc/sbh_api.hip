@@ -1077,6 +1077,42 @@ int sbh_verify_crc(sbh_shard *sh, uint64_t *n_bad, uint64_t *first_bad) {
   return SBH_OK;
 }
 
+// Which decoder produced each block's tokens (a diagnostic).  Nothing on the inflate path records
+// it (a mark stored by k_huff_serial measured 0.35 % of config B's step), so it is derived again:
+// the lane-parallel stage runs once more over the shard (the same kernels over the same bytes: the
+// same decisions), the statuses it leaves say which blocks it hands to the serial decoder and the
+// token counts which are stored copies, and the serial stage then puts status and ntok back as
+// sbh_inflate left them.  The flat bytes are not touched.
+int sbh_inflate_paths(sbh_shard *sh, uint64_t first, uint64_t count, uint8_t *out) {
+  if (!sh || (!out && count)) return SBH_E_ARG;
+  sbh_ctx *ctx = sh->ctx;
+  if (!sh->inflated) return fail(ctx, SBH_E_STATE, "inflate_paths before inflate");
+  if (first > sh->nblocks || count > sh->nblocks - first) return SBH_E_ARG;
+  if (!count) return SBH_OK;
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  hipStream_t st = sh->st;
+  const TokPlan P = tok_plan(sh, ~0ull);
+  HIPCHK(ctx, sh->tok.ensure(P.tok_len));
+  std::vector<uint32_t> h(2 * sh->nblocks);
+  uint32_t *hst = h.data(), *hnt = h.data() + sh->nblocks;
+  for (const auto &bt : P.batches) {  // (a batch's statuses are read before the next reuses the tokens)
+    const DevBlocks d = blocks_from(sh->dev_blocks(), bt.first);
+    const uint64_t base = P.reuse ? sh->hb[bt.first].ustart : 0, nb = bt.second - bt.first;
+    if (!nb) continue;
+    HIPCHK(ctx, launch_huff(sh->comp.p, d, nb, sh->tok.p, base, st, HUFF_FAST));
+    HIPCHK(ctx, hipMemcpyAsync(hst + bt.first, d.status, nb * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(hnt + bt.first, d.ntok, nb * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, launch_huff(sh->comp.p, d, nb, sh->tok.p, base, st, HUFF_SERIAL));
+  }
+  HIPCHK(ctx, hipStreamSynchronize(st));
+  for (uint64_t i = 0; i < count; ++i) {
+    const uint64_t b = first + i;
+    out[i] = hst[b] == INF_SERIAL ? SBH_PATH_SERIAL : hnt[b] == NTOK_STORED ? SBH_PATH_STORED : SBH_PATH_PARALLEL;
+  }
+  return SBH_OK;
+}
+
 int sbh_read_flat(sbh_shard *sh, uint64_t flat, uint64_t n, uint8_t *out) {
   if (!sh || (!out && n)) return SBH_E_ARG;
   if (!sh->inflated) return fail(sh->ctx, SBH_E_STATE, "not inflated");

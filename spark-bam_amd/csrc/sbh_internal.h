@@ -75,6 +75,7 @@ constexpr uint32_t INF_SIZE = 1;      // fewer than ISIZE bytes produced
 constexpr uint32_t INF_DATA = 2;      // DataFormatException (zlib Z_DATA_ERROR)
 constexpr uint32_t INF_BAD_ISIZE = 3; // ISIZE outside [0, 65536]
 constexpr uint32_t INF_SERIAL = 0xffu; // (inside inflate only) left to the serial decoder
+constexpr uint32_t NTOK_STORED = 0xffffffffu;  // ntok of a block whose payload is one stored deflate block
 
 // Eager tile geometry (check.hip): a workgroup decides ETILE positions and stages those
 // plus a look-ahead; EAGER_REACH bounds the flat bytes past a tile's first position
@@ -116,8 +117,11 @@ constexpr uint32_t WPRE_GROUP = 16;
 // of token scratch per flat byte of the launched blocks, tok_buf[0] standing for flat offset
 // tok_base (block b's tokens at tok_buf[ustart_b - tok_base ...]), so a shard can be inflated
 // in batches of blocks that reuse one bounded token buffer.
+// stages: the lane-parallel kernels, which leave INF_SERIAL in the status of a block they do not
+// finish, and the serial decoder behind them (sbh_inflate_paths runs the two apart).
+constexpr uint32_t HUFF_FAST = 1u, HUFF_SERIAL = 2u;
 hipError_t launch_huff(const uint8_t *comp, DevBlocks blocks, uint64_t nblocks, uint32_t *tok_buf, uint64_t tok_base,
-                       hipStream_t stream);
+                       hipStream_t stream, uint32_t stages = HUFF_FAST | HUFF_SERIAL);
 // sieve (optional): bit p of the flat bitmap = position p may pass eager.Checker's refID / next
 // refID range and pos / next pos sign tests (k_eager's first filter, evaluated by k_lz on the bytes
 // still in its LDS ring; 1 wherever the block's WG cannot decide: seams, stored blocks).  nref1 =

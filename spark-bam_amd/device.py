@@ -317,6 +317,14 @@ class Shard:
         bad = C.c_uint64()
         self._c(lib().sbh_inflate(self.h, C.byref(bad)))
 
+    def inflate_paths(self):
+        """Which decoder produced each indexed block (numpy.uint8 per block: 0 lane-parallel,
+        1 stored copy, 2 serial) -- sbh_inflate_paths, a diagnostic."""
+        out = np.zeros(self.n_blocks, dtype=np.uint8)
+        if self.n_blocks:
+            self._c(lib().sbh_inflate_paths(self.h, 0, self.n_blocks, _ptr(out)))
+        return out
+
     def verify_crc(self):
         """(blocks whose footer CRC32 differs from their inflated bytes, first such block's
         file offset) -- sbh_verify_crc."""
