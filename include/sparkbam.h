@@ -464,6 +464,48 @@ int sbh_split_records(sbh_shard *sh, uint64_t start, uint64_t end, int32_t bgzf_
                       int32_t reads_to_check, int32_t max_read_size, int32_t decode,
                       sbh_split_records_result *out);
 
+/* Many FileSplits of loadReadsAndPositions in ONE call: split i = [starts[i], ends[i]) (file
+ * offsets, ascending, starts[i] < ends[i] <= starts[i + 1], starts[0] inside the shard; anything
+ * else is SBH_E_ARG), a Spark executor's concurrent tasks (or a prefetch of the next K splits)
+ * served by one pass over their bytes instead of one pass each.  FindBlockStart(starts[0]), then
+ * index + inflate + eager check + chain proof once from that block to Pos(ends[n - 1], 0)
+ * (sbh_run_shard), every split's FindBlockStart / FindRecordStart / count as sbh_split_starts, the
+ * record starts of all splits in one launch set whose launch count does not grow with n, and one
+ * decode over all of them.  Every split answers what sbh_split_records answers for it alone on a
+ * shard loaded from starts[i] to the same resident end: (status, block_start, first_vpos,
+ * rec_count) and the records.  status is per split -- SBH_OK (rec_count may be 0: an empty
+ * split), SBH_E_NO_READ_FOUND {block_start, maxReadSize}, SBH_E_HEADER_SEARCH_FAILED {starts[i],
+ * 65536}, SBH_E_NEED_HALO when that split's answer needs bytes past an open shard end -- and the
+ * splits with status SBH_OK have their records whatever the others answer.  The call itself fails
+ * when the shared pass fails (inflate errors), with SBH_E_BAD_RECORD when a record of the batch is
+ * malformed, and with SBH_E_NEED_HALO when the last record of the batch runs past an open shard
+ * end (decode == 0 checks that too, so both modes answer the same statuses).
+ * Afterwards sbh_records_fetch serves the batch's columns (vpos included; decode == 0: `flat`
+ * and `vpos` only): the splits' records in split order, split i owning rows [rec_begin,
+ * rec_begin + rec_count); `flat` offsets are the batch's (flat 0 = Pos(out->block_start, 0)), as
+ * are first_flat / owned_flat.  host_path: the split was decided by sbh_split's exact path (an
+ * empty block in the way, a search leaving the bitmap); its record starts are walked along the
+ * chain into its rows.  out->n_host counts them. */
+typedef struct {
+  uint64_t block_start;  /* FindBlockStart(starts[i]) (status SBH_OK / SBH_E_NO_READ_FOUND)      */
+  uint64_t first_flat;   /* first record (batch flat; when rec_count > 0)                        */
+  uint64_t first_vpos;   /* its htsjdk virtual position (when rec_count > 0)                     */
+  uint64_t owned_flat;   /* flat image of Pos(ends[i], 0)                                        */
+  uint64_t rec_begin, rec_count; /* rows [rec_begin, rec_begin + rec_count) of the batch's columns */
+  int32_t status, host_path;
+} sbh_batch_split;
+typedef struct {
+  uint64_t block_start;     /* FindBlockStart of the first split that has one: flat 0            */
+  uint64_t n_blocks;        /* blocks indexed from it                                           */
+  uint64_t flat_size;       /* their uncompressed bytes                                         */
+  uint64_t n_true;          /* eager-true positions below Pos(ends[n - 1], 0)                   */
+  uint64_t n_host;          /* splits with host_path = 1                                        */
+  sbh_records_sizes sizes;  /* sizes.n = records of all splits; column sizes when decoded       */
+} sbh_split_batch_result;
+int sbh_split_records_batch(sbh_shard *sh, const uint64_t *starts, const uint64_t *ends, uint64_t n,
+                            int32_t bgzf_blocks_to_check, int32_t reads_to_check, int32_t max_read_size,
+                            int32_t decode, sbh_batch_split *splits, sbh_split_batch_result *out);
+
 /* ---- loadBamIntervals ----
  * CanLoadBam.loadBamIntervals (load/.../CanLoadBam.scala:78-154) after the host has turned
  * the intervals into BAI chunks (getIntevalChunks, :410-444; Index.scala:11-93): for each

@@ -118,6 +118,14 @@ object Native {
     * flatSize, ownedFlat, firstFlat, firstVpos, nTrue, nRecords, nameBytes, cigarOps, bases, auxBytes} */
   @native def splitRecords(ctx: Long, sh: Long, start: Long, end: Long, blocksToCheck: Int, readsToCheck: Int,
                            maxReadSize: Int, decode: Boolean, out: Array[Long]): Unit
+  /** sbh_split_records_batch: many FileSplits of one shard in one call (one pass over their bytes).
+    * splitOut = 8 longs per split {status, hostPath, blockStart, firstFlat, firstVpos, ownedFlat, recBegin,
+    * recCount}: a split's own failure is its status (SBH_E_*), not an exception; out = {blockStart, nBlocks,
+    * flatSize, nTrue, nHost, nRecords, nameBytes, cigarOps, bases, auxBytes}; recordsFetch then serves the
+    * batch's columns, split i owning rows [recBegin, recBegin + recCount) */
+  @native def splitRecordsBatch(ctx: Long, sh: Long, starts: Array[Long], ends: Array[Long], blocksToCheck: Int,
+                                readsToCheck: Int, maxReadSize: Int, decode: Boolean, splitOut: Array[Long],
+                                out: Array[Long]): Unit
   /** out = {nRecords, nameBytes, cigarOps, bases, auxBytes} */
   @native def recordsScan(ctx: Long, sh: Long, first: Long, endFlat: Long, out: Array[Long]): Unit
   /** 18 (or 19, + vpos) direct buffers in sbh_records_out order, sized from recordsScan's `sizes` */

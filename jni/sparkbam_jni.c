@@ -500,6 +500,48 @@ JNIEXPORT void JNICALL Java_org_hammerlab_bam_gpu_Native_00024_splitRecords(JNIE
   put_longs(env, out, v, 12);
 }
 
+/* Many FileSplits of one shard in one call (sbh_split_records_batch): starts/ends file offsets;
+ * splitOut = 8 longs per split {status, hostPath, blockStart, firstFlat, firstVpos, ownedFlat,
+ * recBegin, recCount} (a split's own failure is its status, not an exception); out = {blockStart,
+ * nBlocks, flatSize, nTrue, nHost, n, nameBytes, cigarOps, bases, auxBytes}; out[5..9] are
+ * recordsFetch's sizes, split i owning rows [recBegin, recBegin + recCount) */
+JNIEXPORT void JNICALL Java_org_hammerlab_bam_gpu_Native_00024_splitRecordsBatch(
+    JNIEnv *env, jobject self, jlong ctx, jlong sh, jlongArray starts, jlongArray ends, jint blocksToCheck,
+    jint readsToCheck, jint maxReadSize, jboolean decode, jlongArray splitOut, jlongArray out) {
+  const jsize n = (*env)->GetArrayLength(env, starts);
+  if (n <= 0 || (*env)->GetArrayLength(env, ends) != n || (*env)->GetArrayLength(env, splitOut) < 8 * n) {
+    throw_arg(env, "splitRecordsBatch: starts / ends of different lengths, or splitOut under 8 longs per split");
+    return;
+  }
+  uint64_t *se = (uint64_t *)malloc(sizeof(uint64_t) * 2 * (size_t)n);
+  sbh_batch_split *sp = (sbh_batch_split *)malloc(sizeof(sbh_batch_split) * (size_t)n);
+  jlong *v = (jlong *)malloc(sizeof(jlong) * 8 * (size_t)n);
+  if (se && sp && v) {
+    (*env)->GetLongArrayRegion(env, starts, 0, n, (jlong *)se);
+    (*env)->GetLongArrayRegion(env, ends, 0, n, (jlong *)(se + n));
+    sbh_split_batch_result r;
+    if (!failed(env, ctx, sbh_split_records_batch(SH(sh), se, se + n, (uint64_t)n, blocksToCheck, readsToCheck,
+                                                  maxReadSize, decode ? 1 : 0, sp, &r))) {
+      for (jsize i = 0; i < n; ++i) {
+        jlong *o = v + 8 * i;
+        o[0] = sp[i].status, o[1] = sp[i].host_path, o[2] = (jlong)sp[i].block_start;
+        o[3] = (jlong)sp[i].first_flat, o[4] = (jlong)sp[i].first_vpos, o[5] = (jlong)sp[i].owned_flat;
+        o[6] = (jlong)sp[i].rec_begin, o[7] = (jlong)sp[i].rec_count;
+      }
+      put_longs(env, splitOut, v, 8 * n);
+      jlong w[10] = {(jlong)r.block_start, (jlong)r.n_blocks, (jlong)r.flat_size, (jlong)r.n_true, (jlong)r.n_host,
+                     (jlong)r.sizes.n, (jlong)r.sizes.name_bytes, (jlong)r.sizes.cigar_ops, (jlong)r.sizes.bases,
+                     (jlong)r.sizes.aux_bytes};
+      put_longs(env, out, w, 10);
+    }
+  } else {
+    throw_status(env, NULL, SBH_E_NOMEM);
+  }
+  free(se);
+  free(sp);
+  free(v);
+}
+
 JNIEXPORT void JNICALL Java_org_hammerlab_bam_gpu_Native_00024_recordsFetch(JNIEnv *env, jobject self, jlong ctx,
                                                                             jlong sh, jlongArray sizes,
                                                                             jobjectArray cols) {

@@ -40,7 +40,7 @@ EXPORTS = [
     "sbh_check_records", "sbh_run_shard",
     "sbh_stage_times", "sbh_run_stream", "sbh_run_stream2", "sbh_records_scan", "sbh_records_fetch", "sbh_records_scan_regions", "sbh_verify_crc",
     "sbh_bgzf_compress_bound", "sbh_bgzf_compress", "sbh_bgzf_compress_level",
-    "sbh_shard_load", "sbh_find_blocks", "sbh_check_stream", "sbh_split_records",
+    "sbh_shard_load", "sbh_find_blocks", "sbh_check_stream", "sbh_split_records", "sbh_split_records_batch",
 ]
 LEVEL_HTSJDK, LEVEL_FAST = 5, -1  # sbh_bgzf_compress_level: htsjdk's zlib level 5 / this library's own coder
 
@@ -98,6 +98,17 @@ class SbhSplitRecordsResult(C.Structure):
     _fields_ = [("block_start", C.c_uint64), ("n_blocks", C.c_uint64), ("flat_size", C.c_uint64),
                 ("owned_flat", C.c_uint64), ("first_flat", C.c_uint64),
                 ("first_vpos", C.c_uint64), ("n_true", C.c_uint64), ("sizes", SbhRecordsSizes)]
+
+
+class SbhBatchSplit(C.Structure):  # sbh_batch_split: one split of sbh_split_records_batch
+    _fields_ = [("block_start", C.c_uint64), ("first_flat", C.c_uint64), ("first_vpos", C.c_uint64),
+                ("owned_flat", C.c_uint64), ("rec_begin", C.c_uint64), ("rec_count", C.c_uint64),
+                ("status", C.c_int32), ("host_path", C.c_int32)]
+
+
+class SbhSplitBatchResult(C.Structure):
+    _fields_ = [("block_start", C.c_uint64), ("n_blocks", C.c_uint64), ("flat_size", C.c_uint64),
+                ("n_true", C.c_uint64), ("n_host", C.c_uint64), ("sizes", SbhRecordsSizes)]
 
 
 class SbhRecordsOut(C.Structure):  # host buffers (sbh_records_out); NULL = not copied
@@ -215,6 +226,8 @@ def lib():
         "sbh_records_scan": [P, U64, U64, C.POINTER(SbhRecordsSizes)],
         "sbh_records_fetch": [P, C.POINTER(SbhRecordsOut)],
         "sbh_split_records": [P, U64, U64, I32, I32, I32, I32, C.POINTER(SbhSplitRecordsResult)],
+        "sbh_split_records_batch": [P, P, P, U64, I32, I32, I32, I32, C.POINTER(SbhBatchSplit),
+                                    C.POINTER(SbhSplitBatchResult)],
         "sbh_records_scan_regions": [P, P, P, U64, P, P, P, C.c_uint32, C.POINTER(SbhRecordsSizes)],
         "sbh_verify_crc": [P, PU64, PU64],
         "sbh_shard_load": [P, P, U64, U64, C.c_int],

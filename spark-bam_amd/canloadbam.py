@@ -13,11 +13,12 @@ positionsAttempted) from FindBlockStart, NoReadFoundException(path, blockStart, 
 FindRecordStart (check/.../spark/FindRecordStart.scala:11-30,66-71).
 """
 import os
+import time
 
 import numpy as np
 
-from ._lib import (SBH_E_BAD_RECORD, SBH_E_NEED_HALO, SBH_E_NOT_FOUND, HeaderSearchFailedException,
-                   NoReadFoundException, SparkBamError)
+from ._lib import (SBH_E_BAD_RECORD, SBH_E_HEADER_SEARCH_FAILED, SBH_E_NEED_HALO, SBH_E_NO_READ_FOUND, SBH_E_NOT_FOUND,
+                   SBH_OK, HeaderSearchFailedException, NoReadFoundException, SparkBamError, error_for)
 from .api import (DEFAULT_BGZF_BLOCKS_TO_CHECK, DEFAULT_MAX_READ_SIZE, DEFAULT_READS_TO_CHECK, Pos, Split,
                   file_splits)
 from .api import DEFAULT_SPLIT_SIZE as DEFAULT_MAX_SPLIT_SIZE
@@ -25,7 +26,7 @@ from .device import Context, PinnedBuffer
 from .intervals import (DEFAULT_COMPRESSION_RATIO, _flat_of_pos, capped_cost_groups, chunk_size,
                         get_interval_chunks, parse_loci, read_bai)
 from .intervals import DEFAULT_SPLIT_SIZE
-from .records import Reads, record_columns
+from .records import Reads, record_columns, slice_columns
 
 
 def _reader(path):
@@ -107,6 +108,64 @@ class SplitWorker:
                 continue
             self.last = info  # (cols["vpos"]: the starts' virtual positions, from the device)
             return cols
+
+    def split_batch(self, read, path, splits, bgzf_blocks_to_check=DEFAULT_BGZF_BLOCKS_TO_CHECK,
+                    reads_to_check=DEFAULT_READS_TO_CHECK, max_read_size=DEFAULT_MAX_READ_SIZE, decode=True,
+                    halo0=1 << 20):
+        """Several FileSplits [(start, end), ...] (ascending) as one batch: their bytes
+        [start_0, min(size, end_last + halo)) are loaded once and one library call
+        (sbh_split_records_batch) answers every split; the halo grows x4 while an answer needs
+        bytes past it, like split().  Returns one column dict per split -- what split() returns
+        for it, `flat` counted from the split's own first block.  A failing split raises what
+        split() raises for it, the first in split order."""
+        lo, hi = splits[0][0], splits[-1][1]
+        halo = halo0
+        while True:
+            sh = self.load(read, lo, min(self.size, hi + halo))
+            can_grow = hi + halo < self.size
+            try:
+                info, per, cols = sh.split_records_batch(splits, bgzf_blocks_to_check, reads_to_check,
+                                                         max_read_size, decode,
+                                                         flat_out=None if decode else self._flat_buf)
+            except SparkBamError as e:
+                if e.code not in (SBH_E_NEED_HALO, SBH_E_NOT_FOUND, SBH_E_BAD_RECORD) or not can_grow:
+                    raise
+                halo *= 4
+                continue
+            bad = next((i for i, s in enumerate(per) if s["status"] != SBH_OK), None)
+            if bad is not None:
+                code = per[bad]["status"]
+                if code in (SBH_E_NEED_HALO, SBH_E_NOT_FOUND, SBH_E_BAD_RECORD) and can_grow:
+                    halo *= 4
+                    continue
+                if code == SBH_E_HEADER_SEARCH_FAILED:
+                    start = splits[bad][0]
+                    raise error_for(code, f"no BGZF block start in [{start}, {start + 65536})",
+                                    (start, 65536)).with_path(path)
+                if code == SBH_E_NO_READ_FOUND:
+                    raise error_for(code, f"Failed to find a valid read-start in {max_read_size} attempts from "
+                                          f"{per[bad]['block_start']}",
+                                    (per[bad]["block_start"], max_read_size)).with_path(path)
+                raise SparkBamError(code, f"split {splits[bad]} of the batch")
+            self.last_batch = info
+            t0 = time.perf_counter()
+            # one column dict per split: views of the batch's arrays (the decoded columns arrive in
+            # arrays of this call's own; the starts leave the landing buffer in one pass that also
+            # recounts `flat` from the split's own first block)
+            if not decode:
+                land, cols = cols, {"flat": np.empty(info["n"], np.uint64), "vpos": cols["vpos"].copy()}
+            out = []
+            for s in per:
+                a, n = s["rec_begin"], s["rec_count"]
+                if not n:
+                    out.append(_empty() if decode else {"flat": np.zeros(0, np.uint64), "vpos": np.zeros(0, np.uint64)})
+                    continue
+                base = np.uint64(sh.flat_of(s["block_start"]))
+                c = slice_columns(cols, a, a + n, copy=False)
+                np.subtract(cols["flat"][a:a + n] if decode else land["flat"][a:a + n], base, out=c["flat"])
+                out.append(c)
+            info["ms_slice"] = 1e3 * (time.perf_counter() - t0)  # (the per-split copies out of the batch)
+            return out
 
     def _flat_buf(self, n):
         """n u64 slots of the worker's page-locked landing buffer (the record starts' copy-out
@@ -198,10 +257,12 @@ def split_partition_calls(ctx, read, size, path, start, end, contigs, bgzf_block
 def load_reads_and_positions(path, split_size=DEFAULT_MAX_SPLIT_SIZE,
                              bgzf_blocks_to_check=DEFAULT_BGZF_BLOCKS_TO_CHECK,
                              reads_to_check=DEFAULT_READS_TO_CHECK, max_read_size=DEFAULT_MAX_READ_SIZE, ctx=None,
-                             threads=1):
+                             threads=1, batch=1):
     """GpuCanLoadBam.loadReadsAndPositions: one partition per FileSplit, each a Reads batch
     (its vpos column = the reference's Pos keys).  threads > 1 runs the splits on that many
-    concurrent task threads sharing the context (a Spark executor's cores)."""
+    concurrent task threads sharing the context (a Spark executor's cores).  batch = K > 1 (or
+    "all") hands a worker K consecutive FileSplits at a time (SplitWorker.split_batch: one load,
+    one library call); the result is still one Reads per FileSplit."""
     from .sharded import read_header
     read, name = _reader(path)
     size = read.size
@@ -211,6 +272,10 @@ def load_reads_and_positions(path, split_size=DEFAULT_MAX_SPLIT_SIZE,
         names, lens, _ = read_header(ctx, read, size)
         splits = file_splits(size, split_size)
         parts = [None] * len(splits)
+        if batch == "all" or int(batch) > 1:
+            _load_batched(ctx, read, size, name, lens, names, splits, parts, bgzf_blocks_to_check, reads_to_check,
+                          max_read_size, threads, len(splits) if batch == "all" else int(batch))
+            return parts
         if threads <= 1:
             w = SplitWorker(ctx, size, lens)
             try:
@@ -256,20 +321,60 @@ def load_reads_and_positions(path, split_size=DEFAULT_MAX_SPLIT_SIZE,
             ctx.close()
 
 
+def _load_batched(ctx, read, size, name, lens, names, splits, parts, bgzf_blocks_to_check, reads_to_check,
+                  max_read_size, threads, k):
+    """load_reads_and_positions with batch = k: groups of k consecutive FileSplits, taken in order
+    by `threads` task threads (each with its own worker), every group one split_batch."""
+    import threading
+    groups = [range(i, min(i + k, len(splits))) for i in range(0, len(splits), k)]
+    nxt = iter(groups)
+    lock = threading.Lock()
+    errors = []
+
+    def task():
+        w = SplitWorker(ctx, size, lens)
+        g = None
+        try:
+            while True:
+                with lock:
+                    g = next(nxt, None)
+                if g is None or errors:
+                    return
+                cols = w.split_batch(read, name, [splits[i] for i in g], bgzf_blocks_to_check, reads_to_check,
+                                     max_read_size)
+                for i, c in zip(g, cols):
+                    parts[i] = Reads(c, names)
+        except BaseException as e:  # (re-raised on the calling thread)
+            errors.append((g[0] if g is not None else 0, e))
+        finally:
+            w.close()
+
+    if threads <= 1:
+        task()
+    else:
+        ts = [threading.Thread(target=task) for _ in range(threads)]
+        for t in ts:
+            t.start()
+        for t in ts:
+            t.join()
+    if errors:
+        raise min(errors, key=lambda x: x[0])[1]  # (the first failing split in split order)
+
+
 def load_bam(path, split_size=DEFAULT_MAX_SPLIT_SIZE, bgzf_blocks_to_check=DEFAULT_BGZF_BLOCKS_TO_CHECK,
-             reads_to_check=DEFAULT_READS_TO_CHECK, max_read_size=DEFAULT_MAX_READ_SIZE, ctx=None, threads=1):
+             reads_to_check=DEFAULT_READS_TO_CHECK, max_read_size=DEFAULT_MAX_READ_SIZE, ctx=None, threads=1, batch=1):
     """GpuCanLoadBam.loadBam = loadReadsAndPositions(...).values: the partitions' records."""
     return load_reads_and_positions(path, split_size, bgzf_blocks_to_check, reads_to_check, max_read_size, ctx,
-                                    threads)
+                                    threads, batch)
 
 
 def load_splits_and_reads(path, split_size=DEFAULT_MAX_SPLIT_SIZE, bgzf_blocks_to_check=DEFAULT_BGZF_BLOCKS_TO_CHECK,
                           reads_to_check=DEFAULT_READS_TO_CHECK, max_read_size=DEFAULT_MAX_READ_SIZE, ctx=None,
-                          threads=1):
+                          threads=1, batch=1):
     """GpuCanLoadBam.loadSplitsAndReads (CanLoadBam.scala:268-302): BAMRecordRDD(splits, reads),
     splits = the first record of every non-empty partition, sliding2 with Pos(fileSize, 0)."""
     parts = load_reads_and_positions(path, split_size, bgzf_blocks_to_check, reads_to_check, max_read_size, ctx,
-                                     threads)
+                                     threads, batch)
     size = _reader(path)[0].size
     firsts = [Pos.from_htsjdk(int(p.cols["vpos"][0])) for p in parts if p.n]
     splits = [Split(a, b) for a, b in zip(firsts, firsts[1:] + [Pos(size, 0)])]

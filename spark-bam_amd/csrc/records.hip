@@ -88,6 +88,100 @@ __global__ __launch_bounds__(WP_T) void k_word_prefix(const uint32_t *bits, uint
   if (r0 < nw) wpre[r0 / WP_WPT] = cpre[blockIdx.x] + before + incl - mine;  // (the group's prefix)
 }
 
+// ---- record starts of many flat ranges at once (sbh_split_records_batch) ----
+// n ranges [first[i], E[i]) over one bitmap, sorted and disjoint: first[] and E[] are both
+// non-decreasing, first[i] <= E[i] <= first[i + 1] (first[i] == E[i]: an empty range), all
+// inside the union [U0, U1) whose word prefix (k_chunk_popcounts / k_word_prefix with first = U0,
+// E = U1) is wpre.  Bits of the union that lie in no range (the gaps) count in wpre and are
+// dropped by the expansion.
+
+// Set bits of [U0, x) for U0 <= x <= U1: the group's prefix, the group's earlier words, and the
+// bits of x's word below x.
+__device__ __forceinline__ uint64_t union_rank(const uint32_t *bits, uint64_t begin, uint64_t U0, uint64_t U1,
+                                               const uint64_t *wpre, uint64_t x) {
+  const uint64_t wb = (U0 - begin) / 32, nw = (U1 - begin + 31) / 32 - wb;
+  const uint64_t r = (x - begin) / 32 - wb;              // x's word, relative (== nw when x is the union's end
+  const uint64_t g = (r < nw ? r : nw - 1) / WPRE_GROUP;  //  on a word boundary: the last group, all its words)
+  uint64_t c = wpre[g];
+  for (uint64_t k = g * WPRE_GROUP; k < r; ++k) c += __popc(masked_word(bits, begin, U0, U1, wb + k));
+  const uint32_t below = (uint32_t)((x - begin) & 31);
+  if (below) c += __popc(masked_word(bits, begin, U0, U1, wb + r) & ((1u << below) - 1u));
+  return c;
+}
+
+// A thread per range: rbase[i] = set bits of the union before first[i], cnt[i] = set bits of
+// the range plus reserve[i] (rows kept free behind the range's own: an empty range whose records
+// another kernel writes); cnt[n] = 0, so the exclusive scan of cnt[0..n] ends with the total.
+__global__ void k_range_counts(const uint32_t *bits, uint64_t begin, uint64_t U0, uint64_t U1, const uint64_t *wpre,
+                               const uint64_t *first, const uint64_t *E, const uint64_t *reserve, uint64_t n,
+                               uint64_t *rbase, uint64_t *cnt) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > n) return;
+  if (i == n) {
+    cnt[n] = 0;
+    return;
+  }
+  const uint64_t a = first[i], b = E[i];
+  const uint64_t ra = union_rank(bits, begin, U0, U1, wpre, a);
+  rbase[i] = ra;
+  cnt[i] = (b > a ? union_rank(bits, begin, U0, U1, wpre, b) - ra : 0) + reserve[i];
+}
+
+// A lane per bitmap word of the union, a wave per 64 words (4 prefix groups): the wave's base is
+// its first group's prefix, a lane's the wave scan of the popcounts before it.  A lane whose
+// word has set bits finds the first range ending after the word's first position (binary search
+// over E) and walks the ranges the word intersects -- one in general; two or more where ranges
+// meet (or lie) inside the word.  Bit b of range i goes to pos[off[i] + its rank in the range]:
+// consecutive set bits of a range are consecutive 8-byte stores across the wave's lanes.
+// Nothing is written at or past cap.
+__global__ __launch_bounds__(256) void k_ranges_positions(const uint32_t *bits, uint64_t begin, uint64_t U0,
+                                                          uint64_t U1, const uint64_t *wpre, const uint64_t *first,
+                                                          const uint64_t *E, uint64_t n, const uint64_t *rbase,
+                                                          const uint64_t *off, uint64_t cap, uint64_t *pos) {
+  const uint64_t wb = (U0 - begin) / 32, nw = (U1 - begin + 31) / 32 - wb;
+  const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;  // relative word
+  const uint64_t r_wave = r & ~(uint64_t)(WAVE - 1);
+  if (r_wave >= nw) return;  // (whole waves only: every lane of a live wave takes part in the scan)
+  const uint32_t v = masked_word(bits, begin, U0, U1, wb + r);  // (0 past the union's last word)
+  const uint32_t pc = __popc(v);
+  const uint64_t base = wpre[r_wave / WPRE_GROUP] + (wave_incl_scan(pc) - pc);
+  if (!v) return;
+  const uint64_t p0 = begin + 32 * (wb + r);
+  uint64_t lo = 0, hi = n;  // first range with E > p0
+  while (lo < hi) {
+    const uint64_t m = (lo + hi) >> 1;
+    if (E[m] <= p0) lo = m + 1;
+    else hi = m;
+  }
+  for (uint64_t i = lo; i < n && first[i] < p0 + 32; ++i) {
+    const uint64_t a = first[i], b = E[i];
+    if (a >= b) continue;
+    uint32_t m = v;
+    if (a > p0) m &= ~0u << (uint32_t)(a - p0);
+    if (b < p0 + 32) m &= (1u << (uint32_t)(b - p0)) - 1u;
+    const uint64_t o = off[i] - rbase[i] + base;  // (rank in the union -> slot of range i)
+    while (m) {
+      const uint32_t bit = (uint32_t)__builtin_ctz(m);
+      const uint64_t at = o + __popc(v & ((1u << bit) - 1u));
+      if (at < cap) pos[at] = p0 + bit;
+      m &= m - 1;
+    }
+  }
+}
+
+// Every record lies inside its stream segment (an empty block ends the stream: a record running
+// over a segment's end is htsjdk's truncated record).  bad = the first such record's row.
+__global__ void k_rec_seg_check(const uint8_t *U, const uint64_t *pos, uint64_t n, const uint64_t *seg_end,
+                                uint32_t nseg, unsigned long long *bad) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t p = pos[i];
+  uint64_t seg = seg_end[nseg - 1];
+  for (uint32_t k = 0; k < nseg; ++k)
+    if (seg_end[k] > p) { seg = seg_end[k]; break; }
+  if (p + 4 > seg || (int64_t)p + 4 + (int32_t)rd_u32(U, p) > (int64_t)seg) atomicMin(bad, (unsigned long long)i);
+}
+
 // Sequential chain from first while the start is < E (fallback when no verified bitmap).
 __global__ void k_chain_positions(const uint8_t *U, uint64_t first, uint64_t E, uint64_t total, uint64_t cap,
                                   uint64_t *pos) {
@@ -259,6 +353,39 @@ hipError_t launch_rec_positions_bits(const uint32_t *bits, uint64_t begin, uint6
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_word_prefix, dim3((uint32_t)nch), dim3(WP_T), 0, st, bits, begin, first, E, cnt + nch, wpre);
   hipLaunchKernelGGL(k_bits_positions, dim3(g), dim3(256), 0, st, bits, begin, first, E, wpre, pos);
+  return hipGetLastError();
+}
+
+// Record starts of n sorted, disjoint ranges (see k_ranges_positions) in six launches (a scan
+// over more values than one workgroup takes adds two per level), not one set per range:
+// the word prefix once over the union [U0, U1) (cnt, wpre, tmp as launch_rec_positions_bits; tmp
+// also scan_tmp_words(n + 1)), each range's base and count, their exclusive prefix off[0..n], and
+// the expansion into pos (capacity cap).  reserve, rbase: n, rcnt and off: n + 1 words.
+hipError_t launch_rec_positions_ranges(const uint32_t *bits, uint64_t begin, uint64_t U0, uint64_t U1,
+                                       const uint64_t *first, const uint64_t *E, const uint64_t *reserve, uint64_t n,
+                                       uint64_t *cnt, uint64_t *wpre, uint64_t *tmp, uint64_t *rbase, uint64_t *rcnt,
+                                       uint64_t *off, uint64_t cap, uint64_t *pos, hipStream_t st) {
+  if (!n || U0 >= U1) return hipSuccess;
+  const uint64_t nw = (U1 - begin + 31) / 32 - (U0 - begin) / 32;
+  const uint64_t nch = (nw + WP_CHUNK - 1) / WP_CHUNK;
+  hipLaunchKernelGGL(k_chunk_popcounts, dim3((uint32_t)nch), dim3(WP_T), 0, st, bits, begin, U0, U1, cnt);
+  hipError_t e = scan_exclusive_u64(cnt, cnt + nch, nch, tmp, st);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_word_prefix, dim3((uint32_t)nch), dim3(WP_T), 0, st, bits, begin, U0, U1, cnt + nch, wpre);
+  hipLaunchKernelGGL(k_range_counts, dim3((uint32_t)((n + 1 + 255) / 256)), dim3(256), 0, st, bits, begin, U0, U1, wpre,
+                     first, E, reserve, n, rbase, rcnt);
+  e = scan_exclusive_u64(rcnt, off, n + 1, tmp, st);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_ranges_positions, dim3((uint32_t)((nw + 255) / 256)), dim3(256), 0, st, bits, begin, U0, U1,
+                     wpre, first, E, n, rbase, off, cap, pos);
+  return hipGetLastError();
+}
+
+hipError_t launch_rec_seg_check(const uint8_t *U, const uint64_t *pos, uint64_t n, const uint64_t *seg_end,
+                                uint32_t nseg, unsigned long long *bad, hipStream_t st) {
+  if (!n || !nseg) return hipSuccess;
+  hipLaunchKernelGGL(k_rec_seg_check, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, U, pos, n, seg_end, nseg,
+                     bad);
   return hipGetLastError();
 }
 

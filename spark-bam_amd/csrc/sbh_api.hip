@@ -225,6 +225,8 @@ struct sbh_shard {
   // record field extraction (sbh_records_scan / fetch): positions, sizes -> offsets, columns
   struct Recs {
     DBuf<uint64_t> pos, wcnt, wpre, nm, cg, sq, ax, nmo, cgo, sqo, axo, keep, kpre, pos2, vpos;
+    // sbh_split_records_batch: [first, E, reserve] x n in, each range's base, count and prefix
+    DBuf<uint64_t> bt_in, bt_rbase, bt_cnt, bt_off;
     DBuf<int64_t> iv_b, iv_e;
     DBuf<int32_t> iv_ref;
     DBuf<int32_t> ref_id, p0, nref, npos, tlen;
@@ -236,7 +238,8 @@ struct sbh_shard {
     bool valid = false;
     bool decoded = false;  // the columns were decoded (else only the starts, sbh_split_records decode = 0)
     void release() {
-      for (auto *b : {&pos, &wcnt, &wpre, &nm, &cg, &sq, &ax, &nmo, &cgo, &sqo, &axo, &keep, &kpre, &pos2, &vpos})
+      for (auto *b : {&pos, &wcnt, &wpre, &nm, &cg, &sq, &ax, &nmo, &cgo, &sqo, &axo, &keep, &kpre, &pos2, &vpos,
+                      &bt_in, &bt_rbase, &bt_cnt, &bt_off})
         b->release();
       iv_b.release(); iv_e.release(); iv_ref.release();
       for (auto *b : {&ref_id, &p0, &nref, &npos, &tlen}) b->release();
@@ -1576,8 +1579,19 @@ int sbh_chain_from(sbh_shard *sh, uint64_t first_flat, uint64_t end_flat, uint64
 // all splits (splits.hip), one proves the record chain over their union, one counts every
 // split.  Splits off the common path take the exact per-split path (sbh_split), so each
 // split's (status, first_vpos, count) equals sbh_split's.
+// (hostf, optional, zeroed by the caller: hostf[i] = 1 for every split the per-split path decided)
+static int split_starts_impl(sbh_shard *sh, const uint64_t *starts, const uint64_t *ends, uint64_t n, int32_t k,
+                             int32_t rtc, int32_t mrs, uint64_t *first_vpos, uint64_t *counts, int32_t *status,
+                             uint64_t *n_host, uint8_t *hostf);
+
 int sbh_split_starts(sbh_shard *sh, const uint64_t *starts, const uint64_t *ends, uint64_t n, int32_t k, int32_t rtc,
                      int32_t mrs, uint64_t *first_vpos, uint64_t *counts, int32_t *status, uint64_t *n_host) {
+  return split_starts_impl(sh, starts, ends, n, k, rtc, mrs, first_vpos, counts, status, n_host, nullptr);
+}
+
+static int split_starts_impl(sbh_shard *sh, const uint64_t *starts, const uint64_t *ends, uint64_t n, int32_t k,
+                             int32_t rtc, int32_t mrs, uint64_t *first_vpos, uint64_t *counts, int32_t *status,
+                             uint64_t *n_host, uint8_t *hostf) {
   if (!sh || (n && (!starts || !ends || !first_vpos || !counts || !status)) || k < 0) return SBH_E_ARG;
   sbh_ctx *ctx = sh->ctx;
   if (!sh->inflated) return fail(ctx, SBH_E_STATE, "splits before inflate");
@@ -1660,6 +1674,7 @@ int sbh_split_starts(sbh_shard *sh, const uint64_t *starts, const uint64_t *ends
           status[i] = SBH_E_NO_READ_FOUND;
         } else {
           ++nh;
+          if (hostf) hostf[i] = 1;
           first_vpos[i] = counts[i] = 0;
           // (sbh_split leaves sp_pin alone: first / E / cnt stay valid)
           status[i] = sbh_split(sh, starts[i], ends[i], k, rtc, mrs, &first_vpos[i], &counts[i]);
@@ -1750,6 +1765,7 @@ int sbh_split_starts(sbh_shard *sh, const uint64_t *starts, const uint64_t *ends
       continue;
     }
     ++nh;
+    if (hostf) hostf[i] = 1;
     if (std::getenv("SBH_SPLIT_DEBUG"))
       fprintf(stderr, "[sbh] split %llu [%llu, %llu) host path: shard [%llu, +%llu) first %llu E %llu dense %d marked %d code %#x\n",
               (unsigned long long)i, (unsigned long long)starts[i], (unsigned long long)ends[i],
@@ -2635,6 +2651,216 @@ int sbh_split_records(sbh_shard *sh, uint64_t start, uint64_t end, int32_t k, in
   // the split's last record runs past the resident bytes: more halo, not a malformed record
   if (rc == SBH_E_BAD_RECORD && !sh->at_eof)
     return fail(ctx, SBH_E_NEED_HALO, "a record of the split runs past the shard");
+  return rc;
+}
+
+// sbh_split from block bi on, for a split whose FindBlockStart lands on an empty block.  sbh_split
+// answers NoReadFoundException there (the stream from an empty block ends at once);
+// sbh_split_records, indexing from that block, searches on in the segment behind it.  The batch
+// answers as sbh_split_records does: the search starts at the empty block's flat position.
+static int split_behind_empty_block(sbh_shard *sh, int64_t bi, uint64_t end, int32_t rtc, int32_t mrs,
+                                    uint64_t *first_vpos, uint64_t *count) {
+  uint64_t first = 0, E = 0;
+  int32_t delta = 0;
+  int rc = sbh_find_record_start(sh, sh->hb[bi].ustart, rtc, mrs, &first, &delta);
+  if (rc) return rc;
+  (void)sbh_flat_bound(sh, end, &E);
+  if (!sh->at_eof && E == sh->utotal)
+    return fail(sh->ctx, SBH_E_NEED_HALO, "split end %llu past the resident blocks", (unsigned long long)end);
+  rc = count_records_impl(sh, first, E, count, nullptr);
+  if (rc) return rc;
+  uint64_t bp = 0;
+  uint32_t off = 0;
+  rc = sbh_pos_of(sh, first, &bp, &off);
+  if (rc) return rc;
+  *first_vpos = (bp << 16) | off;
+  return SBH_OK;
+}
+
+// Many FileSplits of one shard in one call: sbh_split_records' answer for every split [starts[i],
+// ends[i]) from ONE pass over their bytes -- FindBlockStart(starts[0]), sbh_run_shard from that
+// block to the last end, sbh_split_starts for all splits, the record starts of every split in one
+// launch set (launch_rec_positions_ranges over the verified bitmap), one records_finish.  The
+// batch's rows are the splits' records in split order; split i owns rows [rec_begin, + rec_count).
+int sbh_split_records_batch(sbh_shard *sh, const uint64_t *starts, const uint64_t *ends, uint64_t n, int32_t k,
+                            int32_t rtc, int32_t mrs, int32_t decode, sbh_batch_split *splits,
+                            sbh_split_batch_result *out) {
+  if (!sh || !out || !n || !starts || !ends || !splits || k < 0) return SBH_E_ARG;
+  sbh_ctx *ctx = sh->ctx;
+  std::memset(out, 0, sizeof *out);
+  std::memset(splits, 0, n * sizeof *splits);
+  for (uint64_t i = 0; i < n; ++i)
+    if (starts[i] >= ends[i] || (i + 1 < n && ends[i] > starts[i + 1]))
+      return fail(ctx, SBH_E_ARG, "splits must be ascending and disjoint (split %llu)", (unsigned long long)i);
+  if (starts[0] < sh->file_off || starts[0] >= sh->file_off + sh->n)
+    return fail(ctx, SBH_E_ARG, "the first split starts outside the shard");
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  hipStream_t st = sh->st;
+  auto &R = sh->rec;
+  R.valid = R.decoded = false;
+  // the chain starts at the first split whose FindBlockStart succeeds; a split before it keeps
+  // its own failure (HeaderSearchFailedException(path, start, positionsAttempted))
+  uint64_t j0 = 0, b = 0;
+  for (; j0 < n; ++j0) {
+    rc = starts[j0] < sh->file_off + sh->n ? sbh_find_block_start(sh, starts[j0], k, &b) : SBH_E_NEED_HALO;
+    if (rc == SBH_OK) break;
+    if (rc == SBH_E_ARG || rc == SBH_E_HIP || rc == SBH_E_NOMEM) return rc;
+    splits[j0].status = rc;
+  }
+  if (j0 == n) {
+    R.sz = sbh_records_sizes{0, 0, 0, 0, 0};
+    R.valid = true;
+    R.decoded = decode != 0;
+    return SBH_OK;
+  }
+  out->block_start = b;
+  sbh_shard_result r{};
+  rc = sbh_run_shard(sh, b, ends[n - 1], rtc, mrs, &r);
+  if (rc == SBH_E_NEED_HALO) {
+    // the last end has no block behind it in the resident bytes (or an answer of the step needs
+    // the halo): index and inflate what is there; sbh_split_starts runs the eager check over it
+    // and every split decides alone, NEED_HALO where its own answer needs the missing bytes
+    rc = sbh_index(sh, b, nullptr, nullptr);
+    if (!rc) rc = sbh_inflate(sh, nullptr);
+    r = sbh_shard_result{};
+  }
+  if (rc) return rc;
+  out->n_blocks = sh->nblocks;
+  out->flat_size = sh->utotal;
+  out->n_true = r.n_true;
+  const uint64_t m = n - j0;
+  std::vector<uint64_t> fv(m, 0), cnt(m, 0);
+  std::vector<int32_t> stat(m, 0);
+  std::vector<uint8_t> hostf(m, 0);
+  rc = split_starts_impl(sh, starts + j0, ends + j0, m, k, rtc, mrs, fv.data(), cnt.data(), stat.data(), &out->n_host,
+                         hostf.data());
+  if (rc) return rc;
+  // per split: FindBlockStart's block, the flat range of its records, its rows
+  std::vector<uint64_t> in(3 * n, 0);  // [first, E, reserve] x n, normalised: sorted, empty = [cursor, cursor)
+  uint64_t *hf = in.data(), *hE = hf + n, *hres = hE + n;
+  uint64_t rows = 0, U0 = ~0ull, U1 = 0;
+  for (uint64_t i = j0; i < n; ++i) {
+    sbh_batch_split &s = splits[i];
+    s.status = stat[i - j0];
+    s.host_path = hostf[i - j0];
+    s.rec_begin = rows;
+    if (s.status != SBH_OK && s.status != SBH_E_NO_READ_FOUND) continue;
+    if (s.host_path) {
+      if (sbh_find_block_start(sh, starts[i], k, &s.block_start) != SBH_OK) s.block_start = 0;
+    } else {
+      auto it = std::lower_bound(sh->hb.begin(), sh->hb.end(), starts[i],
+                                 [](const sbh_block &bl, uint64_t v) { return bl.start < v; });
+      s.block_start = it == sh->hb.end() ? 0 : it->start;
+    }
+    const int64_t bi = block_index_of(sh, s.block_start);
+    if (s.status == SBH_E_NO_READ_FOUND && bi >= 0 && (sh->hb[bi].flags & SBH_BLOCK_EMPTY)) {
+      s.status = split_behind_empty_block(sh, bi, ends[i], rtc, mrs, &fv[i - j0], &cnt[i - j0]);
+      if (s.status == SBH_E_ARG || s.status == SBH_E_HIP || s.status == SBH_E_NOMEM) return s.status;
+      if (!s.host_path) ++out->n_host;
+      s.host_path = 1;
+      if (s.status != SBH_OK && s.status != SBH_E_NO_READ_FOUND) continue;
+    }
+    (void)sbh_flat_bound(sh, ends[i], &s.owned_flat);
+    if (s.status != SBH_OK || !cnt[i - j0]) continue;
+    rc = sbh_flat_of(sh, fv[i - j0] >> 16, (uint32_t)(fv[i - j0] & 0xffff), &s.first_flat);
+    if (rc) return rc;
+    s.first_vpos = fv[i - j0];
+    s.rec_count = cnt[i - j0];
+    rows += s.rec_count;
+  }
+  uint64_t cursor = 0;
+  for (uint64_t i = 0; i < n; ++i) {
+    const sbh_batch_split &s = splits[i];
+    hf[i] = hE[i] = cursor;
+    if (!s.rec_count) continue;
+    const uint64_t E = std::min(std::min(s.owned_flat, sh->utotal), seg_end_of(sh, s.first_flat));
+    if (s.host_path || s.first_flat < cursor || s.first_flat >= E) {  // (its records by the chain walk)
+      hres[i] = s.rec_count;
+      continue;
+    }
+    hf[i] = s.first_flat;
+    hE[i] = cursor = E;
+    U0 = std::min(U0, hf[i]);
+    U1 = E;
+  }
+  HIPCHK(ctx, R.pos.ensure(rows + 1));
+  std::vector<uint64_t> off(n + 1, 0);
+  const bool covered = U0 < U1 && sh->bits_valid && sh->bits_begin <= U0 && U1 <= sh->bits_end;
+  if (U0 < U1 && !covered)  // no bitmap over the ranges: every split by the chain walk
+    for (uint64_t i = 0; i < n; ++i) {
+      hf[i] = hE[i] = 0;
+      hres[i] = splits[i].rec_count;
+    }
+  if (covered) {
+    for (uint64_t i = 0; i < n; ++i)  // (empty ranges before the first live one: inside the union)
+      if (hf[i] < U0) hf[i] = hE[i] = U0;
+    const uint64_t nw = (U1 - sh->bits_begin + 31) / 32 - (U0 - sh->bits_begin) / 32;
+    HIPCHK(ctx, R.wcnt.ensure(nw + 2));
+    HIPCHK(ctx, R.wpre.ensure(nw));
+    HIPCHK(ctx, sh->tmp.ensure(std::max(scan_tmp_words(nw), scan_tmp_words(n + 1))));
+    HIPCHK(ctx, R.bt_in.ensure(3 * n));
+    HIPCHK(ctx, R.bt_rbase.ensure(n));
+    HIPCHK(ctx, R.bt_cnt.ensure(n + 1));
+    HIPCHK(ctx, R.bt_off.ensure(n + 1));
+    HIPCHK(ctx, hipMemcpyAsync(R.bt_in.p, in.data(), 24 * n, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, launch_rec_positions_ranges(sh->bits.p, sh->bits_begin, U0, U1, R.bt_in.p, R.bt_in.p + n,
+                                            R.bt_in.p + 2 * n, n, R.wcnt.p, R.wpre.p, sh->tmp.p, R.bt_rbase.p,
+                                            R.bt_cnt.p, R.bt_off.p, rows, R.pos.p, st));
+    HIPCHK(ctx, hipMemcpyAsync(off.data(), R.bt_off.p, 8 * (n + 1), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+  }
+  // the layout the splits' counts give; where the bitmap's agrees the rows are in place
+  bool moved = false;
+  for (uint64_t i = 0; i < n && !moved; ++i)
+    moved = covered && (off[i] != splits[i].rec_begin || off[i + 1] - off[i] != splits[i].rec_count);
+  uint64_t *dst = R.pos.p;
+  if (moved) {
+    // set bits off the chain inside a range (false positives): the splits whose bitmap count
+    // is their record count keep their rows (copied to their place), the others walk the chain
+    HIPCHK(ctx, R.pos2.ensure(rows + 1));
+    dst = R.pos2.p;
+  }
+  for (uint64_t i = 0; i < n; ++i) {
+    const sbh_batch_split &s = splits[i];
+    if (!s.rec_count) continue;
+    const bool by_bits = covered && !hres[i] && off[i + 1] - off[i] == s.rec_count && off[i + 1] <= rows;
+    if (by_bits && !moved) continue;
+    if (by_bits) {
+      HIPCHK(ctx, hipMemcpyAsync(dst + s.rec_begin, R.pos.p + off[i], 8 * s.rec_count, hipMemcpyDeviceToDevice, st));
+      continue;
+    }
+    const uint64_t total = seg_end_of(sh, s.first_flat);
+    HIPCHK(ctx, launch_rec_positions_chain(sh->U.p, s.first_flat, std::min(std::min(s.owned_flat, sh->utotal), total),
+                                           total, s.rec_count, dst + s.rec_begin, st));
+  }
+  if (moved) std::swap(R.pos, R.pos2);
+  out->sizes = sbh_records_sizes{rows, 0, 0, 0, 0};
+  // A record over the end of its stream segment.  Starts only: the batch's last record against
+  // an open shard end, so decode = 0 asks for the halo where decode = 1 does.  Decoding: the size
+  // pass below measures every record against the resident bytes' end; where empty blocks cut
+  // the stream into segments, each record against its own segment's end first (sbh_split_records
+  // measures a split's records against the end of the segment its first record lies in).
+  unsigned long long *bad = sh->ctr.p + 25;
+  if (rows && (decode ? sh->seg_end.size() > 1 : !sh->at_eof)) {
+    HIPCHK(ctx, hipMemsetAsync(bad, 0xff, 8, st));
+    HIPCHK(ctx, launch_rec_seg_check(sh->U.p, decode ? R.pos.p : R.pos.p + rows - 1, decode ? rows : 1, sh->d_seg.p,
+                                     (uint32_t)sh->seg_end.size(), bad, st));
+    HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + 25, bad, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    if (sh->h_ctr[25] != ~0ull)
+      return sh->at_eof ? fail(ctx, SBH_E_BAD_RECORD, "a record of the batch runs over the end of the stream")
+                        : fail(ctx, SBH_E_NEED_HALO, "a record of the batch runs past the shard");
+  }
+  if (!decode) {
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    R.sz = out->sizes;
+    R.valid = true;
+    return SBH_OK;
+  }
+  rc = records_finish(sh, rows, sh->utotal, &out->sizes);
+  if (rc == SBH_E_BAD_RECORD && !sh->at_eof)
+    return fail(ctx, SBH_E_NEED_HALO, "a record of the batch runs past the shard");
   return rc;
 }
 

@@ -149,6 +149,16 @@ hipError_t launch_rec_positions_bits(const uint32_t *bits, uint64_t begin, uint6
                                      uint64_t *wpre, uint64_t *tmp, uint64_t *pos, hipStream_t st);
 hipError_t launch_rec_positions_chain(const uint8_t *U, uint64_t first, uint64_t E, uint64_t total, uint64_t cap,
                                       uint64_t *pos, hipStream_t st);
+// record starts of n sorted, disjoint ranges [first[i], E[i]) inside the union [U0, U1) in one
+// launch set: pos[off[i] + r] = the range's r-th set bit, off[0..n] the exclusive prefix of the
+// ranges' counts + reserve[i] (rows left free behind range i's own)
+hipError_t launch_rec_positions_ranges(const uint32_t *bits, uint64_t begin, uint64_t U0, uint64_t U1,
+                                       const uint64_t *first, const uint64_t *E, const uint64_t *reserve, uint64_t n,
+                                       uint64_t *cnt, uint64_t *wpre, uint64_t *tmp, uint64_t *rbase, uint64_t *rcnt,
+                                       uint64_t *off, uint64_t cap, uint64_t *pos, hipStream_t st);
+// bad = min row of a record that runs over the end of its stream segment
+hipError_t launch_rec_seg_check(const uint8_t *U, const uint64_t *pos, uint64_t n, const uint64_t *seg_end,
+                                uint32_t nseg, unsigned long long *bad, hipStream_t st);
 hipError_t launch_rec_sizes(const uint8_t *U, const uint64_t *pos, uint64_t n, uint64_t total, uint64_t *nm,
                             uint64_t *cg, uint64_t *sq, uint64_t *ax, unsigned long long *bad, hipStream_t st);
 hipError_t launch_rec_fields(const uint8_t *U, const uint64_t *pos, uint64_t n, const uint64_t *nm_off,

@@ -1,14 +1,15 @@
 """Context / Shard: thin owners of the C-ABI handles (include/sparkbam.h)."""
 import ctypes as C
+import time
 import weakref
 
 import numpy as np
 
 from .records import record_columns
 
-from ._lib import (SBH_OK, SbhBlock, SbhCheckOpts, SbhCheckResult, SbhRecordsOut, SbhRecordsSizes,
-                   SbhShardResult, SbhSplitRecordsResult, SbhStreamOpts, SbhStreamResult, SparkBamError, error_for,
-                   lib)
+from ._lib import (SBH_OK, SbhBatchSplit, SbhBlock, SbhCheckOpts, SbhCheckResult, SbhRecordsOut, SbhRecordsSizes,
+                   SbhShardResult, SbhSplitBatchResult, SbhSplitRecordsResult, SbhStreamOpts, SbhStreamResult,
+                   SparkBamError, error_for, lib)
 
 
 def _check(ctx_handle, rc):
@@ -521,6 +522,41 @@ class Shard:
         if flat_out is None:
             return info, {"flat": both[:n], "vpos": both[n:]}
         return info, {"flat": both[:n].copy(), "vpos": both[n:].copy()}
+
+    def split_records_batch(self, splits, bgzf_blocks_to_check=5, reads_to_check=10, max_read_size=100000000,
+                            decode=True, flat_out=None):
+        """Many FileSplits [(start, end), ...] of this shard in one call (sbh_split_records_batch):
+        one pass over their bytes, every split answered as split_records answers it alone.
+        Returns (info dict, per-split list of dicts, columns): split i's records are rows
+        [rec_begin, rec_begin + rec_count) of the columns (all of them when decode, else `flat` and
+        `vpos`); a split's `status` is its own SBH_* code.  flat_out(n) (optional, starts only): n
+        u64 slots where the starts and their virtual positions land (e.g. page-locked memory); the
+        columns returned are then views of it.  info["ms_call"] / ["ms_fetch"]: host-clock time of
+        the library call and of the copy-out."""
+        st = np.ascontiguousarray([a for a, _ in splits], dtype=np.uint64)
+        en = np.ascontiguousarray([b for _, b in splits], dtype=np.uint64)
+        n = int(st.size)
+        per = (SbhBatchSplit * max(n, 1))()
+        r = SbhSplitBatchResult()
+        t0 = time.perf_counter()
+        self._c(lib().sbh_split_records_batch(self.h, _ptr(st), _ptr(en), n, int(bgzf_blocks_to_check),
+                                              int(reads_to_check), int(max_read_size), 1 if decode else 0, per,
+                                              C.byref(r)))
+        t1 = time.perf_counter()
+        info = {f: getattr(r, f) for f, _ in SbhSplitBatchResult._fields_ if f != "sizes"}
+        info["n"] = r.sizes.n
+        self.n_blocks, self.flat_size = r.n_blocks, r.flat_size
+        out = [{f: getattr(s, f) for f, _ in SbhBatchSplit._fields_} for s in per[:n]]
+        if decode:
+            cols = self._records_fetch(r.sizes)
+        else:
+            both = np.empty(2 * r.sizes.n, np.uint64) if flat_out is None else flat_out(2 * r.sizes.n)
+            if r.sizes.n:
+                o = SbhRecordsOut(flat=both.ctypes.data, vpos=both[r.sizes.n:].ctypes.data)
+                self._c(lib().sbh_records_fetch(self.h, C.byref(o)))
+            cols = {"flat": both[:r.sizes.n], "vpos": both[r.sizes.n:2 * r.sizes.n]}
+        info["ms_call"], info["ms_fetch"] = 1e3 * (t1 - t0), 1e3 * (time.perf_counter() - t1)
+        return info, out, cols
 
     def _records_fetch(self, sz):
         cols = record_columns(sz.n, sz.name_bytes, sz.cigar_ops, sz.bases, sz.aux_bytes)

@@ -34,6 +34,32 @@ def record_columns(n=0, name_bytes=0, cigar_ops=0, bases=0, aux_bytes=0):
     z = (n, name_bytes, cigar_ops, bases, aux_bytes)
     cols = {k: (np.zeros if n == 0 else np.empty)(f(*z), dt) for k, dt, f in RECORD_COLUMNS}
     return cols
+
+
+# packed column -> the [n + 1] offsets addressing it
+PACKED = {"names": "name_off", "cigar": "cigar_off", "seq": "seq_off", "qual": "seq_off", "aux": "aux_off"}
+
+
+def slice_columns(cols, a, b, copy=True):
+    """Rows [a, b) of a column batch as a batch of its own: fixed columns sliced, packed columns
+    cut at their offsets, the offsets rebased to start at 0.  copy=False: views of the batch's
+    arrays (only the small offset columns are new), for a batch nobody else writes.  Columns the
+    batch does not hold (a starts-only batch) are skipped."""
+    out = {}
+    for k, v in cols.items():
+        if k in PACKED:
+            o = cols[PACKED[k]]
+            out[k] = v[int(o[a]):int(o[b])]
+        elif k in PACKED.values():
+            out[k] = v[a:b + 1] - v[a]
+            continue
+        else:
+            out[k] = v[a:b]
+        if copy:
+            out[k] = out[k].copy()
+    return out
+
+
 _B_FMT = {"c": "b", "C": "B", "s": "h", "S": "H", "i": "i", "I": "I", "f": "f"}
 
 
