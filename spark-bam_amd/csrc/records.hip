@@ -236,6 +236,12 @@ __global__ void k_rec_sizes(const uint8_t *U, const uint64_t *pos, uint64_t n, u
 // ends are sorted too: binary search for the first interval of the record's ref whose
 // end exceeds pos.  A record whose fields run past `total` is kept, so the size pass
 // reports it as malformed (htsjdk would throw on it).
+// pos is not tested against 0: htsjdk's getAlignmentStart is pos + 1 whatever pos is (0,
+// its "no alignment start", for pos = -1), and for a read without flag 4 getAlignmentEnd is
+// start + referenceLength - 1 from that value, so region() is [pos, pos + span) for a
+// negative pos too -- a mapped record at pos = -1 (which the eager checker admits) with
+// span s >= 2 is [-1, s - 1) and does meet [0, ...).  An empty region is span == 0 alone.
+// The arithmetic is int64: pos + span passes 2^31 near the end of a long contig.
 __global__ void k_region_keep(const uint8_t *__restrict__ U, const uint64_t *pos, uint64_t n, uint64_t total,
                               const int32_t *iv_ref, const int64_t *iv_begin, const int64_t *iv_end, uint32_t n_iv,
                               uint64_t *keep) {
@@ -251,7 +257,7 @@ __global__ void k_region_keep(const uint8_t *__restrict__ U, const uint64_t *pos
     const uint64_t q = p + 36 + U[p + 12];
     if (q + 4ull * nc > total) {
       k = 1;
-    } else if (ref >= 0 && !((fnc >> 16) & 4) && rp >= 0) {
+    } else if (ref >= 0 && !((fnc >> 16) & 4)) {
       int64_t span = 0;
       for (uint32_t c = 0; c < nc; ++c) {
         const uint32_t op = rd_u32(U, q + 4ull * c);

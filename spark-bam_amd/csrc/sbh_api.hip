@@ -1453,7 +1453,18 @@ static int count_records_impl(sbh_shard *sh, uint64_t first, uint64_t E, uint64_
                                             c + 1, c + 3, c + 2, tsum_on() ? sh->tsum.p : nullptr, st, nullptr,
                                             sh->cc.p));
       HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + 16, c, 32, hipMemcpyDeviceToHost, st));
+      // The proof walks the set bits of [first, E), and `first` need not be one of them: a caller's
+      // record start (a BAI chunk, a stitched exit) that the eager checker rejects.  Set bits
+      // further on that chain among themselves are then a suffix of the chain, not the chain,
+      // so first's own bit comes back with the counters and a clear one is an anomaly at `first`.
+      const uint64_t fbit = first - sh->bits_begin;
+      sh->h_ctr[604] = 0;
+      HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + 604, sh->bits.p + fbit / 32, 4, hipMemcpyDeviceToHost, st));
       HIPCHK(ctx, hipStreamSynchronize(st));
+      if (!((sh->h_ctr[604] >> (fbit & 31)) & 1)) {
+        ++sh->h_ctr[16];
+        sh->h_ctr[17] = std::min<uint64_t>(sh->h_ctr[17], first);
+      }
     }
     const uint64_t n = sh->h_ctr[18];
     if (sh->h_ctr[16] == 0 && sh->h_ctr[19] != ~0ull) {

@@ -131,7 +131,9 @@ REF_OPS = (0, 2, 3, 7, 8)  # M D N = X consume the reference
 def region(cols, i):
     """CanLoadBam.region (load/.../CanLoadBam.scala:446-454) as (ref_idx, begin, end) or
     None: no contig for refID -1; htsjdk getAlignmentEnd is 0 for an unmapped read and
-    alignmentStart + referenceLength - 1 otherwise; Region(contig, start - 1, end)."""
+    alignmentStart + referenceLength - 1 otherwise; Region(contig, start - 1, end).
+    Nothing here tests pos against 0, as nothing in htsjdk does: pos = -1 on a contig, mapped,
+    span s, is [-1, s - 1) and meets [0, ...) for s >= 2 (record_corpus.py: neg1_s1, neg1_s5)."""
     ref = int(cols["ref_id"][i])
     if ref < 0:
         return None
