@@ -8,8 +8,9 @@
 //   spark-bam full-check    [-m SIZE] [-i RANGES] [-l N] BAM       (check/full/FullCheck.scala)
 //   spark-bam index-blocks  BAM [OUT]                        (bgzf/index/IndexBlocks.scala)
 //   spark-bam index-records BAM [OUT]                        (check/index/IndexRecords.scala)
+//   spark-bam index-bai     BAM [OUT]                        (the .bai samtools index writes; htslib hts.c)
 //   spark-bam check-blocks -s [-r RECORDS] [-l N] BAM        (cli/.../check/blocks/CheckBlocks.scala)
-//   spark-bam htsjdk-rewrite [-r READS] [-b] [-i] BAM OUT     (cli/.../rewrite/HTSJDKRewrite.scala)
+//   spark-bam htsjdk-rewrite [-r READS] [-b] [-i] [--index-bai] BAM OUT  (cli/.../rewrite/HTSJDKRewrite.scala)
 //
 // The hadoop-bam ("seqdoop", -u) comparisons are out of scope: hadoop-bam's
 // BAMSplitGuesser is a competitor's algorithm, not part of spark-bam's path.
@@ -242,14 +243,19 @@ struct Args {
   std::vector<std::pair<uint64_t, uint64_t>> ranges;
   bool has_ranges = false;
   int reads_to_check = 10, max_read_size = 100000000, blocks_to_check = 5;
-  // htsjdk-rewrite: -r record-index ranges (IntRanges), -b / -i write OUT.blocks / OUT.records
+  // htsjdk-rewrite: -r record-index ranges (IntRanges), -b / -i / --index-bai write OUT.blocks /
+  // OUT.records / OUT.bai
   std::vector<std::pair<uint64_t, uint64_t>> read_ranges;
-  bool has_read_ranges = false, idx_blocks = false, idx_records = false;
+  bool has_read_ranges = false, idx_blocks = false, idx_records = false, idx_bai = false;
 };
 
 Args parse(int argc, char **argv) {
   Args a;
-  if (argc < 2) throw Error(SBH_E_ARG, "usage: spark-bam <command> [options] <bam>");
+  if (argc < 2)
+    throw Error(SBH_E_ARG,
+                "usage: spark-bam <command> [options] <bam>\n"
+                "  commands: compute-splits count-reads check-bam full-check index-blocks index-records index-bai\n"
+                "            check-blocks htsjdk-rewrite");
   a.cmd = argv[1];
   const bool rewrite = a.cmd == "htsjdk-rewrite";
   std::vector<std::string> pos;
@@ -262,6 +268,7 @@ Args parse(int argc, char **argv) {
     if (rewrite && (t == "-r" || t == "--read-ranges")) { a.read_ranges = parse_ranges(next()); a.has_read_ranges = true; }
     else if (rewrite && (t == "-b" || t == "--index-blocks")) a.idx_blocks = true;
     else if (rewrite && (t == "-i" || t == "--index-records")) a.idx_records = true;
+    else if (rewrite && t == "--index-bai") a.idx_bai = true;
     else if (t == "-m" || t == "--max-split-size") { a.split = parse_bytes(next()); a.has_split = true; }
     else if (t == "-s" || t == "--spark-bam") a.s = true;
     else if (t == "-u" || t == "--upstream" || t == "--hadoop-bam") a.u = true;
@@ -847,6 +854,38 @@ int index_records(const Args &a) {
   return 0;
 }
 
+// The .bai of a coordinate-sorted BAM (what samtools index writes), whole file resident: the
+// eager calls give the record starts in parallel, sbh_bai_scan turns the records into runs of
+// equal (ref_id, bin) and linear-index minima on the device, sbh_bai_build finishes on the host.
+int index_bai(const Args &a) {
+  Loaded L(a.path);
+  uint64_t seg_end = L.flat;
+  for (const sbh_block &b : L.blocks)
+    if (b.flags & SBH_BLOCK_EMPTY) { seg_end = b.ustart; break; }
+  if (seg_end > L.hdr.end) {
+    uint64_t n = 0;
+    chk(sbh_check_eager(L.sh, L.hdr.end, seg_end, a.reads_to_check, nullptr, &n), "eager");
+  }
+  sbh_bai_sizes sz{};
+  chk(sbh_bai_scan(L.sh, L.hdr.end, seg_end, &sz), "bai scan");
+  std::vector<sbh_bai_run> runs(sz.n_runs);
+  std::vector<uint64_t> lin(sz.lin_size);
+  chk(sbh_bai_fetch(L.sh, runs.data(), lin.data()), "bai fetch");
+  const int32_t n_ref = (int32_t)L.hdr.lens.size();
+  std::vector<uint8_t> bai(sbh_bai_bound(sz.n_runs, sz.lin_size, n_ref));
+  uint64_t size = 0;
+  const int rc = sbh_bai_build(runs.data(), runs.size(), lin.data(), L.hdr.lens.data(), n_ref, sz.n_no_coor, bai.data(),
+                               bai.size(), &size);
+  if (rc) throw Error(rc, "bai build failed (status " + std::to_string(rc) + ")");
+  std::string out = a.out.empty() ? a.path + ".bai" : a.out;
+  FILE *f = fopen(out.c_str(), "wb");
+  if (!f) throw Error(SBH_E_ARG, "cannot write " + out);
+  const bool ok = fwrite(bai.data(), 1, size, f) == size;
+  fclose(f);
+  if (!ok) throw Error(SBH_E_ARG, "short write to " + out);
+  return 0;
+}
+
 // HTSJDKRewrite (cli/.../rewrite/HTSJDKRewrite.scala:40-92): the BAM's uncompressed stream --
 // header, then every record, or only the records whose index is in -r (:48-58) -- re-cut into
 // 65498-byte BGZF members on the GPU (sbh_bgzf_compress) plus the EOF member; -b / -i then
@@ -898,6 +937,7 @@ int htsjdk_rewrite(const Args &a) {
   ix.out.clear();
   if (a.idx_blocks) index_blocks(ix);
   if (a.idx_records) index_records(ix);
+  if (a.idx_bai) index_bai(ix);
   return 0;
 }
 
@@ -1050,6 +1090,7 @@ int main(int argc, char **argv) {
     else if (a.cmd == "full-check") rc = full_check(a);
     else if (a.cmd == "index-blocks") rc = index_blocks(a);
     else if (a.cmd == "index-records") rc = index_records(a);
+    else if (a.cmd == "index-bai") rc = index_bai(a);
     else if (a.cmd == "check-blocks") rc = check_blocks(a);
     else if (a.cmd == "htsjdk-rewrite") rc = htsjdk_rewrite(a);
     else throw Error(SBH_E_ARG, "unknown command " + a.cmd);

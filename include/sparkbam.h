@@ -55,6 +55,7 @@ extern "C" {
 #define SBH_E_STATE 18               /* call order violated (e.g. check before inflate) */
 #define SBH_E_NOT_FOUND 19           /* Pos not in the indexed block chain            */
 #define SBH_E_BAD_RECORD 20          /* record does not fit its block / the stream (htsjdk decode throws) */
+#define SBH_E_UNSORTED 21            /* BAI build: records not coordinate-sorted (htslib hts_idx_push refuses them) */
 
 /* ---- full-checker result word (check/.../full/error/Flags.scala:21-45) ----
  *  bit 31     : Success(readsParsed)
@@ -109,6 +110,7 @@ const char *sbh_last_error(const sbh_ctx *ctx);
  *                              (check/.../spark/FindRecordStart.scala:66-71)
  *   SBH_E_INFLATE_SIZE         {block start, expected bytes}  -> IOException (Stream.scala:52-54)
  *   SBH_E_INFLATE_DATA         {block start}  -> DataFormatException
+ *   SBH_E_UNSORTED             {virtual offset of the first offending record}  (sbh_bai_scan)
  *   anything else              no fields */
 int32_t sbh_last_error_detail(const sbh_ctx *ctx, int32_t *code, int64_t *fields, int32_t cap);
 /* Use a caller-owned hipStream_t (e.g. torch.cuda.current_stream().cuda_stream). */
@@ -517,6 +519,78 @@ int sbh_split_records_batch(sbh_shard *sh, const uint64_t *starts, const uint64_
 int sbh_records_scan_regions(sbh_shard *sh, const uint64_t *chunk_begin, const uint64_t *chunk_end,
                              uint64_t n_chunks, const int32_t *iv_ref, const int64_t *iv_begin,
                              const int64_t *iv_end, uint32_t n_iv, sbh_records_sizes *out);
+
+/* ---- BAI index construction ------------------------------------------------------------
+ * What samtools index / htslib writes for a coordinate-sorted BAM, built from the records that
+ * are already resident.  sbh_bai_scan restates hts_idx_push (htslib hts.c) for every record of
+ * the chain from first_flat while the start is < end_flat (the range of sbh_records_scan), on
+ * the device:
+ *  - a record with ref_id < 0 only counts into n_no_coor;
+ *  - otherwise beg = pos, end = pos + (sum of the M D N = X op lengths) when flag 0x4 is clear
+ *    and that sum is > 0, else pos + 1; bin = hts_reg2bin(beg, end, 14, 5), computed (the stored
+ *    bin field is ignored, as htslib ignores it); the record counts as unmapped for its reference
+ *    when flag 0x4 is set;
+ *  - a RUN is a maximal stretch of consecutive records with one (ref_id, bin): the chunk [vbeg of
+ *    its first record, vend of its last) that hts_idx_push appends to the bin, where a record's
+ *    vend is the next record's vbeg and, for the last record of the scan, the virtual offset
+ *    bgzf_tell reports after it (at the end of the last non-empty block: the next member's
+ *    address, offset 0);
+ *  - the linear index (insert_to_l) holds, per 16 KiB window [beg >> 14, (end - 1) >> 14], the
+ *    smallest vbeg of the records touching it: lin is one array over all references, reference
+ *    r owning (l_ref >> 14) + 2 slots from the sum of the earlier references' counts, UINT64_MAX
+ *    where no record touched; a window past a reference's last slot is clamped to it.
+ * Errors: SBH_E_UNSORTED {virtual offset of the first offending record} when ref_id decreases,
+ * pos decreases within a reference, or a record with a reference follows one without;
+ * SBH_E_BAD_RECORD when ref_id >= n_ref, pos < 0 on a reference, or a record does not fit the
+ * stream (for a record that does not fit, SBH_E_NEED_HALO instead when the shard's end is open:
+ * more resident bytes may cure that, and only that).  Needs sbh_set_contigs.
+ * The runs and the linear-index minima stay on the device for sbh_bai_fetch.
+ *
+ * Windows.  A file larger than HBM is scanned window by window (sbh_shard_load), each window
+ * cut at a record boundary: the caller concatenates the windows' runs in file order, takes the
+ * element-wise minimum of their lin arrays, adds their n_no_coor, and hands the whole to one
+ * sbh_bai_build, which coalesces the run a seam cut in two.  The ordering check across a seam
+ * is split: sbh_bai_build refuses a ref_id that decreases between consecutive runs, and the
+ * caller compares sbh_bai_edges of the two windows -- the later window's first record against the
+ * earlier window's last record with a reference (pos within one reference; any record with a
+ * reference after a window that counted n_no_coor > 0). */
+typedef struct {
+  int32_t ref_id;
+  uint32_t bin;
+  uint64_t vbeg, vend, n_mapped, n_unmapped;
+} sbh_bai_run;
+typedef struct {
+  uint64_t n_records, n_runs, n_no_coor, lin_size;
+} sbh_bai_sizes;
+int sbh_bai_scan(sbh_shard *sh, uint64_t first_flat, uint64_t end_flat, sbh_bai_sizes *out);
+/* runs: n_runs entries; lin: lin_size entries (either may be NULL). */
+int sbh_bai_fetch(sbh_shard *sh, sbh_bai_run *runs, uint64_t *lin);
+/* (ref_id, pos) of the last scan's first record and of its last record with a reference;
+ * ref_id -1 when the first record has none, resp. when no record has one. */
+int sbh_bai_edges(sbh_shard *sh, int32_t *first_ref, int32_t *first_pos, int32_t *last_ref, int32_t *last_pos);
+
+/* hts_idx_finish + the BAI writer (hts_idx_save), HOST ONLY: no context, works without a GPU,
+ * like sbh_header_make.  runs may be the concatenation, in file order, of several scans' runs
+ * (adjacent runs with equal (ref_id, bin) are coalesced first), lin their element-wise minimum.
+ * Per reference: the metadata pseudo-bin 37450 {(vbeg of its first record, vend of its last),
+ * (n_mapped, n_unmapped)}; compress_binning -- for level 5 .. 1, every bin of the level (its
+ * chunks sorted first below level 5) whose chunks span fewer than 0x10000 block addresses is
+ * appended to its parent (bin - 1) >> 3 and deleted, then bin 0 is sorted, then in every bin a
+ * chunk starting in or before the block where the kept one ends is merged into it; the linear
+ * index up to its last touched window, an untouched window taking the next touched one's value
+ * (htslib's backward fill).  Layout: "BAI\1", n_ref, per reference its bins and intervals, then
+ * n_no_coor; a reference without records writes n_bin = 0, n_intv = 0.
+ * Deliberate deviation: bins are written in ascending bin id with 37450 last, where htslib writes
+ * its hash table's order; readers do not depend on the order, so the parsed index equals
+ * htslib's while the bytes need not.
+ * SBH_E_ARG when cap < the size needed (*size is set to it; sbh_bai_bound(...) always suffices),
+ * when two adjacent runs with equal (ref_id, bin) do not meet (the earlier vend != the later
+ * vbeg: windows concatenated with a gap or an overlap) or when a bin id is >= 37450;
+ * SBH_E_UNSORTED when ref_id decreases between runs, SBH_E_BAD_RECORD for a ref_id outside
+ * [0, n_ref). */
+uint64_t sbh_bai_bound(uint64_t n_runs, uint64_t lin_size, int32_t n_ref);
+int sbh_bai_build(const sbh_bai_run *runs, uint64_t n_runs, const uint64_t *lin, const int32_t *contig_len,
+                  int32_t n_ref, uint64_t n_no_coor, uint8_t *out, uint64_t cap, uint64_t *size);
 
 /* ---- BGZF writer -------------------------------------------------
  * The block compressor behind HTSJDKRewrite (cli/src/main/scala/org/hammerlab/bam/rewrite/

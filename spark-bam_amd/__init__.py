@@ -9,6 +9,7 @@ Import name: ``spark_bam_amd`` (the directory name contains a hyphen, so load it
           WindowedEagerChecker / WindowedFullChecker), FindRecordStart
   load:   load_splits_and_reads / load_bam_count / load_reads / load_bam_intervals
           (CanLoadBam), FileSplits, read_bai (bam.index.Index)
+  index:  build_bai / write_bai (the `.bai` samtools index writes, built on the GPU)
 """
 from ._lib import (BLOCK_EMPTY, BLOCK_TRUNCATED, FULL_FLAGS_MASK, FULL_N_SHIFT,  # noqa: F401
                    FULL_SUCCESS, FULL_UNKNOWN, HeaderParseException, HeaderSearchFailedException,
@@ -21,6 +22,7 @@ from .records import Reads  # noqa: F401
 from .checkers import GpuWindow, WindowedEagerChecker, WindowedFullChecker  # noqa: F401
 from .intervals import (Chunk, Index, get_interval_chunks, load_bam_intervals,  # noqa: F401
                         parse_loci, read_bai)
+from .bai import build_bai, write_bai  # noqa: F401
 
 __all__ = [
     "htsjdk_rewrite",
@@ -30,4 +32,5 @@ __all__ = [
     "bam_header", "parse_bam_header", "lib", "load_reads", "Reads", "Chunk", "Index",
     "read_bai", "parse_loci", "get_interval_chunks", "load_bam_intervals",
     "GpuWindow", "WindowedEagerChecker", "WindowedFullChecker",
+    "build_bai", "write_bai",
 ]

@@ -16,11 +16,13 @@ STATUS_NAMES = {
     11: "SBH_E_HEADER_SEARCH_FAILED", 12: "SBH_E_TRUNCATED", 13: "SBH_E_INFLATE_SIZE",
     14: "SBH_E_INFLATE_DATA", 15: "SBH_E_BAD_ISIZE", 16: "SBH_E_NO_READ_FOUND",
     17: "SBH_E_NEED_HALO", 18: "SBH_E_STATE", 19: "SBH_E_NOT_FOUND", 20: "SBH_E_BAD_RECORD",
+    21: "SBH_E_UNSORTED",
 }
 SBH_E_ARG, SBH_E_HIP, SBH_E_HEADER_PARSE, SBH_E_HEADER_SEARCH_FAILED = 1, 2, 10, 11
 SBH_E_TRUNCATED, SBH_E_INFLATE_SIZE, SBH_E_INFLATE_DATA, SBH_E_BAD_ISIZE = 12, 13, 14, 15
 SBH_E_NO_READ_FOUND, SBH_E_NEED_HALO, SBH_E_STATE, SBH_E_NOT_FOUND = 16, 17, 18, 19
 SBH_E_BAD_RECORD = 20
+SBH_E_UNSORTED = 21  # sbh_bai_scan / sbh_bai_build: records out of coordinate order
 
 FULL_SUCCESS = 0x80000000
 FULL_UNKNOWN = 0x40000000
@@ -41,6 +43,7 @@ EXPORTS = [
     "sbh_stage_times", "sbh_run_stream", "sbh_run_stream2", "sbh_records_scan", "sbh_records_fetch", "sbh_records_scan_regions", "sbh_verify_crc",
     "sbh_bgzf_compress_bound", "sbh_bgzf_compress", "sbh_bgzf_compress_level",
     "sbh_shard_load", "sbh_find_blocks", "sbh_check_stream", "sbh_split_records", "sbh_split_records_batch",
+    "sbh_bai_scan", "sbh_bai_fetch", "sbh_bai_edges", "sbh_bai_bound", "sbh_bai_build",
 ]
 LEVEL_HTSJDK, LEVEL_FAST = 5, -1  # sbh_bgzf_compress_level: htsjdk's zlib level 5 / this library's own coder
 
@@ -109,6 +112,11 @@ class SbhBatchSplit(C.Structure):  # sbh_batch_split: one split of sbh_split_rec
 class SbhSplitBatchResult(C.Structure):
     _fields_ = [("block_start", C.c_uint64), ("n_blocks", C.c_uint64), ("flat_size", C.c_uint64),
                 ("n_true", C.c_uint64), ("n_host", C.c_uint64), ("sizes", SbhRecordsSizes)]
+
+
+class SbhBaiSizes(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("n_runs", C.c_uint64), ("n_no_coor", C.c_uint64),
+                ("lin_size", C.c_uint64)]
 
 
 class SbhRecordsOut(C.Structure):  # host buffers (sbh_records_out); NULL = not copied
@@ -233,6 +241,10 @@ def lib():
         "sbh_shard_load": [P, P, U64, U64, C.c_int],
         "sbh_find_blocks": [P, P, U64, P, P, U64, I32, U64, P, U64, PU64],
         "sbh_check_stream": [P, P, U64, P, I32, C.POINTER(SbhCheckOpts), C.POINTER(SbhCheckResult)],
+        "sbh_bai_scan": [P, U64, U64, C.POINTER(SbhBaiSizes)],
+        "sbh_bai_fetch": [P, P, P],
+        "sbh_bai_edges": [P, PI32, PI32, PI32, PI32],
+        "sbh_bai_build": [P, U64, P, P, I32, U64, P, U64, PU64],
         "sbh_bgzf_compress": [P, P, U64, I32, P, U64, PU64, PU64, C.POINTER(C.c_float)],
         "sbh_bgzf_compress_level": [P, P, U64, I32, I32, P, U64, PU64, PU64, C.POINTER(C.c_float)],
     }
@@ -242,6 +254,8 @@ def lib():
         f.restype = C.c_int
     L.sbh_bgzf_compress_bound.argtypes = [U64]
     L.sbh_bgzf_compress_bound.restype = U64
+    L.sbh_bai_bound.argtypes = [U64, U64, I32]
+    L.sbh_bai_bound.restype = U64
     L.sbh_stage_times.argtypes = [P, C.POINTER(C.c_double), I32]
     L.sbh_stage_times.restype = C.c_int
     L.sbh_last_error.argtypes = [P]

@@ -248,6 +248,22 @@ struct sbh_shard {
       valid = false;
     }
   } rec;
+  // BAI construction (sbh_bai_scan / fetch): per-record keys, windows, starts, the scan's input and
+  // prefix, the runs and the linear-index minima of the last scan
+  struct Bai {
+    DBuf<uint64_t> pos, key, win, vbeg, flg, pre, ridx, lin, lin_off, aux;
+    DBuf<sbh_bai_run> runs;
+    sbh_bai_sizes sz{};
+    int32_t edges[4] = {-1, 0, -1, 0};
+    bool valid = false;
+    bool off_ok = false;  // lin_off holds the window prefix of the current contig lengths
+    void release() {
+      for (auto *b : {&pos, &key, &win, &vbeg, &flg, &pre, &ridx, &lin, &lin_off, &aux}) b->release();
+      runs.release();
+      valid = off_ok = false;
+    }
+  } bai;
+  std::vector<int32_t> h_ctg;  // host copy of the contig lengths (sbh_set_contigs)
   // batched splits (sbh_split_starts) and check-bam truth (sbh_check_records)
   DBuf<uint64_t> sp_start, sp_end, sp_first, sp_E, sp_vpos;
   DBuf<uint32_t> sp_code;
@@ -536,6 +552,7 @@ int sbh_shard_destroy(sbh_shard *sh) {
   sh->defer.release();
   sh->xq.release();
   sh->rec.release();
+  sh->bai.release();
   for (auto *b : {&sh->sp_start, &sh->sp_end, &sh->sp_first, &sh->sp_E, &sh->sp_vpos, &sh->t_rb, &sh->t_re,
                   &sh->t_fp, &sh->t_fn})
     b->release();
@@ -582,6 +599,7 @@ int sbh_shard_load(sbh_shard *sh, const void *src, uint64_t n, uint64_t file_off
   sh->sieve_nref1 = 0;
   sh->indexed = sh->inflated = sh->bits_valid = sh->chain_ok = sh->cm_valid = false;
   sh->rec.valid = false;
+  sh->bai.valid = false;
   sh->ncand = 0;
   sh->scan_from = ~0ull;
   sh->hb.clear();
@@ -720,6 +738,7 @@ int shard_prefetch_finish(sbh_shard *sh, bool use, double *copy_ms) {
   sh->sieve_nref1 = 0;
   sh->indexed = sh->inflated = sh->bits_valid = sh->chain_ok = sh->cm_valid = false;
   sh->rec.valid = false;
+  sh->bai.valid = false;
   sh->ncand = 0;
   sh->scan_from = ~0ull;
   sh->hb.clear();
@@ -1188,6 +1207,8 @@ int sbh_set_contigs(sbh_shard *sh, const int32_t *lens, int32_t n) {
   if (n) HIPCHK(sh->ctx, hipMemcpyAsync(sh->ctg.p, lens, (uint64_t)n * 4, hipMemcpyHostToDevice, sh->st));
   HIPCHK(sh->ctx, hipStreamSynchronize(sh->st));
   sh->nctg = n;
+  sh->h_ctg.assign(lens, lens + n);
+  sh->bai.valid = sh->bai.off_ok = false;
   sh->bits_valid = sh->chain_ok = sh->cm_valid = false;
   return SBH_OK;
 }
@@ -3040,6 +3061,129 @@ int sbh_records_fetch(sbh_shard *sh, const sbh_records_out *o) {
   HIPCHK(ctx, cp(o->qual, R.qual.p, R.sz.bases));
   HIPCHK(ctx, cp(o->aux, R.aux.p, R.sz.aux_bytes));
   HIPCHK(ctx, hipStreamSynchronize(sh->st));
+  return SBH_OK;
+}
+
+// ---- BAI construction (bai.hip; htslib hts_idx_push over the record chain) ------------------
+int sbh_bai_scan(sbh_shard *sh, uint64_t first, uint64_t end_flat, sbh_bai_sizes *out) {
+  if (!sh || !out) return SBH_E_ARG;
+  sbh_ctx *ctx = sh->ctx;
+  if (!sh->inflated) return fail(ctx, SBH_E_STATE, "bai scan before inflate");
+  if (sh->nctg < 0) return fail(ctx, SBH_E_STATE, "contig lengths not set");
+  if (first > sh->utotal) return SBH_E_ARG;
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  hipStream_t st = sh->st;
+  auto &B = sh->bai;
+  B.valid = false;
+  const int32_t nref = sh->nctg;
+  if (!B.off_ok) {  // the linear index's layout: reference r owns (l_ref >> 14) + 2 slots
+    std::vector<uint64_t> off((size_t)nref + 1, 0);
+    for (int32_t r = 0; r < nref; ++r) {
+      if (sh->h_ctg[r] < 0) return fail(ctx, SBH_E_ARG, "contig %d has a negative length", r);
+      off[r + 1] = off[r] + ((uint64_t)sh->h_ctg[r] >> 14) + 2;
+    }
+    HIPCHK(ctx, B.lin_off.ensure((uint64_t)nref + 1));
+    HIPCHK(ctx, hipMemcpyAsync(B.lin_off.p, off.data(), 8 * ((uint64_t)nref + 1), hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    B.sz.lin_size = off[nref];
+    B.off_ok = true;
+  }
+  const uint64_t lin_size = B.sz.lin_size;
+  const uint64_t total = seg_end_of(sh, first);
+  const uint64_t E = std::min(std::min(end_flat, sh->utotal), total);
+  uint64_t n = 0;
+  int32_t anomalies = 0;
+  rc = count_records_impl(sh, first, E, &n, &anomalies);
+  if (rc) return rc;
+  if (n >= 0xffffffffull) return fail(ctx, SBH_E_ARG, "bai scan: %llu records in one scan (scan in windows)",
+                                      (unsigned long long)n);
+  HIPCHK(ctx, B.pos.ensure(n));
+  rc = records_positions(sh, first, E, total, n, anomalies, B.pos.p);
+  if (rc) return rc;
+  for (auto *b : {&B.key, &B.win, &B.vbeg}) HIPCHK(ctx, b->ensure(n));
+  HIPCHK(ctx, B.flg.ensure(n + 1));
+  HIPCHK(ctx, B.pre.ensure(n + 1));
+  HIPCHK(ctx, B.lin.ensure(lin_size));
+  HIPCHK(ctx, B.aux.ensure(8));
+  HIPCHK(ctx, sh->tmp.ensure(scan_tmp_words(n + 1)));
+  unsigned long long *err = sh->ctr.p + 40;  // rows: [40] does not fit, [41] unsorted, [42] off its reference
+  HIPCHK(ctx, hipMemsetAsync(err, 0xff, 24, st));
+  HIPCHK(ctx, hipMemsetAsync(B.aux.p, 0xff, 24, st));
+  if (lin_size) HIPCHK(ctx, hipMemsetAsync(B.lin.p, 0xff, 8 * lin_size, st));
+  uint64_t nruns = 0, no_coor = 0;
+  B.edges[0] = B.edges[2] = -1;
+  B.edges[1] = B.edges[3] = 0;
+  if (n) {
+    HIPCHK(ctx, launch_bai_keys(sh->U.p, B.pos.p, n, total, sh->ctg.p, nref, sh->dev_blocks(), sh->nblocks,
+                                sh->file_off, B.key.p, B.win.p, B.vbeg.p, B.flg.p, B.aux.p, err, st));
+    HIPCHK(ctx, launch_bai_heads(B.key.p, B.win.p, B.vbeg.p, n, B.lin_off.p, B.flg.p, B.lin.p, st));
+    HIPCHK(ctx, scan_exclusive_u64(B.flg.p, B.pre.p, n + 1, sh->tmp.p, st));
+    HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + 40, err, 24, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + 43, B.pre.p + n, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + 44, B.aux.p, 24, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    const uint64_t unfit = sh->h_ctr[40], uns = sh->h_ctr[41], off_ref = sh->h_ctr[42];
+    const uint64_t bad = std::min(unfit, off_ref);
+    if (bad != ~0ull || uns != ~0ull) {
+      const uint64_t row = std::min(bad, uns);
+      HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + 47, B.vbeg.p + row, 8, hipMemcpyDeviceToHost, st));
+      HIPCHK(ctx, hipStreamSynchronize(st));
+      const uint64_t v = sh->h_ctr[47];
+      if (bad <= uns) {
+        // only a record that does not fit can be cured by more resident bytes
+        if (unfit < off_ref && !sh->at_eof)
+          return fail(ctx, SBH_E_NEED_HALO, "record %llu of the scan may run past the shard", (unsigned long long)row);
+        return fail(ctx, SBH_E_BAD_RECORD, "record %llu of the scan (%llu:%u) is malformed or off its reference",
+                    (unsigned long long)row, (unsigned long long)(v >> 16), (unsigned)(v & 0xffff));
+      }
+      return fail_with(ctx, SBH_E_UNSORTED, {(int64_t)v},
+                       "record %llu of the scan (%llu:%u) is out of coordinate order", (unsigned long long)row, (unsigned long long)(v >> 16), (unsigned)(v & 0xffff));
+    }
+    nruns = sh->h_ctr[43] & 0xffffffffull;
+    HIPCHK(ctx, B.ridx.ensure(nruns));
+    HIPCHK(ctx, B.runs.ensure(nruns));
+    HIPCHK(ctx, launch_bai_runs(B.flg.p, B.pre.p, n, nruns, B.key.p, B.vbeg.p, B.aux.p, B.ridx.p, B.runs.p, st));
+    sbh_bai_run last{};
+    HIPCHK(ctx, hipMemcpyAsync(&last, B.runs.p + (nruns - 1), sizeof last, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    if (last.ref_id < 0) {  // the trailing run of records without a reference
+      no_coor = last.n_mapped + last.n_unmapped;
+      --nruns;
+    }
+    B.edges[0] = (int32_t)(sh->h_ctr[45] >> 32), B.edges[1] = (int32_t)(uint32_t)sh->h_ctr[45];
+    if (sh->h_ctr[46] != ~0ull)
+      B.edges[2] = (int32_t)(sh->h_ctr[46] >> 32), B.edges[3] = (int32_t)(uint32_t)sh->h_ctr[46];
+  }
+  B.sz = sbh_bai_sizes{n, nruns, no_coor, lin_size};
+  B.valid = true;
+  *out = B.sz;
+  return SBH_OK;
+}
+
+int sbh_bai_fetch(sbh_shard *sh, sbh_bai_run *runs, uint64_t *lin) {
+  if (!sh) return SBH_E_ARG;
+  sbh_ctx *ctx = sh->ctx;
+  auto &B = sh->bai;
+  if (!B.valid) return fail(ctx, SBH_E_STATE, "bai_fetch without a bai_scan");
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  if (runs && B.sz.n_runs)
+    HIPCHK(ctx, hipMemcpyAsync(runs, B.runs.p, B.sz.n_runs * sizeof(sbh_bai_run), hipMemcpyDeviceToHost, sh->st));
+  if (lin && B.sz.lin_size)
+    HIPCHK(ctx, hipMemcpyAsync(lin, B.lin.p, 8 * B.sz.lin_size, hipMemcpyDeviceToHost, sh->st));
+  HIPCHK(ctx, hipStreamSynchronize(sh->st));
+  return SBH_OK;
+}
+
+int sbh_bai_edges(sbh_shard *sh, int32_t *first_ref, int32_t *first_pos, int32_t *last_ref, int32_t *last_pos) {
+  if (!sh) return SBH_E_ARG;
+  if (!sh->bai.valid) return fail(sh->ctx, SBH_E_STATE, "bai_edges without a bai_scan");
+  const int32_t *e = sh->bai.edges;
+  if (first_ref) *first_ref = e[0];
+  if (first_pos) *first_pos = e[1];
+  if (last_ref) *last_ref = e[2];
+  if (last_pos) *last_pos = e[3];
   return SBH_OK;
 }
 

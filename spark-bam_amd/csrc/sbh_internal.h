@@ -181,6 +181,18 @@ hipError_t launch_split_count_cc(const uint32_t *bits, uint64_t begin, const uin
 // record starts (flat) -> htsjdk virtual positions over the device block table
 hipError_t launch_rec_vpos(const uint64_t *pos, uint64_t n, DevBlocks bl, uint64_t nblocks, uint64_t file_off,
                            uint64_t *vpos, hipStream_t st);
+// BAI construction (bai.hip; the passes are described there).  key / win / vbeg: n u64 each,
+// flg: n + 1 (the scan's input, head | unmapped << 32), aux: 3 words, err: 3 (preset to ~0).
+hipError_t launch_bai_keys(const uint8_t *U, const uint64_t *pos, uint64_t n, uint64_t total, const int32_t *ctg,
+                           int32_t nctg, DevBlocks bl, uint64_t nblocks, uint64_t file_off, uint64_t *key,
+                           uint64_t *win, uint64_t *vbeg, uint64_t *flg, uint64_t *aux, unsigned long long *err,
+                           hipStream_t st);
+hipError_t launch_bai_heads(const uint64_t *key, const uint64_t *win, const uint64_t *vbeg, uint64_t n,
+                            const uint64_t *lin_off, uint64_t *flg, uint64_t *lin, hipStream_t st);
+// pre: the exclusive scan of flg[0..n]; ridx: nruns words; runs: nruns entries
+hipError_t launch_bai_runs(const uint64_t *flg, const uint64_t *pre, uint64_t n, uint64_t nruns, const uint64_t *key,
+                           const uint64_t *vbeg, const uint64_t *aux, uint64_t *ridx, sbh_bai_run *runs,
+                           hipStream_t st);
 // BGZF footer CRC32 of every inflated, non-truncated block (crc.hip).
 hipError_t launch_block_crc(const uint8_t *comp, DevBlocks bl, uint64_t nblocks, const uint8_t *U,
                             unsigned long long *n_bad, unsigned long long *first_bad, hipStream_t st);
@@ -226,7 +238,7 @@ hipError_t launch_member_footer(const uint8_t *src, uint64_t n, uint64_t b0, uin
 //                                 n_unknown, min_unknown, close_n, Counts [4, 403),
 //                                 rbe [403, 1747)); FindRecordStart best [8]; chain walk
 //                                 [16, 20); chain marks [20, 26); block CRCs [32, 34);
-//                                 check-records [40, 46); first bad block [100]
+//                                 check-records [40, 46); BAI scan [40, 48); first bad block [100]
 //   persistent [CTR_TRUE_SPREAD, +CTR_TRUE_WORDS)  k_eager's per-wave true counts: must be
 //                                 zero before every k_eager launch; k_fold_true folds them
 //                                 into n_true and zeroes them again

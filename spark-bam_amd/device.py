@@ -7,9 +7,14 @@ import numpy as np
 
 from .records import record_columns
 
-from ._lib import (SBH_OK, SbhBatchSplit, SbhBlock, SbhCheckOpts, SbhCheckResult, SbhRecordsOut, SbhRecordsSizes,
-                   SbhShardResult, SbhSplitBatchResult, SbhSplitRecordsResult, SbhStreamOpts, SbhStreamResult,
-                   SparkBamError, error_for, lib)
+from ._lib import (SBH_OK, SbhBaiSizes, SbhBatchSplit, SbhBlock, SbhCheckOpts, SbhCheckResult, SbhRecordsOut,
+                   SbhRecordsSizes, SbhShardResult, SbhSplitBatchResult, SbhSplitRecordsResult, SbhStreamOpts,
+                   SbhStreamResult, SparkBamError, error_for, lib)
+
+
+# sbh_bai_run (include/sparkbam.h)
+BAI_RUN_DTYPE = np.dtype([("ref_id", "<i4"), ("bin", "<u4"), ("vbeg", "<u8"), ("vend", "<u8"),
+                          ("n_mapped", "<u8"), ("n_unmapped", "<u8")])
 
 
 def _check(ctx_handle, rc):
@@ -564,6 +569,26 @@ class Shard:
         out = SbhRecordsOut(**{k: v.ctypes.data if v.size else None for k, v in cols.items()})
         self._c(lib().sbh_records_fetch(self.h, C.byref(out)))
         return cols
+
+    def bai_scan(self, first_flat, end_flat):
+        """The BAI runs and linear-index minima of the records from first_flat while the start
+        is < end_flat (sbh_bai_scan + sbh_bai_fetch; needs set_contigs): (runs as a numpy
+        structured array of BAI_RUN_DTYPE, lin as uint64 with UINT64_MAX = untouched,
+        n_no_coor)."""
+        sz = SbhBaiSizes()
+        self._c(lib().sbh_bai_scan(self.h, int(first_flat), int(end_flat), C.byref(sz)))
+        runs = np.zeros(sz.n_runs, dtype=BAI_RUN_DTYPE)
+        lin = np.empty(sz.lin_size, dtype=np.uint64)
+        self._c(lib().sbh_bai_fetch(self.h, _ptr(runs) if sz.n_runs else None, _ptr(lin) if sz.lin_size else None))
+        return runs, lin, sz.n_no_coor
+
+    def bai_edges(self):
+        """(first ref_id, first pos, last ref_id, last pos) of the last bai_scan (sbh_bai_edges):
+        its first record and its last record with a reference (ref_id -1: none), for the
+        ordering check between windows."""
+        e = [C.c_int32() for _ in range(4)]
+        self._c(lib().sbh_bai_edges(self.h, *(C.byref(x) for x in e)))
+        return tuple(x.value for x in e)
 
     def stage_times(self):
         """[index, inflate+eager pipeline, eager (sum of launches), records, k_huff

@@ -282,15 +282,23 @@ def load_bam_intervals(path, intervals, split_size=DEFAULT_SPLIT_SIZE,
     ranges lie within `merge_gap` of each other share one device shard [first chunk's
     block, last chunk's end block + halo); the halo grows x4 while a result depends on
     bytes past it (SBH_E_NEED_HALO: an eager check reads on; SBH_E_BAD_RECORD: a kept
-    record runs past the shard)."""
+    record runs past the shard).
+
+    bai: the index as a path or bytes; None reads path + ".bai"; the string "build" builds it
+    in memory on the same context (bai.build_bai; in windows for a file too large to hold
+    resident), for a BAM that has no index file."""
     from .sharded import bytes_reader, file_reader, read_header
-    index = read_bai(bai if bai is not None else str(path) + ".bai")
+    build = isinstance(bai, str) and bai == "build"
+    index = None if build else read_bai(bai if bai is not None else str(path) + ".bai")
     read = bytes_reader(path) if isinstance(path, (bytes, bytearray, memoryview, np.ndarray)) \
         else file_reader(path)
     size = read.size
     own_ctx = ctx is None
     ctx = ctx or Context(0)
     try:
+        if build:
+            from .bai import build_bai, resident_window
+            index = read_bai(build_bai(path, ctx=ctx, window=resident_window(size), reads_to_check=reads_to_check))
         names, lens, _ = read_header(ctx, read, size)
         names = list(names)
         loci = parse_loci(intervals, dict(zip(names, (int(x) for x in lens))))
