@@ -9,6 +9,7 @@
 //   spark-bam index-blocks  BAM [OUT]                        (bgzf/index/IndexBlocks.scala)
 //   spark-bam index-records BAM [OUT]                        (check/index/IndexRecords.scala)
 //   spark-bam index-bai     BAM [OUT]                        (the .bai samtools index writes; htslib hts.c)
+//   spark-bam view [-h] [-o FILE] BAM                        (the records as SAM text: htsjdk getSAMString)
 //   spark-bam check-blocks -s [-r RECORDS] [-l N] BAM        (cli/.../check/blocks/CheckBlocks.scala)
 //   spark-bam htsjdk-rewrite [-r READS] [-b] [-i] [--index-bai] BAM OUT  (cli/.../rewrite/HTSJDKRewrite.scala)
 //
@@ -247,6 +248,7 @@ struct Args {
   // OUT.records / OUT.bai
   std::vector<std::pair<uint64_t, uint64_t>> read_ranges;
   bool has_read_ranges = false, idx_blocks = false, idx_records = false, idx_bai = false;
+  bool sam_header = false;  // view -h: the BAM header text first
 };
 
 Args parse(int argc, char **argv) {
@@ -255,7 +257,8 @@ Args parse(int argc, char **argv) {
     throw Error(SBH_E_ARG,
                 "usage: spark-bam <command> [options] <bam>\n"
                 "  commands: compute-splits count-reads check-bam full-check index-blocks index-records index-bai\n"
-                "            check-blocks htsjdk-rewrite");
+                "            check-blocks htsjdk-rewrite view\n"
+                "  view [-h|--header] [-o FILE] <bam>: the records as SAM text (-h: the header text first)");
   a.cmd = argv[1];
   const bool rewrite = a.cmd == "htsjdk-rewrite";
   std::vector<std::string> pos;
@@ -269,6 +272,8 @@ Args parse(int argc, char **argv) {
     else if (rewrite && (t == "-b" || t == "--index-blocks")) a.idx_blocks = true;
     else if (rewrite && (t == "-i" || t == "--index-records")) a.idx_records = true;
     else if (rewrite && t == "--index-bai") a.idx_bai = true;
+    else if (a.cmd == "view" && (t == "-h" || t == "--header")) a.sam_header = true;
+    else if (a.cmd == "view" && (t == "-o" || t == "--output")) a.out = next();
     else if (t == "-m" || t == "--max-split-size") { a.split = parse_bytes(next()); a.has_split = true; }
     else if (t == "-s" || t == "--spark-bam") a.s = true;
     else if (t == "-u" || t == "--upstream" || t == "--hadoop-bam") a.u = true;
@@ -886,6 +891,50 @@ int index_bai(const Args &a) {
   return 0;
 }
 
+// The records as SAM text (one line per record, htsjdk SAMRecord.getSAMString), whole file
+// resident as index-bai holds it: the eager calls give the record starts, sbh_records_scan
+// decodes from the header's end, sbh_records_sam_scan renders on the device, the fetch brings the
+// text back.  -h: the BAM header text (the l_text bytes after the magic) first, verbatim.
+int view(const Args &a) {
+  Loaded L(a.path);
+  uint64_t seg_end = L.flat;
+  for (const sbh_block &b : L.blocks)
+    if (b.flags & SBH_BLOCK_EMPTY) { seg_end = b.ustart; break; }
+  std::vector<char> text;
+  uint64_t head = 0;
+  if (a.sam_header) {
+    uint8_t lt[4];
+    chk(sbh_read_flat(L.sh, 4, 4, lt), "read header");
+    const int32_t l_text = rd32(lt);
+    if (l_text < 0 || 8 + (uint64_t)l_text > L.hdr.end) throw Error(SBH_E_ARG, "bad BAM header text length");
+    head = (uint64_t)l_text;
+    text.resize(head);
+    if (head) chk(sbh_read_flat(L.sh, 8, head, (uint8_t *)text.data()), "read header text");
+  }
+  if (seg_end > L.hdr.end) {
+    uint64_t n = 0;
+    chk(sbh_check_eager(L.sh, L.hdr.end, seg_end, a.reads_to_check, nullptr, &n), "eager");
+    sbh_records_sizes rs{};
+    chk(sbh_records_scan(L.sh, L.hdr.end, seg_end, &rs), "records scan");
+    std::string names;
+    std::vector<uint64_t> off(1, 0);
+    for (const std::string &s : L.hdr.names) {
+      names += s;
+      off.push_back(names.size());
+    }
+    sbh_sam_sizes sz{};
+    chk(sbh_records_sam_scan(L.sh, names.data(), off.data(), (int32_t)L.hdr.names.size(), &sz), "sam scan");
+    text.resize(head + sz.text_bytes);
+    chk(sbh_records_sam_fetch(L.sh, text.data() + head, nullptr), "sam fetch");
+  }
+  FILE *f = a.out.empty() ? stdout : fopen(a.out.c_str(), "wb");
+  if (!f) throw Error(SBH_E_ARG, "cannot write " + a.out);
+  const bool ok = fwrite(text.data(), 1, text.size(), f) == text.size() && fflush(f) == 0;
+  if (f != stdout) fclose(f);
+  if (!ok) throw Error(SBH_E_ARG, "short write to " + (a.out.empty() ? std::string("stdout") : a.out));
+  return 0;
+}
+
 // HTSJDKRewrite (cli/.../rewrite/HTSJDKRewrite.scala:40-92): the BAM's uncompressed stream --
 // header, then every record, or only the records whose index is in -r (:48-58) -- re-cut into
 // 65498-byte BGZF members on the GPU (sbh_bgzf_compress) plus the EOF member; -b / -i then
@@ -1093,6 +1142,7 @@ int main(int argc, char **argv) {
     else if (a.cmd == "index-bai") rc = index_bai(a);
     else if (a.cmd == "check-blocks") rc = check_blocks(a);
     else if (a.cmd == "htsjdk-rewrite") rc = htsjdk_rewrite(a);
+    else if (a.cmd == "view") rc = view(a);
     else throw Error(SBH_E_ARG, "unknown command " + a.cmd);
     sbh_ctx_destroy(g_ctx);
     return rc;

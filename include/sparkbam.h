@@ -111,6 +111,7 @@ const char *sbh_last_error(const sbh_ctx *ctx);
  *   SBH_E_INFLATE_SIZE         {block start, expected bytes}  -> IOException (Stream.scala:52-54)
  *   SBH_E_INFLATE_DATA         {block start}  -> DataFormatException
  *   SBH_E_UNSORTED             {virtual offset of the first offending record}  (sbh_bai_scan)
+ *   SBH_E_BAD_RECORD           {row of the first malformed record}  (sbh_records_sam_scan only)
  *   anything else              no fields */
 int32_t sbh_last_error_detail(const sbh_ctx *ctx, int32_t *code, int64_t *fields, int32_t cap);
 /* Use a caller-owned hipStream_t (e.g. torch.cuda.current_stream().cuda_stream). */
@@ -591,6 +592,41 @@ int sbh_bai_edges(sbh_shard *sh, int32_t *first_ref, int32_t *first_pos, int32_t
 uint64_t sbh_bai_bound(uint64_t n_runs, uint64_t lin_size, int32_t n_ref);
 int sbh_bai_build(const sbh_bai_run *runs, uint64_t n_runs, const uint64_t *lin, const int32_t *contig_len,
                   int32_t n_ref, uint64_t n_no_coor, uint8_t *out, uint64_t cap, uint64_t *size);
+
+/* ---- SAM text ----------------------------------------------------------------------------
+ * The records of the last decoded scan as SAM text, one line per record ending in '\n', rendered
+ * on the device: what htsjdk SAMRecord.getSAMString prints (the reference's .sam fixtures under test_bams).
+ * Eleven tab-separated fields -- QNAME (the name bytes up to the first NUL), FLAG, RNAME (the
+ * name of 0 <= ref_id < n_ref, else "*"), POS (pos + 1), MAPQ, CIGAR ("*" for no ops), RNEXT ("*"
+ * for next_ref_id < 0, "=" for next_ref_id == ref_id, the name below n_ref, else "*"), PNEXT, TLEN,
+ * SEQ ("*" for l_seq == 0), QUAL ("*" for l_seq == 0 or a first quality byte 0xFF, else byte + 33)
+ * -- then "\tTG:T:VALUE" per tag: A the byte, c C s S i I ":i:" and the decimal value, Z / H the
+ * bytes up to the NUL, B ":B:<sub>" and ",<value>" per element, f and B:f Java's Float.toString
+ * (csrc/sam_core.h holds the definition for device and host).
+ * rows = the rows of the last decoded scan on this shard (sbh_records_scan,
+ * sbh_records_scan_regions, sbh_split_records / sbh_split_records_batch with decode != 0), in their
+ * order: after a batch, split i's text is text[line_off[rec_begin] .. line_off[rec_begin +
+ * rec_count]).  ref_names packed, name k = ref_names[ref_name_off[k] .. ref_name_off[k + 1]).
+ * sbh_records_sam_scan renders into device memory and reports the sizes; sbh_records_sam_fetch
+ * copies the text (text_bytes bytes, no terminator) and the lines' prefix offsets out (either
+ * pointer may be NULL).  n_host = rows holding an f or B:f tag: their lines are rendered on the
+ * host inside the library (Float.toString needs strtof) and land in the text with the fetch.
+ * Errors: SBH_E_STATE without a valid decoded scan (none yet, or the last was decode == 0);
+ * SBH_E_BAD_RECORD {row} for the first row whose CIGAR has an op code above 8 (htsjdk throws) or
+ * whose tag area is malformed: an unknown type or B sub-type byte, a value running past the
+ * record's tag bytes, a Z / H without a NUL inside them, a negative B count, 1 or 2 bytes left
+ * after the last tag.  n == 0 gives text_bytes = 0 and line_off = [0]. */
+typedef struct { uint64_t n, text_bytes, n_host; } sbh_sam_sizes;
+int sbh_records_sam_scan(sbh_shard *sh, const char *ref_names, const uint64_t *ref_name_off,
+                         int32_t n_ref, sbh_sam_sizes *out);
+int sbh_records_sam_fetch(sbh_shard *sh, char *text /* [text_bytes] */, uint64_t *line_off /* [n+1] */);
+/* HOST ONLY, no context, no GPU (like sbh_bai_build): the same text for the records at starts[]
+ * of a flat BAM stream.  line_off (n + 1 entries) is always filled; text == NULL: sizes only.
+ * SBH_E_BAD_RECORD with *bad_row = the first row that does not fit the stream or its block_size
+ * (as sbh_records_scan judges) or is malformed as above; SBH_E_ARG when text_cap < line_off[n]. */
+int sbh_sam_render_host(const uint8_t *flat, uint64_t flat_size, const uint64_t *starts, uint64_t n,
+                        const char *ref_names, const uint64_t *ref_name_off, int32_t n_ref,
+                        char *text, uint64_t text_cap, uint64_t *line_off, uint64_t *bad_row);
 
 /* ---- BGZF writer -------------------------------------------------
  * The block compressor behind HTSJDKRewrite (cli/src/main/scala/org/hammerlab/bam/rewrite/

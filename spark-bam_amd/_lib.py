@@ -44,6 +44,7 @@ EXPORTS = [
     "sbh_bgzf_compress_bound", "sbh_bgzf_compress", "sbh_bgzf_compress_level",
     "sbh_shard_load", "sbh_find_blocks", "sbh_check_stream", "sbh_split_records", "sbh_split_records_batch",
     "sbh_bai_scan", "sbh_bai_fetch", "sbh_bai_edges", "sbh_bai_bound", "sbh_bai_build",
+    "sbh_records_sam_scan", "sbh_records_sam_fetch", "sbh_sam_render_host",
 ]
 LEVEL_HTSJDK, LEVEL_FAST = 5, -1  # sbh_bgzf_compress_level: htsjdk's zlib level 5 / this library's own coder
 
@@ -117,6 +118,10 @@ class SbhSplitBatchResult(C.Structure):
 class SbhBaiSizes(C.Structure):
     _fields_ = [("n_records", C.c_uint64), ("n_runs", C.c_uint64), ("n_no_coor", C.c_uint64),
                 ("lin_size", C.c_uint64)]
+
+
+class SbhSamSizes(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("text_bytes", C.c_uint64), ("n_host", C.c_uint64)]
 
 
 class SbhRecordsOut(C.Structure):  # host buffers (sbh_records_out); NULL = not copied
@@ -245,6 +250,9 @@ def lib():
         "sbh_bai_fetch": [P, P, P],
         "sbh_bai_edges": [P, PI32, PI32, PI32, PI32],
         "sbh_bai_build": [P, U64, P, P, I32, U64, P, U64, PU64],
+        "sbh_records_sam_scan": [P, P, P, I32, C.POINTER(SbhSamSizes)],
+        "sbh_records_sam_fetch": [P, P, P],
+        "sbh_sam_render_host": [P, U64, P, U64, P, P, I32, P, U64, P, PU64],
         "sbh_bgzf_compress": [P, P, U64, I32, P, U64, PU64, PU64, C.POINTER(C.c_float)],
         "sbh_bgzf_compress_level": [P, P, U64, I32, I32, P, U64, PU64, PU64, C.POINTER(C.c_float)],
     }

@@ -219,6 +219,13 @@ def iter_reads(path_or_bytes, window=None, halo=4 << 20, ctx=None, reads_to_chec
     time; yields one columnar `Reads` batch per window, in file order, each with a `vpos` column
     (htsjdk virtual offsets; `flat` is window-relative).  A window starts at the block of the
     previous window's chain exit, so batches never overlap."""
+    return _iter_windows(path_or_bytes, lambda sh, f, E, names: Reads(sh.records(f, E), names), window, halo, ctx,
+                         reads_to_check)
+
+
+def _iter_windows(path_or_bytes, deliver, window=None, halo=4 << 20, ctx=None, reads_to_check=DEFAULT_READS_TO_CHECK):
+    """iter_reads' walk through the file; deliver(shard, first_flat, end_flat, names) turns a
+    window's records into what is yielded (anything with a len(): empty ones are dropped)."""
     window = int(window or STREAM_WINDOW)
     data = _file_array(path_or_bytes)
     size = int(data.size)
@@ -246,7 +253,7 @@ def iter_reads(path_or_bytes, window=None, halo=4 << 20, ctx=None, reads_to_chec
                     if seg is not None:
                         E = min(E, seg)
                     sh.check_eager(f, E, reads_to_check, want_bits=False)
-                    cols = sh.records(f, E) if E > f else None
+                    batch = deliver(sh, f, E, names) if E > f else None
                     n, x = sh.chain_from(f, E) if E > f else (0, f)
                     if not last and x >= sh.flat_size:
                         raise SparkBamError(SBH_E_NEED_HALO, "the chain leaves the halo")
@@ -258,14 +265,72 @@ def iter_reads(path_or_bytes, window=None, halo=4 << 20, ctx=None, reads_to_chec
                     halo *= 4
                 finally:
                     sh.close()
-            if cols is not None and cols["flat"].size:
-                yield Reads(cols, names)
+            if batch is not None and len(batch):
+                yield batch
             if last:
                 return
             start, lo = nxt, nxt >> 16
     finally:
         if own_ctx:
             ctx.close()
+
+
+def view(path_or_bytes, header=False, out=None, window=None, ctx=None, reads_to_check=DEFAULT_READS_TO_CHECK):
+    """The file's records as SAM text, one line per record (what `samtools view` / htsjdk
+    SAMRecord.getSAMString print; the reference's test_bams .sam fixtures), rendered on the GPU
+    (Shard.records_sam) a window at a time, with iter_reads' windowing.  header=True puts the BAM
+    header text first, verbatim.  out: a binary file object the text is written to as it is
+    produced (returns the byte count); None: returns the text as bytes."""
+    data = _file_array(path_or_bytes)
+    own_ctx = ctx is None
+    ctx = ctx or Context(0)
+    parts, total = [], 0
+
+    def put(b):
+        nonlocal total
+        total += len(b)
+        if out is None:
+            parts.append(bytes(b))
+        else:
+            out.write(b)
+
+    def deliver(sh, f, E, names):
+        sh.records_scan(f, E)
+        return sh.records_sam(names)[0]
+
+    try:
+        if header:
+            put(header_text(ctx, data))
+        for text in _iter_windows(data, deliver, window, ctx=ctx, reads_to_check=reads_to_check):
+            put(text.data)
+    finally:
+        if own_ctx:
+            ctx.close()
+    return b"".join(parts) if out is None else total
+
+
+def header_text(ctx, data):
+    """The BAM header's text (the l_text bytes after the magic), from the file's leading blocks
+    inflated on the device."""
+    size = int(data.size)
+    n = min(size, 1 << 20)
+    while True:
+        sh = ctx.shard(np.ascontiguousarray(data[:n]), file_offset=0, file_size=size)
+        try:
+            sh.index(0)
+            sh.inflate()
+            flat = sh.read_flat(0, sh.flat_size)
+        finally:
+            sh.close()
+        if flat.size >= 8 and bytes(flat[:4]) != b"BAM\1":
+            raise SparkBamError(1, "not a BAM file (missing BAM\\1 magic)")
+        if flat.size >= 8:
+            l_text = int.from_bytes(bytes(flat[4:8]), "little", signed=True)
+            if 8 + l_text <= flat.size:
+                return bytes(flat[8:8 + l_text])
+        if n >= size:
+            raise SparkBamError(12, "truncated BAM header")
+        n = min(size, n * 4)
 
 
 def load_bam_count(path_or_bytes, split_size=DEFAULT_SPLIT_SIZE, ctx=None, **kw):

@@ -193,6 +193,24 @@ hipError_t launch_bai_heads(const uint64_t *key, const uint64_t *win, const uint
 hipError_t launch_bai_runs(const uint64_t *flg, const uint64_t *pre, uint64_t n, uint64_t nruns, const uint64_t *key,
                            const uint64_t *vbeg, const uint64_t *aux, uint64_t *ridx, sbh_bai_run *runs,
                            hipStream_t st);
+// SAM text of the decoded records (sam.hip; the line is defined in sam_core.h).  len / hostf: n + 1
+// words (the caller zeroes entry n); names / name_off: the packed reference names on the device.
+hipError_t launch_sam_sizes(const uint8_t *U, const uint64_t *pos, uint64_t n, const uint64_t *nm_off,
+                            const uint64_t *cg_off, const uint64_t *sq_off, const uint64_t *ax_off, const char *names,
+                            const uint64_t *name_off, int32_t n_ref, uint64_t *len, uint64_t *hostf,
+                            unsigned long long *bad, hipStream_t st);
+hipError_t launch_sam_emit(const uint8_t *U, const uint64_t *pos, uint64_t n, const uint64_t *nm_off,
+                           const uint64_t *cg_off, const uint64_t *sq_off, const uint64_t *ax_off, const char *names,
+                           const uint64_t *name_off, int32_t n_ref, const uint64_t *line_off, const uint64_t *hostf,
+                           char *text, hipStream_t st);
+// the rows with hostf set (hpre: its exclusive scan), compacted: their indices and record sizes;
+// their bytes packed at goff; their lines' lengths back into len
+hipError_t launch_sam_host_rows(const uint8_t *U, const uint64_t *pos, const uint64_t *hostf, const uint64_t *hpre,
+                                uint64_t n, uint64_t *rows, uint64_t *rec_bytes, hipStream_t st);
+hipError_t launch_sam_gather(const uint8_t *U, const uint64_t *pos, const uint64_t *rows, const uint64_t *goff,
+                             uint64_t m, uint8_t *out, hipStream_t st);
+hipError_t launch_sam_scatter(const uint64_t *rows, const uint64_t *vals, uint64_t m, uint64_t n, uint64_t *len,
+                              hipStream_t st);
 // BGZF footer CRC32 of every inflated, non-truncated block (crc.hip).
 hipError_t launch_block_crc(const uint8_t *comp, DevBlocks bl, uint64_t nblocks, const uint8_t *U,
                             unsigned long long *n_bad, unsigned long long *first_bad, hipStream_t st);

@@ -5,11 +5,11 @@ import weakref
 
 import numpy as np
 
-from .records import record_columns
+from .records import pack_ref_names, record_columns
 
 from ._lib import (SBH_OK, SbhBaiSizes, SbhBatchSplit, SbhBlock, SbhCheckOpts, SbhCheckResult, SbhRecordsOut,
-                   SbhRecordsSizes, SbhShardResult, SbhSplitBatchResult, SbhSplitRecordsResult, SbhStreamOpts,
-                   SbhStreamResult, SparkBamError, error_for, lib)
+                   SbhRecordsSizes, SbhSamSizes, SbhShardResult, SbhSplitBatchResult, SbhSplitRecordsResult,
+                   SbhStreamOpts, SbhStreamResult, SparkBamError, error_for, lib)
 
 
 # sbh_bai_run (include/sparkbam.h)
@@ -569,6 +569,32 @@ class Shard:
         out = SbhRecordsOut(**{k: v.ctypes.data if v.size else None for k, v in cols.items()})
         self._c(lib().sbh_records_fetch(self.h, C.byref(out)))
         return cols
+
+    def records_scan(self, first_flat, end_flat):
+        """records() without the copy-out: the decoded columns stay on the device (for
+        records_sam).  Returns the number of records."""
+        sz = SbhRecordsSizes()
+        self._c(lib().sbh_records_scan(self.h, int(first_flat), int(end_flat), C.byref(sz)))
+        return sz.n
+
+    def records_sam(self, ref_names, want_text=True):
+        """The SAM text of the rows of the last decoded scan on this shard (records,
+        records_regions, split_records / split_records_batch with decode), rendered on the GPU
+        (sbh_records_sam_scan + sbh_records_sam_fetch): (text as a uint8 array, one line per
+        record ending in a newline; line_off, uint64 [n + 1], line i = text[line_off[i]:line_off[i + 1]]).
+        ref_names: the contig names (str or bytes).  `self.sam_n_host` = rows holding an f / B:f
+        tag, rendered on the host inside the library.  want_text=False leaves the text on the
+        device and returns (None, None) (a measurement of the scan alone)."""
+        names, off = pack_ref_names(ref_names)
+        sz = SbhSamSizes()
+        self._c(lib().sbh_records_sam_scan(self.h, _ptr(names), _ptr(off), int(off.size - 1), C.byref(sz)))
+        self.sam_n_host = int(sz.n_host)
+        if not want_text:
+            return None, None
+        text = np.empty(sz.text_bytes, dtype=np.uint8)
+        line_off = np.zeros(sz.n + 1, dtype=np.uint64)
+        self._c(lib().sbh_records_sam_fetch(self.h, _ptr(text) if text.size else None, _ptr(line_off)))
+        return text, line_off
 
     def bai_scan(self, first_flat, end_flat):
         """The BAI runs and linear-index minima of the records from first_flat while the start

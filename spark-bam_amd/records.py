@@ -115,6 +115,46 @@ def tags_text(aux):
     return out
 
 
+def pack_ref_names(ref_names):
+    """Contig names (str or bytes) packed for the C-ABI: (uint8 bytes, uint64 [n + 1] offsets)."""
+    raw = [n if isinstance(n, (bytes, bytearray)) else str(n).encode("latin-1") for n in ref_names]
+    off = np.zeros(len(raw) + 1, dtype=np.uint64)
+    if raw:
+        off[1:] = np.cumsum([len(r) for r in raw])
+    return np.frombuffer(b"".join(raw) + b"\0", dtype=np.uint8), off
+
+
+def sam_text_host(flat, starts, ref_names, want_text=True):
+    """The SAM text of the records at `starts` of a flat BAM stream, rendered on the host by the
+    library (sbh_sam_render_host: no GPU, the renderer the device path shares its definition with
+    and uses for rows with float tags): (text as uint8, line_off uint64 [n + 1]); want_text=False:
+    (None, line_off).  Raises SparkBamError(SBH_E_BAD_RECORD) with `.fields = (row,)` for the first
+    malformed record.  Unlike sam_line / tags_text it refuses a malformed tag area, as htsjdk does."""
+    import ctypes as C
+
+    from ._lib import SBH_OK, SparkBamError, lib
+    flat = np.ascontiguousarray(np.frombuffer(flat, dtype=np.uint8) if not isinstance(flat, np.ndarray) else flat)
+    st = np.ascontiguousarray(starts, dtype=np.uint64)
+    names, off = pack_ref_names(ref_names)
+    line_off = np.zeros(st.size + 1, dtype=np.uint64)
+    bad = C.c_uint64()
+    p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+
+    def call(text):
+        rc = lib().sbh_sam_render_host(p(flat), flat.size, p(st), st.size, p(names), p(off), off.size - 1,
+                                       p(text) if text is not None and text.size else None,
+                                       0 if text is None else text.size, p(line_off), C.byref(bad))
+        if rc != SBH_OK:
+            raise SparkBamError(rc, "record %d is malformed" % bad.value if rc == 20 else "sam_text_host", (bad.value,))
+    call(None)
+    if not want_text:
+        return None, line_off
+    text = np.empty(int(line_off[-1]), dtype=np.uint8)
+    if text.size:
+        call(text)
+    return text, line_off
+
+
 class Reads:
     """A decoded batch: fixed fields as arrays, variable-length fields packed."""
 
