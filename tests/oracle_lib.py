@@ -49,6 +49,7 @@ def lib():
     P, I32, I64, U32, U64 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_uint64
     sig = {
         "or_header_make": (C.c_int, [P, I64, C.POINTER(I32), C.POINTER(I32)]),
+        "or_metadata_next": (C.c_int, [P, I64, I64, C.POINTER(Block)]),
         "or_metadata_stream": (I64, [P, I64, I64, P, I64]),
         "or_find_block_start": (C.c_int, [P, I64, I64, I32, C.POINTER(I64)]),
         "or_stream_open": (P, [P, I64, I64]),
@@ -201,6 +202,24 @@ class OracleFile:
                             self.contig_len.size, blocks_to_check, reads_to_check,
                             max_read_size, C.byref(v), C.byref(n))
         return rc, v.value, n.value
+
+
+def metadata_next(data, pos):
+    """MetadataStream._advance at file offset pos: (status, (start, csize, hsize, usize, empty));
+    status OR_END with the block filled in is the empty block that ends the stream, OR_END at
+    fewer than 18 remaining bytes leaves it zero."""
+    b = Block()
+    rc = lib().or_metadata_next(_ptr(data), int(data.size), int(pos), C.byref(b))
+    return rc, (b.start, b.csize, b.hsize, b.usize, b.empty)
+
+
+def metadata_stream(data, start=0):
+    """The blocks MetadataStream yields from `start` as (start, csize, hsize, usize, empty), or the
+    negated oracle status of the exception that ends it."""
+    cap = int(data.size) // 28 + 2
+    out = (Block * cap)()
+    n = lib().or_metadata_stream(_ptr(data), int(data.size), int(start), out, cap)
+    return n if n < 0 else [(b.start, b.csize, b.hsize, b.usize, b.empty) for b in out[:n]]
 
 
 def file_splits(file_size, split_size):
