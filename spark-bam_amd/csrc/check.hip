@@ -328,19 +328,6 @@ __device__ __forceinline__ void stage_vec(uint4 *lds, const uint8_t *U, uint64_t
   }
 }
 
-// One dword of every 128-byte line of [p, p + n) (a lane per line) loaded into a register that
-// nothing waits for: the lines come into L2 / MALL for the workgroup that stages them later.
-// The caller keeps the result live (l2_keep) past a wait the compiler places for its own later
-// loads -- vector loads return in order, so that wait covers this one too and the register is
-// never reused while the load is in flight.
-__device__ __forceinline__ uint32_t l2_touch(const uint8_t *p, uint64_t n) {
-  uint32_t v = 0;
-  const uint64_t off = (uint64_t)threadIdx.x * 128;
-  if (off < n) asm volatile("global_load_dword %0, %1, off" : "=v"(v) : "v"(p + off) : "memory");
-  return v;
-}
-__device__ __forceinline__ void l2_keep(uint32_t v) { asm volatile("" ::"v"(v)); }
-
 __device__ __forceinline__ uint32_t seg_index(const Segs &sg, uint64_t p, uint32_t from) {
   uint32_t k = from;
   while (k + 1 < sg.n && sg.end[k] <= p) ++k;
@@ -369,7 +356,6 @@ struct EagerOut {
   unsigned long long *xq_n;
   uint64_t xq_cap;                // 0: every exact check runs inline
   unsigned long long *true_spread;  // k_eager: per-wave true counts, folded into n_true by k_fold_true
-  TileSum *tsum;                  // per tile: the chain proof's summary (nullptr: none)
   const uint32_t *sieve = nullptr;  // k_lz's first-filter bitmap, bit p = flat position p (nullptr: sweep here)
 };
 
@@ -412,12 +398,6 @@ constexpr uint32_t ESTAGE = EW + 512;     // staged bytes (records near the end 
 #define SBH_EQ_CHUNK 4096
 #endif
 constexpr uint32_t EQ_CHUNK = SBH_EQ_CHUNK;  // survivor-queue capacity
-#ifndef SBH_EAGER_PF
-#define SBH_EAGER_PF 0  // k_eager: the tile this many workgroups ahead is touched into L2 (A/B r06zb: 1024 slower, k_eager 2.42 -> 2.50 ms)
-#endif
-#ifndef SBH_EAGER_SHIFT_SWEEP
-#define SBH_EAGER_SHIFT_SWEEP 1  // k_eager's refID sweep: tests shifted into each word (see k_eager)
-#endif
 static_assert(EAGER_REACH >= ESTAGE + 32 + 16, "EAGER_REACH covers the staged window");
 
 // PosChecker.getRefPosError with the contig length already loaded (len_idx: len[idx]
@@ -534,7 +514,6 @@ __global__ __launch_bounds__(T) void k_eager(const uint8_t *__restrict__ U, uint
   __shared__ uint32_t lnk[EQ_CHUNK / 32], lfail[EQ_CHUNK / 32];  // per sorted candidate: LINK / FAIL step
   __shared__ uint32_t seg0, nq, wcnt[NWV];
   __shared__ uint64_t seg_end0;
-  __shared__ uint32_t ts_dirty;  // a result settled after this kernel (no chain summary)
   __shared__ uint16_t queue[EQ_CHUNK];
   const uint32_t *lds32 = reinterpret_cast<const uint32_t *>(ldsv);
   const uint64_t t0 = begin + (uint64_t)blockIdx.x * ETILE;
@@ -543,14 +522,9 @@ __global__ __launch_bounds__(T) void k_eager(const uint8_t *__restrict__ U, uint
   const uint64_t c0 = __builtin_readcyclecounter();
   uint32_t nsurv = 0, ncand = 0, nexact = 0;
 #endif
-  // the window of the tile SBH_EAGER_PF workgroups on (the one that starts about when this one
-  // ends, on the same XCD) into L2 / MALL while this one stages its own
-  uint32_t pfv = 0;
-  if (SBH_EAGER_PF) {
-    const uint64_t tn = begin + ((uint64_t)blockIdx.x + SBH_EAGER_PF) * ETILE;
-    const uint64_t sn = tn & ~15ull;
-    if (tn < end && sn < u_pad) pfv = l2_touch(U + sn, std::min<uint64_t>(ESTAGE + 32, u_pad - sn));
-  }
+  // (measured and removed: the window of the tile 1024 workgroups on -- the one that starts about
+  // when this one ends, on the same XCD -- touched into L2 / MALL while this one stages its own:
+  // A/B r06zb: slower, k_eager 2.42 -> 2.50 ms)
   stage_vec<NV>(ldsv, U, s0, u_pad);
   for (uint32_t i = threadIdx.x; i < EW / 32; i += T) { ok[i] = 0; nrm[i] = 0; und[i] = 0; }
   for (uint32_t i = threadIdx.x; i < ETILE / 32; i += T) res[i] = 0;
@@ -560,10 +534,8 @@ __global__ __launch_bounds__(T) void k_eager(const uint8_t *__restrict__ U, uint
     seg0 = k;
     seg_end0 = sg.end[k];
     nq = 0;
-    ts_dirty = 0;
   }
   __syncthreads();
-  l2_keep(pfv);
   Src s{U, lds32, s0, ESTAGE};  // >= EW + 15 + 44: every phase-A read is staged
   const uint32_t k0 = seg0;
   const uint64_t e0 = seg_end0;  // positions below e0 are in segment k0 (nearly all)
@@ -691,7 +663,6 @@ __global__ __launch_bounds__(T) void k_eager(const uint8_t *__restrict__ U, uint
     if (x < o.defer_cap) o.defer_pos[x] = t0 + i;
   };
   auto settle = [&](uint32_t i, uint32_t r) {  // a candidate's result (queue-driven paths)
-    if (r > 1) ts_dirty = 1;  // its bit is settled later (k_eager_xq / k_eager_defer) or unknown
     if (r == 1) {
       atomicOr(&res[i >> 5], 1u << (i & 31));
     } else if (r == EAGER_DEFER) {
@@ -754,7 +725,7 @@ __global__ __launch_bounds__(T) void k_eager(const uint8_t *__restrict__ U, uint
       lo_w = hi_w;
       msk[w] = word_keep(w, m);
     }
-  } else if (SBH_EAGER_SHIFT_SWEEP) {
+  } else {
     // each word's 32 refID tests shifted into it last position first (m = 2 m + test: one
     // add-with-carry per position, no per-position range logic); the word's range after
     static_assert(EMW * 8 >= EG, "the words cover the thread's groups");
@@ -775,23 +746,6 @@ __global__ __launch_bounds__(T) void k_eager(const uint8_t *__restrict__ U, uint
         }
       }
       msk[w] = word_keep(w, m);
-    }
-  } else {
-    uint32_t a = lds32[g0 + 1];
-#pragma unroll
-    for (uint32_t gi = 0; gi < EG; ++gi) {
-      const uint32_t g = g0 + gi;
-      const uint32_t b = lds32[g + 2];
-      uint32_t m4 = 0;
-#pragma unroll
-      for (uint32_t k = 0; k < 4; ++k) {
-        const uint32_t ref = __builtin_amdgcn_alignbyte(b, a, k);
-        const uint32_t ii = 4 * g + k - sa;  // wraps for positions before the window
-        const bool in = ii < EW && g < ngroups;
-        m4 |= (in && (ref + 1u < nref1 || ii >= fast_end)) ? 1u << k : 0u;
-      }
-      msk[(gi * 4) / 32] |= m4 << ((gi * 4) % 32);
-      a = b;
     }
   }
 #ifdef SBH_EPROBE
@@ -937,76 +891,6 @@ __global__ __launch_bounds__(T) void k_eager(const uint8_t *__restrict__ U, uint
 #ifdef SBH_EPROBE
     c4 = __builtin_readcyclecounter();
 #endif
-    if (SBH_TSUM_CODE && o.tsum) {
-      // each wave's quarter of the tile (EAGER_SUB positions, its lanes' result words): each true
-      // position's record step (its length field, staged) against the next true position of the
-      // quarter; the last one's step for k_verify_chain_w.  Wave-local: no barrier.
-      constexpr uint32_t TW = ETILE / 32 / T;  // result words per thread
-      static_assert(TW * T * 32 == ETILE && ETILE / NWV == EAGER_SUB, "whole result words per thread");
-      const uint32_t wt0 = threadIdx.x * TW;
-      uint32_t rw[TW];
-      bool any = false;
-#pragma unroll
-      for (uint32_t k = 0; k < TW; ++k) {
-        rw[k] = res[wt0 + k];
-        any = any || rw[k] != 0;
-      }
-      const uint64_t bal = __ballot(any);
-      uint32_t an = 0, af = ~0u;
-      uint64_t mystep = TS_NONE;
-      bool last = false;
-      if (any) {
-        uint32_t nx = ETILE;  // the first true position after this thread's words in the quarter
-        const uint64_t after = lane == WAVE - 1 ? 0ull : bal & (~0ull << (lane + 1));
-        if (after) {
-          const uint32_t tn = wid * WAVE + (uint32_t)__builtin_ctzll(after);
-#pragma unroll
-          for (uint32_t k = TW; k-- > 0;) {
-            const uint32_t x = res[tn * TW + k];
-            if (x) nx = 32 * (tn * TW + k) + __builtin_ctz(x);
-          }
-        }
-#pragma unroll
-        for (uint32_t k = 0; k < TW; ++k) {
-          uint32_t x = rw[k];
-          while (x) {
-            const uint32_t i = 32 * (wt0 + k) + __builtin_ctz(x);
-            x &= x - 1;
-            uint32_t nxt = nx;
-            if (x) {
-              nxt = 32 * (wt0 + k) + __builtin_ctz(x);
-            } else {
-#pragma unroll
-              for (uint32_t k2 = k + 1; k2 < TW; ++k2)
-                if (rw[k2] && nxt == nx) nxt = 32 * (wt0 + k2) + __builtin_ctz(rw[k2]);
-            }
-            const uint64_t q = t0 + i;
-            const uint64_t total = q < e0 ? e0 : sg.end[seg_index(sg, q, k0)];
-            const uint64_t step = q + 4 > total ? TS_NONE : q + 4 + (int64_t)(int32_t)s.word_at(q);
-            if (nxt < ETILE) {
-              if (step != t0 + nxt) {
-                ++an;
-                af = min(af, i - wid * EAGER_SUB);
-              }
-            } else {
-              mystep = step;
-              last = true;
-            }
-          }
-        }
-      }
-      an = __builtin_amdgcn_readlane(wave_incl_scan(an), WAVE - 1);
-#pragma unroll
-      for (uint32_t o2 = 1; o2 < WAVE; o2 <<= 1) af = min(af, (uint32_t)__shfl_xor(af, o2, WAVE));
-      const uint64_t lb = __ballot(last);
-      uint64_t sl = TS_NONE;
-      if (lb) {
-        const uint32_t l = (uint32_t)__builtin_ctzll(lb);
-        sl = (uint64_t)(uint32_t)__builtin_amdgcn_readlane((uint32_t)(mystep >> 32), l) << 32 |
-             (uint32_t)__builtin_amdgcn_readlane((uint32_t)mystep, l);
-      }
-      if (lane == 0) o.tsum[blockIdx.x * NWV + wid] = TileSum{ts_dirty ? TS_DIRTY : sl, an, af};
-    }
     write_res();
   } else {
     // ---- fallback (a survivor list overflowed, or rtc <= 0): per-thread survivor loop
@@ -1074,8 +958,6 @@ __global__ __launch_bounds__(T) void k_eager(const uint8_t *__restrict__ U, uint
     if (lane == 0 && wt)
       atomicAdd(o.true_spread + ((blockIdx.x * NWV + wid) % TRUE_SLOTS) * TRUE_STRIDE, (unsigned long long)wt);
   }
-  if (SBH_TSUM_CODE && o.tsum && !fast && lane == 0)  // (the fallback path leaves no summaries)
-    o.tsum[blockIdx.x * NWV + wid] = TileSum{TS_DIRTY, 0, ~0u};
 #ifdef SBH_EPROBE
   __shared__ uint32_t psurv, pcand, pexact, ntrue;
   if (threadIdx.x == 0) { psurv = 0; pcand = 0; pexact = 0; ntrue = 0; }
@@ -1134,21 +1016,6 @@ constexpr uint32_t FBW = FSN / 32;            // bitmap words
 #define SBH_FULL_FCCAP 256
 #endif
 constexpr uint32_t FCCAP = SBH_FULL_FCCAP;    // close calls buffered per workgroup
-#ifndef SBH_FULL_CTG_LDS
-#define SBH_FULL_CTG_LDS 1
-#endif
-#ifndef SBH_FULL_RUN
-#define SBH_FULL_RUN 0  // 1: Counts rows of equal consecutive failure words added once per run (A/B: 7.44 -> 7.50 ms, off)
-#endif
-#ifndef SBH_FULL_ACCF
-#define SBH_FULL_ACCF 1  // fast tiles: failures accounted without the success / unknown / rbe cases
-#endif
-#ifndef SBH_FULL_FAST
-#define SBH_FULL_FAST 1  // tiles far from a segment end: full_first_win (no end-of-stream cases)
-#endif
-#ifndef SBH_FULL_HOT
-#define SBH_FULL_HOT 0  // 1: fast tiles count the wave's most shared failure word by ballot (A/B r04o: 7.40 -> 7.89 ms at 4 M records: off)
-#endif
 constexpr uint32_t FCTG = 1024;               // contig lengths staged in LDS (more: read from global)
 constexpr uint32_t FULL_SLOW = 0xFFFFFFFFu;   // "take the exact path" (no valid word has all bits)
 constexpr uint32_t FULL_PASS = 0xFFFFFFFEu;   // the first record passes: the chain decides
@@ -1202,9 +1069,6 @@ __device__ __forceinline__ uint32_t full_first(const Src &s, const uint32_t *bna
   uint32_t f = ref_pos_error(x.idx, x.pos, c) << 1;
   if (x.rem < implied_min_remaining(rnl, nc, x.seq_len)) f |= 1u << 18;
   f |= ref_pos_error(x.nidx, x.npos, c) << 5;
-#ifdef SBH_FULL_FIXEDONLY  // A/B probe (timing only, results wrong): no read-name / CIGAR tests
-  if (f) return f;
-#endif
   uint64_t cur = p + 36;
   uint32_t a = q + 36;  // window offset of cur
   if (rnl == 0) {
@@ -1271,9 +1135,6 @@ __device__ __forceinline__ uint32_t full_first_win(const Src &s, const uint32_t 
   uint32_t f = ref_pos_error_bf(x.idx, x.pos, c) << 1;
   f |= x.rem < implied_min_remaining(rnl, nc, x.seq_len) ? 1u << 18 : 0u;
   f |= ref_pos_error_bf(x.nidx, x.npos, c) << 5;
-#ifdef SBH_FULL_FIXEDONLY  // A/B probe (timing only, results wrong): no read-name / CIGAR tests
-  if (f) return f;
-#endif
   uint32_t a = q + 36;  // window offset of the name / CIGAR
   if (rnl < 2) {
     f |= rnl == 0 ? 1u << 12 : 1u << 13;
@@ -1349,20 +1210,15 @@ __device__ uint32_t chain_full(const Src &s, const uint32_t *bname, const uint32
 #endif
 __global__ __launch_bounds__(T, SBH_FULL_WGS) void k_full(const uint8_t *__restrict__ U, uint64_t u_pad, uint64_t begin,
                                             uint64_t end, Segs sg, Ctg c, int32_t rtc, FullOut o, OpIdx oi) {
-#ifndef SBH_FULL_PACKED
-#define SBH_FULL_PACKED 0  // 1: Counts replicas as 16-bit counter pairs (A/B: 7.53 -> 7.72 ms, not kept)
-#endif
 #ifndef SBH_FULL_NREP
-#define SBH_FULL_NREP (SBH_FULL_PACKED ? 8 : 4)
+#define SBH_FULL_NREP 4
 #endif
-  // Counts histogram replicas, one per lane residue.  Packed: a row of 10 words per nnz, flags 2w
-  // and 2w + 1 as the low / high 16 bits of word w (a replica counts at most FTILE positions, so
-  // 16 bits hold it): the same LDS as 4 unpacked replicas gives 8, halving the lanes that add to
-  // one address in one instruction, and a failing position adds once per flag pair, not per flag.
-  constexpr uint32_t RW = SBH_FULL_PACKED ? 10 : 19;  // words per nnz row
-  static_assert(!SBH_FULL_PACKED || FTILE < 65536, "16-bit replica counters");
-  constexpr uint32_t NREP = SBH_FULL_NREP, REP = 21 * RW + (SBH_FULL_PACKED ? 1 : 2);  // (odd stride: replica
-                                                                 // bases on distinct banks)
+  // Counts histogram replicas, one per lane residue.
+  // (measured and removed: replicas packed as 16-bit counter pairs, a row of 10 words per nnz --
+  // the same LDS as 4 unpacked replicas gives 8, halving the lanes that add to one address in one
+  // instruction, and a failing position adds once per flag pair, not per flag: A/B 7.53 -> 7.72 ms)
+  constexpr uint32_t RW = 19;  // words per nnz row
+  constexpr uint32_t NREP = SBH_FULL_NREP, REP = 21 * RW + 2;  // (odd stride: replica bases on distinct banks)
   constexpr uint32_t SLOWCAP = 512;
   __shared__ uint4 ldsv[FNV];
   __shared__ uint32_t bname[FBW], bop[FBW];
@@ -1373,7 +1229,6 @@ __global__ __launch_bounds__(T, SBH_FULL_WGS) void k_full(const uint8_t *__restr
   __shared__ uint32_t seg0, nsucc, ncl, nslow;
   __shared__ uint64_t e0;
   __shared__ unsigned long long cbase;
-#if SBH_FULL_CTG_LDS
   // contig lengths in LDS (getRefPosError reads one for every position whose refID is valid:
   // inside records that is several per record, each an L1/L2 round trip from global memory)
   __shared__ int32_t ctgl[FCTG];
@@ -1381,7 +1236,6 @@ __global__ __launch_bounds__(T, SBH_FULL_WGS) void k_full(const uint8_t *__restr
     for (int32_t i = threadIdx.x; i < c.n; i += T) ctgl[i] = c.len[i];
     c.len = ctgl;
   }
-#endif
   const uint32_t *lds32 = reinterpret_cast<const uint32_t *>(ldsv);
   const uint64_t s0 = (begin & ~15ull) + (uint64_t)blockIdx.x * FTILE;  // 16-aligned tile start
   stage_vec<FNV>(ldsv, U, s0, u_pad);
@@ -1428,19 +1282,10 @@ __global__ __launch_bounds__(T, SBH_FULL_WGS) void k_full(const uint8_t *__restr
     if (nnz != 77) return;
 #endif
     uint32_t *row = myhist + nnz * RW;
-#if SBH_FULL_PACKED
-    while (f) {
-      const uint32_t w = __builtin_ctz(f) >> 1;
-      const uint32_t pr = (f >> (2 * w)) & 3u;
-      atomicAdd(&row[w], (pr & 1u) | (pr >> 1) << 16);
-      f &= ~(3u << (2 * w));
-    }
-#else
     while (f) {
       atomicAdd(&row[__builtin_ctz(f)], 1u);
       f &= f - 1;
     }
-#endif
     if (rbe > 0 && rbe < 64) atomicAdd(&o.rbe[nnz * 64 + rbe], 1ull);  // rare: positions past a record
     if (nnz <= 2) {
       const uint32_t slot = atomicAdd(&ncl, 1u);
@@ -1454,44 +1299,24 @@ __global__ __launch_bounds__(T, SBH_FULL_WGS) void k_full(const uint8_t *__restr
     }
   };
   // account() for a first-record failure of a fast tile: never success, unknown, TooFewFixed-
-  // BlockBytes alone or a readsBeforeError count, so only the Counts row and close calls
-  // Counts rows of a run of equal failure words are added once with the run's length: inside
-  // quality strings consecutive positions mostly fail the same checks (every field is ASCII)
-#if SBH_FULL_RUN
-  uint32_t run_f = 0, run_n = 0;
-  auto run_flush = [&]() {
-    if (run_n) {
-      uint32_t f = run_f;
-      uint32_t *row = myhist + __popc(f) * RW;
-      while (f) {
-        atomicAdd(&row[__builtin_ctz(f)], run_n);
-        f &= f - 1;
-      }
-    }
-  };
-#endif
+  // BlockBytes alone or a readsBeforeError count, so only the Counts row and close calls.
+  // (measured and removed: Counts rows of a run of equal consecutive failure words added once
+  // with the run's length -- inside quality strings consecutive positions mostly fail the same
+  // checks: A/B 7.44 -> 7.50 ms; the wave's most shared failure word counted by ballot, one add
+  // per wave when the hot word changes, against the same-address LDS atomics -- A/B r04o: 7.40
+  // -> 7.89 ms at 4 M records)
   auto account_fail = [&](uint64_t p, uint32_t r) {
     if (o.words) o.words[p - begin] = r;
     const uint32_t nnz = __popc(r);  // (a fast tile's failure word has no high bits)
 #ifdef SBH_FULL_NOHIST
     if (nnz != 77) return;
 #endif
-#if SBH_FULL_RUN
-    if (r == run_f) {
-      ++run_n;
-    } else {
-      run_flush();
-      run_f = r;
-      run_n = 1;
-    }
-#else
     uint32_t f = r;
     uint32_t *row = myhist + nnz * RW;
     while (f) {
       atomicAdd(&row[__builtin_ctz(f)], 1u);
       f &= f - 1;
     }
-#endif
     if (nnz <= 2) {
       const uint32_t slot = atomicAdd(&ncl, 1u);
       if (slot < FCCAP) {
@@ -1510,32 +1335,12 @@ __global__ __launch_bounds__(T, SBH_FULL_WGS) void k_full(const uint8_t *__restr
   };
   // a tile inside [begin, end) whose every position is FULL_FAST_REACH before its segment's
   // end meets no end-of-stream rule: its positions take full_first_win
-  const bool fast = SBH_FULL_FAST && rtc > 0 && s0 >= begin && s0 + FTILE <= end &&
+  const bool fast = rtc > 0 && s0 >= begin && s0 + FTILE <= end &&
                     s0 + FTILE + FULL_FAST_REACH <= e0;
   if (fast) {
     // queue overflows (more record starts in the tile than slowq holds) are kept as bits and
     // decided after the sweep, so the exact path is not inlined into every unrolled position
     uint32_t ovf = 0;
-#if SBH_FULL_HOT
-    // The wave's hot failure word: inside quality strings and sequences most of a wave's 64
-    // positions fail with one and the same word, and their per-flag LDS adds all land on the
-    // same counters (a same-address atomic serialises: the bulk of k_full's bank conflicts).
-    // Lanes whose word equals the hot word only count (one ballot popcount per wave); the count
-    // goes into the word's Counts row when the hot word changes (to a word more lanes share) and
-    // after the sweep.  Words with <= 2 flags (close calls, listed per position) are never hot.
-    uint32_t hotw = 0, hotn = 0;  // wave-uniform; 0 is no failure word
-    const uint32_t lane = threadIdx.x & (WAVE - 1);
-    auto hot_flush = [&]() {
-      if (hotn && lane == 0) {
-        uint32_t f = hotw;
-        uint32_t *row = myhist + __popc(f) * RW;
-        while (f) {
-          atomicAdd(&row[__builtin_ctz(f)], hotn);
-          f &= f - 1;
-        }
-      }
-    };
-#endif
     for (uint32_t step = 0; step < FTILE / (FPL * T); ++step) {
       const uint32_t j = threadIdx.x + step * T;
       const uint4 v0 = ldsv[j], v1 = ldsv[j + 1], v2 = ldsv[j + 2];
@@ -1556,47 +1361,16 @@ __global__ __launch_bounds__(T, SBH_FULL_WGS) void k_full(const uint8_t *__restr
           x.npos = (int32_t)__builtin_amdgcn_alignbyte(D[b + 8], D[b + 7], sh);
           const uint32_t r = full_first_win(s, bname, bop, q, x, c, oi);
           const bool queued = r == FULL_SLOW || r == FULL_PASS;
-#if SBH_FULL_HOT
-          uint64_t hm = __ballot(!queued && r == hotw);
-          const uint64_t om = __ballot(!queued && r != hotw);
-          if (__builtin_popcountll(om) > __builtin_popcountll(hm)) {  // uniform: try another hot word
-            const uint32_t cw = __builtin_amdgcn_readlane(r, (uint32_t)__builtin_ctzll(om));
-            const uint64_t cm = __ballot(!queued && r == cw);
-            if (__popc(cw) > 2 && __builtin_popcountll(cm) > __builtin_popcountll(hm)) {
-              hot_flush();
-              hotw = cw;
-              hotn = 0;
-              hm = cm;
-            }
-          }
-          hotn += (uint32_t)__builtin_popcountll(hm);
-#endif
           if (queued) {  // record starts, long CIGARs: the balanced pass below
             const uint32_t qi = atomicAdd(&nslow, 1u);
             if (qi < SLOWCAP) slowq[qi] = q;
             else ovf |= 1u << (16 * step + 4 * b + sh);
             continue;
           }
-#if SBH_FULL_HOT
-          if ((hm >> lane) & 1ull) {
-            if (o.words) o.words[s0 + q - begin] = r;
-            continue;
-          }
-#endif
-#if SBH_FULL_ACCF
           account_fail(s0 + q, r);
-#else
-          account(s0 + q, r);
-#endif
         }
       }
     }
-#if SBH_FULL_RUN
-    run_flush();
-#endif
-#if SBH_FULL_HOT
-    hot_flush();
-#endif
     static_assert(FTILE / (FPL * T) * FPL <= 32, "overflow bits fit a word");
     while (ovf) {
       const uint32_t i = __builtin_ctz(ovf);
@@ -1647,11 +1421,7 @@ __global__ __launch_bounds__(T, SBH_FULL_WGS) void k_full(const uint8_t *__restr
     }
   }
   __syncthreads();
-#ifdef SBH_FULL_NOCHAIN  // A/B probe (timing only, results wrong): queued record starts not walked
-  const uint32_t ns = 0;
-#else
   const uint32_t ns = nslow < SLOWCAP ? nslow : SLOWCAP;
-#endif
   for (uint32_t i = threadIdx.x; i < ns; i += T) {
     const uint64_t p = s0 + slowq[i];
     uint64_t total;
@@ -1668,11 +1438,7 @@ __global__ __launch_bounds__(T, SBH_FULL_WGS) void k_full(const uint8_t *__restr
     uint32_t t = 0;
 #pragma unroll
     for (uint32_t r = 0; r < NREP; ++r)
-#if SBH_FULL_PACKED
-      t += (hist[r * REP + (i / 19) * RW + (i % 19) / 2] >> (16 * ((i % 19) & 1))) & 0xffffu;
-#else
       t += hist[r * REP + i];
-#endif
     if (t) atomicAdd(&o.counts[i], (unsigned long long)t);
   }
   if (threadIdx.x == 0 && nsucc) atomicAdd(o.n_success, (unsigned long long)nsucc);
@@ -1749,7 +1515,7 @@ __global__ __launch_bounds__(256) void k_verify_chain_w(const uint8_t *U, const 
                                                          uint64_t bits_end, uint64_t from, uint64_t E, uint64_t total,
                                                          unsigned long long *n_anom, unsigned long long *first_anom,
                                                          unsigned long long *exit_pos, unsigned long long *n_set,
-                                                         const TileSum *tsum, const unsigned long long *from_dev,
+                                                         const unsigned long long *from_dev,
                                                          uint32_t *chunk_cnt) {
   // chunk_cnt (optional): the set bits of [from, E) per wave chunk of VC_CHUNK words, chunk k =
   // words [VC_CHUNK k, VC_CHUNK (k + 1)) from `begin` (the chunks are aligned to that grid): the
@@ -1761,7 +1527,6 @@ __global__ __launch_bounds__(256) void k_verify_chain_w(const uint8_t *U, const 
     if (from >= E) return;
   }
   const uint32_t lane = threadIdx.x & (WAVE - 1);
-  constexpr uint32_t TWORDS = EAGER_SUB / 32;  // bitmap words per summarised quarter tile (from `begin`)
   const uint64_t W0 = (from - begin) / 32 / VC_CHUNK * VC_CHUNK;  // (chunk-aligned; earlier words are masked)
   const uint64_t w_end = (E - begin + 31) / 32;
   const uint64_t w_lim = (bits_end - begin + 31) / 32;
@@ -1797,24 +1562,10 @@ __global__ __launch_bounds__(256) void k_verify_chain_w(const uint8_t *U, const 
       for (int off = 32; off > 0; off >>= 1) cs += __shfl_xor(cs, off, WAVE);
       if (lane == 0) chunk_cnt[wave_w0 / VC_CHUNK] = cs;
     }
-    // a tile wholly inside [from, E) with a summary: its own pairs were checked by k_eager (their
-    // anomalies added once, by the lane of its first word); only its last true position's step
-    // is needed, from the summary, not from U
-    bool cov = false;
-    uint64_t tstep = TS_NONE, thi = 0;
-    if (SBH_TSUM_CODE && tsum && w < w_end) {
-      const uint64_t tile = w / TWORDS, tlo = begin + tile * EAGER_SUB;
-      thi = tlo + EAGER_SUB;
-      if (tlo >= from && thi <= E) {
-        const TileSum ts = tsum[tile];
-        cov = ts.step_last != TS_DIRTY;
-        tstep = ts.step_last;
-        if (cov && w % TWORDS == 0 && ts.n_anom) {
-          atomicAdd(n_anom, (unsigned long long)ts.n_anom);
-          atomicMin(first_anom, (unsigned long long)(tlo + ts.first_anom));
-        }
-      }
-    }
+    // (measured and removed: per-quarter-tile chain summaries written by k_eager -- the pairs
+    // inside a quarter checked there, its last true position's step read from the summary instead
+    // of U: proof 0.46 -> 0.36 ms but k_eager 3.00 -> 3.24 ms per config-B step, and the branches
+    // alone cost the proof 0.34 -> 0.42 ms with the summaries off (r04q kernel trace))
     // the lane's first set position (successor of the previous non-empty lane's last bit)
     uint64_t f = ~0ull;
     for (int k = 3; k >= 0; --k)
@@ -1855,13 +1606,7 @@ __global__ __launch_bounds__(256) void k_verify_chain_w(const uint8_t *U, const 
       while (kn < 4 && !v[kn]) ++kn;
       const uint64_t nxt_set = kn < 4 ? begin + 32 * (w + kn) + __builtin_ctz(v[kn]) : lane_next;
       uint64_t step;
-      if (cov && nxt_set != ~0ull && nxt_set < thi) {  // a pair inside a summarised tile
-        k = kn;
-        continue;
-      }
-      if (cov) {
-        step = tstep;  // the tile's last true position
-      } else if (s + 4 > total) {
+      if (s + 4 > total) {
         step = ~0ull;  // getInt at EOF: the chain ends here
       } else {
         const uint32_t *g = reinterpret_cast<const uint32_t *>(U + (s & ~3ull));
@@ -2222,13 +1967,13 @@ static inline uint32_t ngrid(uint64_t n, uint32_t t) { return (uint32_t)((n + t 
 hipError_t launch_eager(const uint8_t *U, uint64_t u_pad, uint64_t begin, uint64_t end, const uint64_t *seg_end,
                         uint32_t nseg, uint32_t open_last, const int32_t *ctg, int32_t nctg, int32_t rtc,
                         uint32_t *bits, unsigned long long *counters, hipStream_t st, uint64_t front,
-                        uint64_t *defer_pos, uint64_t defer_cap, uint64_t *xq_pos, uint64_t xq_cap, TileSum *tsum,
+                        uint64_t *defer_pos, uint64_t defer_cap, uint64_t *xq_pos, uint64_t xq_cap,
                         const uint32_t *sieve) {
   if (end <= begin) return hipSuccess;
   Segs sg{seg_end, nseg, open_last};
   Ctg c{ctg, nctg};
   EagerOut o{bits,   counters,     counters + 1, counters + 2, front, defer_pos, counters + 3, defer_cap,
-             xq_pos, counters + 4, xq_cap,       counters + TRUE_SPREAD_OFF, tsum, sieve};
+             xq_pos, counters + 4, xq_cap,       counters + TRUE_SPREAD_OFF, sieve};
   hipLaunchKernelGGL(k_eager, dim3(ngrid(end - begin, ETILE)), dim3(T), 0, st, U, u_pad, begin, end, sg, c,
                      rtc, o);
   hipLaunchKernelGGL(k_fold_true, dim3(1), dim3(WAVE), 0, st, counters + TRUE_SPREAD_OFF, counters);
@@ -2261,9 +2006,6 @@ hipError_t launch_full(const uint8_t *U, uint64_t u_pad, uint64_t begin, uint64_
   // the op index over [begin rounded down to 1 KiB, the last byte a CIGAR of a position
   // before `end` can reach), clipped to the resident bytes and to op_cap_words
   OpIdx oi{nullptr, nullptr, 0, 0, 0};
-#ifdef SBH_FULL_NOOPIX  // A/B: every CIGAR past the staged window takes the exact path
-  op_words = nullptr;
-#endif
   if (op_words) {
     const uint64_t base = begin & ~1023ull;
     uint64_t top = end + 36 + 255 + 4ull * 65535 + 4;
@@ -2306,13 +2048,13 @@ hipError_t launch_first_set(const uint32_t *bits, uint64_t begin, uint64_t from,
 hipError_t launch_verify_chain_count(const uint8_t *U, const uint32_t *bits, uint64_t begin, uint64_t bits_end,
                                      uint64_t from, uint64_t E, uint64_t total, unsigned long long *n_anom,
                                      unsigned long long *first_anom, unsigned long long *exit_pos,
-                                     unsigned long long *n_set, const TileSum *tsum, hipStream_t st,
+                                     unsigned long long *n_set, hipStream_t st,
                                      const unsigned long long *from_dev, uint32_t *chunk_cnt) {
   if (E <= from) return hipSuccess;  // (with from_dev: from is a lower bound of *from_dev)
   const uint64_t nw = (E - begin + 31) / 32 - (from - begin) / 32 / VC_CHUNK * VC_CHUNK;
   const uint32_t grid = (uint32_t)std::min<uint64_t>(ngrid(nw, 1024), 2048);
   hipLaunchKernelGGL(k_verify_chain_w, dim3(grid), dim3(256), 0, st, U, bits, begin, bits_end, from, E, total,
-                     n_anom, first_anom, exit_pos, n_set, tsum, from_dev, chunk_cnt);
+                     n_anom, first_anom, exit_pos, n_set, from_dev, chunk_cnt);
   return hipGetLastError();
 }
 

@@ -109,43 +109,6 @@ struct MemberRec {
 };
 static_assert(sizeof(MemberRec) <= DEFLATE_REC_BYTES, "member record fits its scratch");
 
-#ifdef SBH_DEFLATE_PROBE
-// per-launch phase sums (cycles, thread 0 of each workgroup)
-__device__ unsigned long long dp_acc[3][4];
-__device__ unsigned int dp_done[3];
-#define DP_INIT uint64_t dp_t = __builtin_readcyclecounter()
-#define DP_MARK(kern, k)                                                  \
-  do {                                                                    \
-    if (threadIdx.x == 0) {                                               \
-      const uint64_t nw = __builtin_readcyclecounter();                   \
-      atomicAdd(&dp_acc[kern][k], (unsigned long long)(nw - dp_t));       \
-      dp_t = nw;                                                          \
-    }                                                                     \
-  } while (0)
-#define DP_DONE(kern, what)                                                                       \
-  do {                                                                                            \
-    if (threadIdx.x == 0) {                                                                       \
-      __threadfence();                                                                            \
-      if (atomicAdd(&dp_done[kern], 1u) == gridDim.x - 1) {                                       \
-        unsigned long long x[4];                                                                  \
-        for (int k = 0; k < 4; ++k) x[k] = atomicExch(&dp_acc[kern][k], 0ull);                    \
-        dp_done[kern] = 0;                                                                        \
-        const double m = (double)gridDim.x;                                                       \
-        printf("deflateprobe %s members %u per-member cycles: %.0f %.0f %.0f %.0f\n", what, gridDim.x, \
-               x[0] / m, x[1] / m, x[2] / m, x[3] / m);                                           \
-      }                                                                                           \
-    }                                                                                             \
-  } while (0)
-#else
-#define DP_INIT
-#define DP_MARK(kern, k) \
-  do {                   \
-  } while (0)
-#define DP_DONE(kern, what) \
-  do {                      \
-  } while (0)
-#endif
-
 // (1) k_deflate_parse: the member into LDS, each lane's segment parsed once into tokens (batch
 // scratch) and the member's histogram (LDS atomics), both written to the member record.
 __global__ __launch_bounds__(256) void k_deflate_parse(const uint8_t *__restrict__ src, uint64_t n, uint64_t b0,
@@ -156,7 +119,6 @@ __global__ __launch_bounds__(256) void k_deflate_parse(const uint8_t *__restrict
   const uint32_t t = threadIdx.x;
   const uint64_t b = b0 + blockIdx.x;
   if (b >= nblocks) return;
-  DP_INIT;
   const uint64_t s0 = b * PAYLOAD;
   const uint32_t len = (uint32_t)((n - s0) < PAYLOAD ? (n - s0) : PAYLOAD);
   const uint16_t *pv = prevg + (uint64_t)blockIdx.x * PREV_STRIDE;
@@ -185,7 +147,6 @@ __global__ __launch_bounds__(256) void k_deflate_parse(const uint8_t *__restrict
     for (uint32_t i = t; i < 286 + 30; i += 256) sfl[i] = i == 256 ? 1u : 0u;
   }
   __syncthreads();
-  DP_MARK(0, 0);
   const auto ld = [&](uint32_t i) -> uint64_t {  // 8 bytes from byte i
     const uint32_t a = i >> 2, r = i & 3;
     const uint32_t x0 = ssrc[a], x1 = ssrc[a + 1], x2 = ssrc[a + 2];
@@ -205,12 +166,10 @@ __global__ __launch_bounds__(256) void k_deflate_parse(const uint8_t *__restrict
     });
   R.ntok[t] = ntok;
   __syncthreads();
-  DP_MARK(0, 1);
   for (uint32_t i = t; i < 286 + 30; i += 256) {
     if (i < 286) R.fl[i] = sfl[i];
     else R.fd[i - 286] = sfl[i];
   }
-  DP_DONE(0, "parse (load, parse)");
 }
 
 // (2) k_deflate_codes: the member's dynamic Huffman codes and block header from its histogram,
@@ -228,7 +187,6 @@ __global__ __launch_bounds__(128) void k_deflate_codes(uint8_t *__restrict__ rec
   __shared__ CodesLds S;
   const uint32_t t = threadIdx.x;
   if (blockIdx.x >= nbatch) return;
-  DP_INIT;
   MemberRec &R = *reinterpret_cast<MemberRec *>(recs + (uint64_t)blockIdx.x * DEFLATE_REC_BYTES);
   for (uint32_t i = t; i < 286 + 30; i += 128) {
     if (i < 286) S.fl[i] = R.fl[i];
@@ -243,14 +201,11 @@ __global__ __launch_bounds__(128) void k_deflate_codes(uint8_t *__restrict__ rec
     }
   }
   __syncthreads();
-  DP_MARK(1, 0);
   if (t == 0) huff_tree(S.fl, 286, 15, S.H.ll, S.wl);
   if (t == WAVE) huff_tree(S.fd, 30, 15, S.H.dl, S.wd);
   __syncthreads();
-  DP_MARK(1, 1);
   if (t == 0) S.hbits = build_header(S.H, S.wl, S.cd, S.hdr);
   __syncthreads();
-  DP_MARK(1, 2);
   for (uint32_t i = t; i < 286 + 30; i += 128) {
     if (i < 286) R.cd.lit[i] = S.cd.lit[i];
     else R.cd.dist[i - 286] = S.cd.dist[i - 286];
@@ -258,7 +213,6 @@ __global__ __launch_bounds__(128) void k_deflate_codes(uint8_t *__restrict__ rec
   for (uint32_t i = t; i < HDR_CAP / 4; i += 128)
     reinterpret_cast<uint32_t *>(R.hdr)[i] = reinterpret_cast<const uint32_t *>(S.hdr)[i];
   if (t == 0) R.hbits = S.hbits;
-  DP_DONE(1, "codes (ranks, trees, header)");
 }
 
 // Writes a lane's bit range into the slot as dwords: the first and last dword (shared with
@@ -306,7 +260,6 @@ __global__ __launch_bounds__(256) void k_deflate_emit(const uint8_t *__restrict_
   const uint32_t t = threadIdx.x, w = t / WAVE, lane = t % WAVE;
   const uint64_t b = b0 + blockIdx.x;
   if (b >= nblocks) return;
-  DP_INIT;
   const uint64_t s0 = b * PAYLOAD;
   const uint32_t len = (uint32_t)((n - s0) < PAYLOAD ? (n - s0) : PAYLOAD);
   const uint32_t *tk = toks + (uint64_t)blockIdx.x * TOK_STRIDE + t;
@@ -334,7 +287,6 @@ __global__ __launch_bounds__(256) void k_deflate_emit(const uint8_t *__restrict_
   }
   if (lane == WAVE - 1) wsum[w] = x;
   __syncthreads();
-  DP_MARK(2, 0);
   uint32_t off = x - nbits, total = 0;
   for (uint32_t k = 0; k < 4; ++k) {
     off += k < w ? wsum[k] : 0u;
@@ -367,12 +319,10 @@ __global__ __launch_bounds__(256) void k_deflate_emit(const uint8_t *__restrict_
     for (uint32_t i = t; i < len; i += 256) d0[5 + i] = src[s0 + i];
   }
   __syncthreads();
-  DP_MARK(2, 1);
   if (t == 0) {
     put_header(slot, 18 + dsize + 8);
     sizes[blockIdx.x] = 18 + dsize + 8;
   }
-  DP_DONE(2, "emit (count+scan, emit)");
 }
 
 // Footer: CRC32 (one wave per member, 1 KiB per lane chained with the GF(2) matrix of 1024

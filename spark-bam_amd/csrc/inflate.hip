@@ -32,16 +32,10 @@
 namespace sbh {
 namespace {
 
-#ifndef SBH_LIT_FAST
-#define SBH_LIT_FAST 10
-#endif
 #ifndef SBH_HUFF_WAVES
 #define SBH_HUFF_WAVES 4
 #endif
-constexpr int LIT_FAST = SBH_LIT_FAST;
-#ifndef SBH_HUFF_PAIRS
-#define SBH_HUFF_PAIRS 1  // literal-pair table entries and two-byte literal tokens (see PE_PAIR)
-#endif
+constexpr int LIT_FAST = 10;  // (slow_lane and the asm loops index 10-bit tables)
 constexpr int DIST_FAST = 8;
 constexpr int CL_FAST = 7;
 constexpr int PDIST_FAST = 10;  // PAR-format distance table: one dword per entry, as wide as the literal one
@@ -86,7 +80,7 @@ constexpr uint32_t PE_LEN = 1u << 12;      // a length code: a distance code fol
 constexpr uint32_t PE_EOB = 1u << 13;      // (with PE_SPECIAL) end of block
 constexpr uint32_t PE_SLOW = 1u << 14;     // (with PE_SPECIAL) code longer than the table: slow_lane
 constexpr uint32_t PE_SPECIAL = 1u << 31;  // not a token: end of block, invalid, or long code
-// (SBH_HUFF_PAIRS) a literal entry that decodes two literal codes at once (their lengths summed in
+// Literal pairs: a literal entry that decodes two literal codes at once (their lengths summed in
 // [4:0]; the first byte at [23:16], the second's low 7 bits at [30:24] and its bit 7 at PE_L2B7):
 // one token of two bytes, (byte1 << 8) | (byte2 << 16) | TOK_PAIR
 constexpr uint32_t PE_L2B7 = 1u << 9;
@@ -338,14 +332,14 @@ __device__ __forceinline__ uint32_t ptable_entry(const SM &sm, const uint32_t *l
   return sm.sent[(kind ? 288 : 0) + (((sm.pk[kind][len] & 0xffffu) + (c15 >> (15 - len))) & 0xffffu)];
 }
 
-// Entry i of the literal/length table (PAR format), paired (SBH_HUFF_PAIRS): a literal code of
+// Entry i of the literal/length table (PAR format), paired: a literal code of
 // L1 < LIT_FAST bits whose next LIT_FAST - L1 bits hold a whole literal code gives both at once.
 // (The entry of i >> L1 is that second code's whatever the bits past the window: codes are
 // prefix-free, and a code of at most LIT_FAST - L1 bits lies inside it.)
 template <class SM>
 __device__ __forceinline__ uint32_t ptable_lit_entry(const SM &sm, const uint32_t *lj, uint32_t i) {
   const uint32_t e1 = ptable_entry(sm, lj, 0, LIT_FAST, i);
-  if (!SBH_HUFF_PAIRS || (int32_t)e1 < 0 || (e1 & PE_LEN) || (e1 & 31) >= (uint32_t)LIT_FAST) return e1;
+  if ((int32_t)e1 < 0 || (e1 & PE_LEN) || (e1 & 31) >= (uint32_t)LIT_FAST) return e1;
   const uint32_t L1 = e1 & 31;
   const uint32_t e2 = ptable_entry(sm, lj, 0, LIT_FAST, i >> L1);
   if ((int32_t)e2 < 0 || (e2 & PE_LEN) || L1 + (e2 & 31) > (uint32_t)LIT_FAST) return e1;
@@ -887,9 +881,9 @@ __device__ __forceinline__ void inflate_serial(const uint8_t *__restrict__ comp,
   }
 }
 
-// Serial decoder kernel: one wave per block.  As the A/B baseline it decodes every block
-// (SBH_HUFF_SERIAL); behind the lane-parallel k_huff it decodes only the blocks k_huff
-// marked INF_SERIAL.
+// Serial decoder kernel: one wave per block.  Behind the lane-parallel k_huff it decodes only
+// the blocks k_huff marked INF_SERIAL (ONLY_MARKED; false decoded every block, the A/B baseline
+// of the lane-parallel stage: that launch is removed).
 template <bool ONLY_MARKED>
 __global__ __launch_bounds__(WAVES *WAVE) void k_huff_serial(const uint8_t *__restrict__ comp, DevBlocks bl,
                                                               uint64_t nblocks, uint32_t *__restrict__ tok) {
@@ -980,22 +974,10 @@ constexpr uint32_t HDR_OK = 0x48445231u;
 constexpr uint32_t HDR_STAGE_DW = 160;  // deflate dwords k_hdr stages (a header is < 2.5 kbit)
 static_assert(HDR_OUT_DW < PAR_MIN_USIZE, "the header record fits the token region of every parallel block");
 static_assert(HDR_SENT % SBH_HT == 0, "k_huff copies the tables in whole rounds");
-#ifndef SBH_CK1  // (A/B at 4 M records: 4/16, 6/24, 8/32, 10/40 within 2%)
-#define SBH_CK1 8
-#define SBH_CK2 32
-#endif
-#ifndef SBH_CK3
-#define SBH_CK3 64
-#endif
-#ifndef SBH_MARGIN
-#define SBH_MARGIN 0  // pass-1 warm-up bits before each slice (A/B: 128-384 bits measured neutral)
-#endif
-constexpr uint32_t CK1 = SBH_CK1, CK2 = SBH_CK2;  // pass-1 checkpoints (tokens)
-constexpr uint32_t CK3 = SBH_CK3;                 // a third, for chains that sync late (0: none)
+// pass-1 checkpoints (tokens), and a third for chains that sync late; the asm pass-1 loop
+// hard-codes this schedule (A/B at 4 M records: 4/16, 6/24, 8/32, 10/40 within 2%)
+constexpr uint32_t CK1 = 8, CK2 = 32, CK3 = 64;
 constexpr uint32_t LR_RUN = 0, LR_EOB = 1, LR_DEAD = 2, LR_PAST = 3;
-#ifndef SBH_TAIL
-#define SBH_TAIL 1  // short final deflate blocks left to k_huff_tail (0: k_huff decodes them)
-#endif
 constexpr uint32_t INF_TAIL = 0xfeu;  // (inside inflate only) k_huff_tail finishes the block
 #ifdef SBH_HUFF_PROBE
 // whole-kernel phase sums (cycles): 0 stage, 1 header, 2 pass 1, 3 repair, 4 emit, 5 repair
@@ -1142,7 +1124,7 @@ __device__ __forceinline__ LaneRun lane_run(const WaveSmem &t, S src, uint32_t A
       c2o = c1o;
       c1p = pos;
       c1o = ntok + (acc >> 12);
-      ck_next = ck_next == CK1 ? CK2 : ck_next == CK2 && CK3 > CK2 ? CK3 : ~0u;
+      ck_next = ck_next == CK1 ? CK2 : ck_next == CK2 ? CK3 : ~0u;
     }
     cut = atb && (pos >= stop2 || (MODE == RUN_REDO && (pos == ck.p1 || pos == ck.p2 || pos == ck.p3)));
     if (cut || special) break;
@@ -1170,7 +1152,7 @@ __device__ __forceinline__ LaneRun lane_run(const WaveSmem &t, S src, uint32_t A
     tsel = tnew;
   }
   if (MODE == RUN_SPEC) {  // oldest first: CK1's boundary in p1
-    const uint32_t nck = ck_next == CK1 ? 0u : ck_next == CK2 ? 1u : ck_next == CK3 && CK3 > CK2 ? 2u : CK3 > CK2 ? 3u : 2u;
+    const uint32_t nck = ck_next == CK1 ? 0u : ck_next == CK2 ? 1u : ck_next == CK3 ? 2u : 3u;
     ck = nck == 3 ? Ckpt{c3p, c3o, c2p, c2o, c1p, c1o}
        : nck == 2 ? Ckpt{c2p, c2o, c1p, c1o, NOPOS, 0}
        : nck == 1 ? Ckpt{c1p, c1o, NOPOS, 0, NOPOS, 0}
@@ -1338,10 +1320,8 @@ __device__ __forceinline__ LaneRun spec_asm(const WaveSmem &t, const uint32_t *s
       "v_addc_co_u32_e64 %[ntok], vcc, 0, %[ntok], %[sA]\n\t"
       "v_add_u32 %[tselb], %[tabb], %[vt]\n\t"
       "v_mad_u32_u24 %[acc], %[vt], %[val], %[acc]\n\t"
-#if SBH_HUFF_PAIRS
       "v_and_b32 %[tmp], 0x400, %[e]\n\t"  // a literal pair (PE_PAIR): one byte more than its token
       "v_lshl_add_u32 %[acc], %[tmp], 2, %[acc]\n\t"
-#endif
       "s_branch L_top%=\n"
       "L_end%=:\n\t"
       "s_waitcnt lgkmcnt(0)\n\t"
@@ -1492,10 +1472,8 @@ __device__ __forceinline__ LaneRun redo_asm(const WaveSmem &t, const uint32_t *s
       "v_addc_co_u32_e64 %[ntok], vcc, 0, %[ntok], %[sA]\n\t"
       "v_add_u32 %[tselb], %[tabb], %[vt]\n\t"
       "v_mad_u32_u24 %[acc], %[vt], %[val], %[acc]\n\t"
-#if SBH_HUFF_PAIRS
       "v_and_b32 %[tmp], 0x400, %[e]\n\t"  // a literal pair (PE_PAIR): one byte more than its token
       "v_lshl_add_u32 %[acc], %[tmp], 2, %[acc]\n\t"
-#endif
       "s_branch L_top%=\n"
       "L_end%=:\n\t"
       "s_waitcnt lgkmcnt(0)\n\t"
@@ -1531,16 +1509,15 @@ __device__ __forceinline__ LaneRun redo_asm(const WaveSmem &t, const uint32_t *s
 #ifndef SBH_ASM_EMIT
 #define SBH_ASM_EMIT 1  // pass 3 (RUN_EMIT over the LDS stage) as the hand-written loop below
 #endif
-#ifndef SBH_EMIT_NOCHK
-#define SBH_EMIT_NOCHK 1  // emit_asm: no too-far-back test per distance code (k_lz tests each match token once)
-#endif
-#ifndef SBH_EMIT_X4
-#define SBH_EMIT_X4 1  // emit_asm: a lane's tokens stored four at a time (16-byte stores from v124..v127; A/B r05m/r05n: k_huff -7% E, +-0.2% B and D)
-#endif
 // RUN_EMIT over the LDS stage as hand-written code (lane_run<RUN_EMIT>'s results): the decode
 // loop of spec_asm without the checkpoints, each token stored once (a literal at its code, a
 // match at its distance code) through a 32-bit offset from the block's token base `tk` (wave-
-// uniform), and the too-far-back test of every distance accumulated as a lane mask.
+// uniform).  A lane's tokens leave four at a time (16-byte stores from v124..v127; A/B r05m/r05n
+// against one 4-byte store per token: k_huff -7% E, +-0.2% B and D).  No too-far-back test per
+// distance code: k_lz tests each match token once, so `bad` comes back unchanged and the token /
+// byte counts that fed the test are not kept (the operands stay: the register assignment is
+// part of the measured loop).
+// (removed: the per-distance test here; measured and removed: the single-token stores.)
 __device__ __forceinline__ void emit_asm(const WaveSmem &t, const uint32_t *stage, uint32_t A, uint32_t stop,
                                          uint32_t limit, uint32_t *tk, uint32_t tidx, uint32_t out0, uint32_t &bad) {
   const uint32_t stop2 = stop < limit ? stop : limit;
@@ -1649,31 +1626,13 @@ __device__ __forceinline__ void emit_asm(const WaveSmem &t, const uint32_t *stag
       "v_mov_b32 %[pos], %[np]\n\t"
       // the token: a literal (byte << 8) or the match completed by this distance code
       "v_lshlrev_b32 %[vtok], 8, %[val]\n\t"
-#if SBH_HUFF_PAIRS
       "v_and_b32 %[tmp], 0x600, %[e]\n\t"  // (a literal pair: byte2's bit 7 and TOK_PAIR)
       "v_lshl_or_b32 %[vtok], %[tmp], 14, %[vtok]\n\t"
-#endif
-#if SBH_EMIT_NOCHK
       // (ml: the match token's upper half, TOK_MATCH | length << 16, set by every code -- only a
       // length code's is ever read, by the distance code after it)
       "v_or_b32 %[np], %[ml], %[val]\n\t"
       "v_lshl_add_u32 %[ml], %[val], 16, %[mlk]\n\t"
-#else
-      "v_add_u32 %[tmp], 1, %[ml]\n\t"
-      "v_lshl_or_b32 %[np], %[tmp], 16, %[val]\n\t"
-      "v_or_b32 %[np], 0x80000000, %[np]\n\t"
-#endif
       "v_cndmask_b32_e64 %[vtok], %[np], %[vtok], %[sA]\n\t"
-#if !SBH_EMIT_NOCHK
-      // too far back: a distance past the bytes before its match
-      "v_lshrrev_b32 %[vb], 12, %[acc]\n\t"
-      "v_sub_u32 %[vb], %[vb], %[ml]\n\t"
-      "v_add3_u32 %[vb], %[vb], %[ntok], %[om1]\n\t"
-      "v_cmp_gt_u32 %[sB], %[val], %[vb]\n\t"
-      "s_andn2_b64 %[sB], %[sB], %[sA]\n\t"
-      "s_or_b64 %[sBad], %[sBad], %[sB]\n\t"
-      "v_cndmask_b32_e64 %[ml], %[ml], %[val], %[sL]\n\t"
-#endif
       "s_waitcnt lgkmcnt(0)\n\t"
       "v_cndmask_b32_e32 %[lo], %[lo], %[hi], vcc\n\t"
       "v_cndmask_b32_e32 %[hi], %[hi], %[nx], vcc\n\t"
@@ -1681,7 +1640,6 @@ __device__ __forceinline__ void emit_asm(const WaveSmem &t, const uint32_t *stag
       "s_and_b64 %[sE], %[sA], %[sL]\n\t"
       "s_mov_b64 %[sB], exec\n\t"
       "s_andn2_b64 exec, exec, %[sE]\n\t"
-#if SBH_EMIT_X4
       // tokens gather in v124..v127 (oldest first) and leave four at a time in one 16-byte store
       "v_mov_b32 v124, v125\n\t"
       "v_mov_b32 v125, v126\n\t"
@@ -1696,25 +1654,12 @@ __device__ __forceinline__ void emit_asm(const WaveSmem &t, const uint32_t *stag
       "v_add_u32 %[voff], 16, %[voff]\n\t"
       "v_mov_b32 %[cnt], 0\n"
       "L_nofl%=:\n\t"
-#else
-      "global_store_dword %[voff], %[vtok], %[tkb]\n\t"
-      "v_add_u32 %[voff], 4, %[voff]\n\t"
-#endif
       "s_mov_b64 exec, %[sB]\n\t"
-#if !SBH_EMIT_NOCHK  // (the token and byte counts feed the distance test only)
-      "v_addc_co_u32_e64 %[ntok], vcc, 0, %[ntok], %[sA]\n\t"
-      "v_mad_u32_u24 %[acc], %[vt], %[val], %[acc]\n\t"
-#if SBH_HUFF_PAIRS
-      "v_and_b32 %[tmp], 0x400, %[e]\n\t"
-      "v_lshl_add_u32 %[acc], %[tmp], 2, %[acc]\n\t"
-#endif
-#endif
       "v_add_u32 %[tselb], %[tabb], %[vt]\n\t"
       "s_branch L_top%=\n"
       "L_end%=:\n\t"
       "s_waitcnt lgkmcnt(0)\n\t"
       "s_mov_b64 exec, %[sv]\n\t"
-#if SBH_EMIT_X4
       // the last cnt (< 4) tokens of each lane: v127 (newest) at voff + 4 (cnt - 1), v126 before it, ...
       "v_cmp_le_u32 %[sE], 1, %[cnt]\n\t"
       "s_and_b64 exec, exec, %[sE]\n\t"
@@ -1729,7 +1674,6 @@ __device__ __forceinline__ void emit_asm(const WaveSmem &t, const uint32_t *stag
       "global_store_dword %[tmp], v125, %[tkb] offset:-12\n"
       "L_fld%=:\n\t"
       "s_mov_b64 exec, %[sv]\n\t"
-#endif
       "v_cndmask_b32_e64 %[badv], 0, 1, %[sBad]"
       : [pos] "+v"(pos), [lo] "+v"(lo), [hi] "+v"(hi), [vt] "+v"(vt), [tselb] "+v"(tselb), [ntok] "+v"(ntok),
         [acc] "+v"(acc), [ml] "+v"(ml), [voff] "+v"(voff), [badv] "+v"(badv), [cnt] "+v"(cnt), [e] "+v"(e),
@@ -1742,9 +1686,7 @@ __device__ __forceinline__ void emit_asm(const WaveSmem &t, const uint32_t *stag
       : [stop] "v"(stop2), [tabb] "s"(tabb), [stb] "s"(stb), [pkb] "s"(pkb), [sentb] "s"(sentb),
         [sentd] "s"(sentd), [bad_e] "v"(bad_e), [om1] "v"(om1), [tkb] "s"(tkb), [mlk] "s"(0x80010000u)
       : "vcc", "scc", "memory"
-#if SBH_EMIT_X4
       , "v124", "v125", "v126", "v127"
-#endif
   );
   bad |= badv;
 }
@@ -1979,18 +1921,8 @@ __device__ __forceinline__ uint32_t inflate_par(SM &sm, const uint8_t *__restric
     uint32_t A = s, nobad = 0;
     Ckpt ck;
     const LaneRun none{};
-#if SBH_MARGIN
-    // warm-up: decode from SBH_MARGIN bits before the slice, so that by the slice start the
-    // chain has (very likely) fallen onto the true token boundaries; the speculative start is
-    // then the first boundary at or past the slice start -- usually exactly where the left
-    // neighbour's chain exits, so the first repair round has nothing to redo for that lane
-    if (tid) {
-      Ckpt nock{NOPOS, 0, NOPOS, 0, NOPOS, 0};
-      const uint32_t w0 = s - p0 > SBH_MARGIN ? s - SBH_MARGIN : p0;
-      const LaneRun rw = lane_run<RUN_REDO>(sm.t, src, w0, s, limit, nock, none, nullptr, 0, nobad);
-      if (rw.st == LR_RUN && rw.exit < stop) A = rw.exit;
-    }
-#endif
+    // (measured and removed: a warm-up decode from 128-384 bits before the slice, so that the
+    // speculative start is already a true token boundary -- A/B: neutral)
 #if SBH_ASM_SPEC
     LaneRun r = LDS ? spec_asm(sm.t, sm.stage, A, stop, limit, ck)
                     : lane_run<RUN_SPEC>(sm.t, src, A, stop, limit, ck, none, nullptr, 0, nobad);
@@ -2010,9 +1942,6 @@ __device__ __forceinline__ uint32_t inflate_par(SM &sm, const uint8_t *__restric
     uint32_t nrounds = 0;
     __syncthreads();
     const uint64_t tp1 = __builtin_readcyclecounter();
-#endif
-#if defined(SBH_HUFF_TIMING) && (SBH_HUFF_TIMING & 1)
-    if (false)  // timing probe: no repair rounds
 #endif
     for (;;) {
 #ifdef SBH_HUFF_PROBE
@@ -2105,17 +2034,6 @@ __device__ __forceinline__ uint32_t inflate_par(SM &sm, const uint8_t *__restric
       atomicAdd(&hp_acc[11], (unsigned long long)ttot);
     }
 #endif
-#ifdef SBH_HUFF_TIMING  // A/B phase-cost probe (timing only, results wrong): the first deflate block's
-                        // passes, none of the checks; bit 0: no repair rounds, bit 1: no emit pass
-    {
-      uint32_t bad = 0;
-      if ((SBH_HUFF_TIMING & 2) == 0)
-        lane_run<RUN_EMIT>(sm.t, src, A, stop, limit, ck, none, tk + ((tid * 16) & 2047), opre, bad);  // (in bounds)
-      __syncthreads();
-      ntok_out = 0;
-      return PAR_OK;
-    }
-#endif
     if (k >= NT || eob_end == NOPOS || otot > usize - out) return PAR_FAIL;
     // pass 3: emit
     uint32_t bad = 0;
@@ -2134,10 +2052,6 @@ __device__ __forceinline__ uint32_t inflate_par(SM &sm, const uint8_t *__restric
     ntok += ttot;
     out += otot;
     p = eob_end;
-#ifdef SBH_HUFF_FIRST_ONLY  // A/B probe (timing only, results wrong): the first deflate block alone
-    ntok_out = ntok;
-    return PAR_OK;
-#endif
     if (last) break;
     // (the tail's two words go where its tokens will start: ntok + 2 <= usize keeps them
     // inside the block's token region)
@@ -2194,14 +2108,12 @@ __device__ __forceinline__ bool huff_serial_block(const DevBlocks &bl, uint64_t 
 #define SBH_HDR_WAVES 4
 #endif
 constexpr uint32_t HDR_WAVES = SBH_HDR_WAVES;  // blocks (one per wave) per k_hdr workgroup
-#ifndef SBH_TAIL_HDR
-#define SBH_TAIL_HDR 1  // the tails' headers decoded and tabled by k_hdr<true> between k_huff and k_huff_tail
-#endif
 
 // A tail's header record fits between its two leading words (tok[G + n1 ..]) and the end of the
 // block's token region; k_huff_tail reads it there, before any tail token is written over it.
+// (The tails' headers are decoded and tabled by k_hdr<true> between k_huff and k_huff_tail.)
 __device__ __forceinline__ bool tail_hdr_room(uint32_t n1, uint32_t usize) {
-  return SBH_TAIL_HDR && n1 <= usize && usize - n1 >= HDR_OUT_DW + 2;
+  return n1 <= usize && usize - n1 >= HDR_OUT_DW + 2;
 }
 
 // TAIL: the header of a tail k_huff left (INF_TAIL), at the bit its two leading words give --
@@ -2395,7 +2307,7 @@ __global__ __launch_bounds__(HT, SBH_HUFF_OCC) void k_huff(const uint8_t *__rest
       if (tid == 0) atomicAdd(&hp_acc[0], __builtin_readcyclecounter() - hk0);
 #endif
       rc = inflate_par<true>(sm, dbase, skip, limit, usize, tok + G, tid, lane, wid, ntok, pre, pre_psym, pre_last, 0,
-                             SBH_TAIL != 0, &tail_p, &tail_out);
+                             true, &tail_p, &tail_out);  // (tail_ok: short final deflate blocks go to k_huff_tail)
     } else {
       take_record();
       if (pre) {
@@ -2403,7 +2315,7 @@ __global__ __launch_bounds__(HT, SBH_HUFF_OCC) void k_huff(const uint8_t *__rest
         __syncthreads();
       }
       rc = inflate_par<false>(sm, dbase, skip, limit, usize, tok + G, tid, lane, wid, ntok, pre, pre_psym, pre_last,
-                              0, SBH_TAIL != 0, &tail_p, &tail_out);
+                              0, true, &tail_p, &tail_out);
     }
     if (uni(rc) == PAR_TAIL) {  // k_huff_tail decodes the rest: its start bit and bytes so far at tok[ntok..]
       if (tid == 0) {
@@ -2526,32 +2438,28 @@ __global__ __launch_bounds__(TAIL_NT) void k_huff_tail(const uint8_t *__restrict
 constexpr uint32_t LZ_TPT = SBH_LZ_TPT;                       // tokens per thread per chunk
 constexpr uint32_t LZ_CHUNK = LZ_THREADS * LZ_TPT;      // tokens per chunk
 constexpr uint32_t PTR_HALF = 8;                        // pointer slots per thread and pass
-#ifndef SBH_LZ_RING
-// k_lz's block image as a ring of 32 KiB of history + one pass, flushed to U pass by pass, so that
-// three workgroups fit a CU (6656-byte passes, 80 VGPRs: 6 waves per SIMD) instead of two with the
-// whole 64 KiB image (A/B r05y, output identical: k_lz -13% B, -15% D, -11% E)
-#define SBH_LZ_RING 1
-#endif
 #ifndef SBH_LZ_PTR_CAP
-#define SBH_LZ_PTR_CAP (SBH_LZ_RING ? 6656 : 7552)
+#define SBH_LZ_PTR_CAP 6656
 #endif
 constexpr uint32_t PTR_CAP = SBH_LZ_PTR_CAP;            // bytes one pointer-chasing pass resolves
 constexpr uint32_t SB_WORDS = PTR_CAP / 32;             // token-start bitmap words
 constexpr uint32_t NHP = 2;                             // half granules (8 slots) per k_lz thread, at most
 static_assert(PTR_CAP <= NHP * LZ_THREADS * PTR_HALF, "slot pass covers the slots");
 
-// image bytes: the whole block, or (ring) the deflate window before a pass plus the pass itself
-// (a pass's pointers reach at most 32768 bytes before its first byte), a multiple of 16 so
-// granules stay whole; image position q lives at q mod LZ_IMG (q < 2 LZ_IMG always)
-constexpr uint32_t LZ_IMG = SBH_LZ_RING ? (32768u + PTR_CAP + 16u + 15u) / 16u * 16u : 65536u + 16u;
-static_assert(!SBH_LZ_RING || 65536u + 16u < 2 * LZ_IMG, "one subtraction maps an image position into the ring");
+// k_lz's block image is a ring: the deflate window before a pass plus the pass itself (a pass's
+// pointers reach at most 32768 bytes before its first byte), flushed to U pass by pass, a multiple
+// of 16 so granules stay whole; image position q lives at q mod LZ_IMG (q < 2 LZ_IMG always).
+// Three workgroups fit a CU (6656-byte passes, 80 VGPRs: 6 waves per SIMD).
+// (measured and removed: the whole 64 KiB block image in LDS, 7552-byte passes, two workgroups
+// per CU -- A/B r05y, output identical: the ring's k_lz -13% B, -15% D, -11% E.)
+constexpr uint32_t LZ_IMG = (32768u + PTR_CAP + 16u + 15u) / 16u * 16u;
+static_assert(65536u + 16u < 2 * LZ_IMG, "one subtraction maps an image position into the ring");
 __device__ __forceinline__ uint32_t lz_ri(uint32_t q) {
-  if (!SBH_LZ_RING) return q;
   const uint32_t r = q - LZ_IMG;
   return r < q ? r : q;  // (q < LZ_IMG: r wraps above q)
 }
 struct LzSmem {
-  uint8_t img[LZ_IMG];  // block image (or its ring), placed at (ustart & 15) so granules align with HBM
+  uint8_t img[LZ_IMG];  // the block image's ring, placed at (ustart & 15) so granules align with HBM
   struct {
     uint16_t p16[PTR_CAP];     // per pass byte: its source pointer (token starts first)
     uint32_t sbits[SB_WORDS];  // per pass byte: starts a token (every byte of a long match)
@@ -2559,9 +2467,8 @@ struct LzSmem {
     uint32_t wmin[LZ_THREADS / WAVE];  // block_min scratch (a pass cut)
   } pp;
 };
-// two workgroups per CU (three with the ring), counting the 256 B of LDS the compiler adds
-static_assert(sizeof(LzSmem) * 2 + 512 <= 160 * 1024, "two k_lz workgroups per CU");
-static_assert(!SBH_LZ_RING || sizeof(LzSmem) * 3 + 768 <= 160 * 1024, "three k_lz workgroups per CU with the ring");
+// three workgroups per CU, counting the 256 B of LDS the compiler adds
+static_assert(sizeof(LzSmem) * 3 + 768 <= 160 * 1024, "three k_lz workgroups per CU");
 
 // k mod d for k < 2^17, d >= 1 (one reciprocal, one correction).
 __device__ __forceinline__ uint32_t mod_small(uint32_t k, uint32_t d) {
@@ -2577,44 +2484,14 @@ __device__ __forceinline__ uint4 pack8_u16(const uint32_t *c) {
                     __builtin_amdgcn_perm(c[5], c[4], 0x05040100u), __builtin_amdgcn_perm(c[7], c[6], 0x05040100u));
 }
 
-#ifndef SBH_LZ_NO_END_BAR
-#define SBH_LZ_NO_END_BAR 1  // k_lz: no barrier at a chunk's end (the next chunk's scan barrier orders it; A/B: k_lz -3% B, -2% D, -3% E)
-#endif
 #ifndef SBH_ASM_CHASE
 #define SBH_ASM_CHASE 1  // k_lz's pointer chase as the hand-written loop below
-#endif
-#ifndef SBH_LZ_SLOT128
-#define SBH_LZ_SLOT128 1  // k_lz slot pass: a thread's 8 start values from one 16-byte read of its own slots
-#endif
-#ifndef SBH_LZ_SBMASK
-#define SBH_LZ_SBMASK 0  // 1: k_lz marks OR a thread's start bits per word (A/B r04e: +0.5..3% k_lz: kept off)
 #endif
 #ifndef SBH_LZ_LMARK_MIN
 #define SBH_LZ_LMARK_MIN 1  // k_lz: long matches per wave and token slot from which their threads mark them (A/B r04f: 1 best; 99 = wave-serial only: D +11%)
 #endif
 constexpr uint32_t LZ_LMARK_MIN = SBH_LZ_LMARK_MIN;
-#ifndef SBH_LZ_OVL_WAVE
-#define SBH_LZ_OVL_WAVE 0  // 1: overlapping short matches (dist < len) marked byte by byte by the wave (A/B r04c: k_lz +5% B, +26% D, +10% E: kept off)
-#endif
-#ifndef SBH_LZ_CARRY
-#define SBH_LZ_CARRY 1  // k_lz: a chunk that overflows its pass ends at the cut; the next chunk starts there
-#endif
-#ifndef SBH_LZ_NOCLAMP
-#define SBH_LZ_NOCLAMP 1  // the chase reads settled pointers' slots unclamped: one VALU + one SALU fewer per pointer (A/B r04v: k_lz -2.7% B, -2.8% D, -3.4% E)
-#endif
-#ifndef SBH_LZ_NOHOIST
-#define SBH_LZ_NOHOIST 1  // keep the long-match marker mod inside its branch (see k_lz)
-#endif
-#ifndef SBH_LZ_RUN1
-#define SBH_LZ_RUN1 1  // distance-1 matches point every byte at the source byte (no mod branch)
-#endif
 
-#ifndef SBH_LZ_MOD2
-#define SBH_LZ_MOD2 1  // (with RUN1) overlaps at distance >= 2 chased instead of taking the mod
-#endif
-#ifndef SBH_LZ_MOD
-#define SBH_LZ_MOD 1  // 1: a byte of an overlapping short match points at v + (j mod distance) (0: at v + j, a longer chase: A/B r04p k_lz +4% B, +2% D)
-#endif
 // (r04n-r04p, measured and removed -- profiles/r04_ab/: each lane's 8 pointers rotated by
 // 2 ((h >> 3) & 3) slots so the chase's u16 reads of lanes h, h + 8, h + 16, h + 24 (16 bytes
 // apart, one bank) hit four distinct dwords: k_lz +5% B, +4% D, +2.5% E; a thread's two half
@@ -2637,13 +2514,14 @@ constexpr uint32_t LZ_LMARK_MIN = SBH_LZ_LMARK_MIN;
 // value (u16 LDS reads at 2 c + p16 - 2 * abase, all 8 issued before the first is
 // waited for), the 8 slots written back as 16 bytes at w0, until no pointer of the lane moved to
 // another in-pass position.  4 vector + 2 scalar instructions per pointer and round besides
-// the read (SBH_LZ_NOCLAMP; the compiler's version: ~9 and ~3, plus a register rotation of the
+// the read (the compiler's version: ~9 and ~3, plus a register rotation of the
 // 8 pointers every round); a read's address register takes its result (8 VGPRs fewer: k_lz -1% B).
-#if SBH_LZ_NOCLAMP
 // (no clamp to the pass start: a settled pointer c < pb reads whatever LDS word 2 c + off names
 // -- the image below the slots, or nothing (an out-of-range LDS read returns 0) -- and the
 // value is dropped: c moves only when pb <= c.  A pointer moves on in the pass when
 // pb <= r < c: slot values never exceed their slot, so r != c is r < c)
+// (measured and removed: the read address clamped to the pass start, one VALU + one SALU more
+// per pointer -- A/B r04v: unclamped k_lz -2.7% B, -2.8% D, -3.4% E.)
 #define SBH_CH_ADDR(k) "v_lshl_add_u32 %[a" #k "], %[c" #k "], 1, %[off]\n\t" \
                        "ds_read_u16 %[a" #k "], %[a" #k "]\n\t"
 #define SBH_CH_STEP(k, w) "s_waitcnt lgkmcnt(" #w ")\n\t" \
@@ -2653,19 +2531,6 @@ constexpr uint32_t LZ_LMARK_MIN = SBH_LZ_LMARK_MIN;
                           "s_and_b64 %[sx], %[sx], %[sy]\n\t" \
                           "s_or_b64 %[sc], %[sc], %[sx]\n\t" \
                           "v_cndmask_b32_e32 %[c" #k "], %[c" #k "], %[a" #k "], vcc\n\t"
-#else
-#define SBH_CH_ADDR(k) "v_max_u32 %[a" #k "], %[pb], %[c" #k "]\n\t" \
-                       "v_lshl_add_u32 %[a" #k "], %[a" #k "], 1, %[off]\n\t" \
-                       "ds_read_u16 %[a" #k "], %[a" #k "]\n\t"
-#define SBH_CH_STEP(k, w) "s_waitcnt lgkmcnt(" #w ")\n\t" \
-                          "v_cmp_le_u32 vcc, %[pb], %[c" #k "]\n\t" \
-                          "v_cmp_ne_u32 %[sx], %[a" #k "], %[c" #k "]\n\t" \
-                          "v_cmp_le_u32 %[sy], %[pb], %[a" #k "]\n\t" \
-                          "s_and_b64 %[sx], %[sx], vcc\n\t" \
-                          "s_and_b64 %[sx], %[sx], %[sy]\n\t" \
-                          "s_or_b64 %[sc], %[sc], %[sx]\n\t" \
-                          "v_cndmask_b32_e32 %[c" #k "], %[c" #k "], %[a" #k "], vcc\n\t"
-#endif
 #define SBH_CH_WB(w, k0, k1, k2, k3, k4, k5, k6, k7) \
   "v_perm_b32 %[a" #k0 "], %[c" #k1 "], %[c" #k0 "], %[sel]\n\t" \
   "v_perm_b32 %[a" #k1 "], %[c" #k3 "], %[c" #k2 "], %[sel]\n\t" \
@@ -2714,37 +2579,18 @@ __device__ __forceinline__ void chase8_asm(uint32_t (&c)[8], uint32_t pend, uint
 // copies from (itself for a literal; match byte k: off - dist + k mod dist, always
 // earlier), written by its own token; then each thread follows its 16 bytes' pointers to
 // final bytes -- rewriting its slots with the results, which shortens other threads'
-// chases -- and gathers.  A longer chunk (long matches) is resolved the same way in
-// passes of at most PTR_CAP bytes, each cut at a token start, so every chunk takes the
+// chases -- and gathers.  A longer chunk (long matches) is cut at a token start after at
+// most PTR_CAP bytes and the next chunk starts at the cut, so every chunk takes the
 // pointer path (the dependency-rounds fallback this replaced cost ~100 k cycles per
 // overflowing chunk: 2-4 per block of long-read data).
 #ifndef SBH_LZ_WAVES_PER_EU
-#define SBH_LZ_WAVES_PER_EU (SBH_LZ_RING ? 6 : 4)  // (the register budget: 512 VGPRs / waves per SIMD)
+#define SBH_LZ_WAVES_PER_EU 6  // (the register budget: 512 VGPRs / waves per SIMD)
 #endif
-#ifndef SBH_LZ_SIEVE
-// 1: k_lz leaves k_eager's first filter as a bitmap (launch_lz's sieve; run with SBH_SIEVE=1).
-// Measured and not kept: k_eager -0.55 ms, k_lz +0.95 ms on config B -- the
-// filter's ~180 vector instructions per 16-byte granule are issue time k_lz does not have spare
-#define SBH_LZ_SIEVE 0
-#endif
-// k_eager's first filter at the 16 positions of a granule: eager.Checker reads refID, pos, next
-// refID and next pos first (PosChecker.getRefPosError, check/.../PosChecker.scala:43-63; the
-// refID / next refID in [-1, n) and pos / next pos >= -1 parts need no contig length), so a
-// position failing one of them is false; d[] = the 48 bytes from the granule's first.
-__device__ __forceinline__ uint32_t sieve16(const uint32_t (&d)[12], uint32_t nref1) {
-  uint32_t m = 0;
-#pragma unroll
-  for (uint32_t j = 0; j < 16; ++j) {
-    const uint32_t q = j >> 2, k = j & 3;
-    const uint32_t ref = __builtin_amdgcn_alignbyte(d[q + 2], d[q + 1], k);
-    const uint32_t pos = __builtin_amdgcn_alignbyte(d[q + 3], d[q + 2], k);
-    const uint32_t nrf = __builtin_amdgcn_alignbyte(d[q + 7], d[q + 6], k);
-    const uint32_t nps = __builtin_amdgcn_alignbyte(d[q + 8], d[q + 7], k);
-    m |= (ref + 1u < nref1 && nrf + 1u < nref1 && (int32_t)pos >= -1 && (int32_t)nps >= -1) ? 1u << j : 0u;
-  }
-  return m;
-}
-
+// (measured and removed: k_lz leaving k_eager's first filter -- refID, pos, next refID and next
+// pos in range at each of a granule's 16 positions -- as a bitmap in `sieve`, a word per granule
+// once the ring had the granule's 48 bytes: k_eager -0.55 ms, k_lz +0.95 ms on
+// config B -- the filter's ~180 vector instructions per 16-byte granule are issue time k_lz does
+// not have spare.  The `sieve` / `nref1` arguments stay in the kernel's signature, unused.)
 __global__ __launch_bounds__(LZ_THREADS, SBH_LZ_WAVES_PER_EU) void k_lz(const uint8_t *__restrict__ comp, DevBlocks bl, uint64_t nblocks,
                                                     const uint32_t *__restrict__ tok, uint8_t *__restrict__ U,
                                                     uint32_t *__restrict__ sieve, uint32_t nref1) {
@@ -2761,10 +2607,6 @@ __global__ __launch_bounds__(LZ_THREADS, SBH_LZ_WAVES_PER_EU) void k_lz(const ui
     const uint64_t src = bl.cstart[b] + bl.hsize[b] + 5;
     const uint32_t usize = bl.usize[b];
     const uint64_t g0 = G & ~15ull;
-    if (SBH_LZ_SIEVE && sieve) {  // (no ring here: the whole block is "undecided" for k_eager's filter)
-      uint16_t *sv = reinterpret_cast<uint16_t *>(sieve) + (g0 >> 4);
-      for (uint32_t q = t; q < (sh + usize + 15) / 16; q += LZ_THREADS) sv[q] = 0xffffu;
-    }
     // the thread's whole granules: every load first (a granule past the payload reads the
     // first one again and is not stored), then the stores -- one round trip, not one per granule
     constexpr uint32_t NG = (65536u + 16u + 16u * LZ_THREADS - 1u) / (16u * LZ_THREADS);
@@ -2796,10 +2638,8 @@ __global__ __launch_bounds__(LZ_THREADS, SBH_LZ_WAVES_PER_EU) void k_lz(const ui
     }
     return;
   }
-  [[maybe_unused]] uint8_t *img = sm.img + sh;
   const uint32_t *tk = tok + G;
   const uint64_t g0u = G & ~15ull;  // flat address of image position 0
-#if SBH_LZ_RING
   uint32_t fl = 0;  // image position of the first granule not yet in U (uniform)
   // granules [fl, to) of the ring to U (the first one partial: the image starts at sh)
   auto lz_flush = [&](uint32_t &from, uint32_t to) {
@@ -2813,57 +2653,15 @@ __global__ __launch_bounds__(LZ_THREADS, SBH_LZ_WAVES_PER_EU) void k_lz(const ui
     }
     from = to > from ? to : from;
   };
-#endif
-#if SBH_LZ_RING && SBH_LZ_SIEVE
-  // k_eager's first filter on the bytes in the ring: granule G's 16 positions need image bytes
-  // [16 G, 16 G + 48), so its sieve word is written once granule G + 2 is final (flushed); a
-  // granule holding another block's positions (the first, when the block does not start on a
-  // granule) or positions whose 48 bytes run past the block is all ones -- k_eager decides those
-  // itself (both blocks write 0xffff to a shared granule)
-  uint16_t *const sv16 = sieve ? reinterpret_cast<uint16_t *>(sieve) + (g0u >> 4) : nullptr;
-  uint32_t svf = 0;  // first granule whose sieve word is not written yet (uniform)
-  auto lz_sieve = [&](uint32_t upto, uint32_t end_img) {
-    for (uint32_t q = svf + t; q < upto; q += LZ_THREADS) {
-      const uint32_t lo = q * 16;
-      uint32_t m = 0xffffu;
-      if (lo >= sh && lo + 48 <= end_img) {
-        const uint4 a = *reinterpret_cast<const uint4 *>(sm.img + lz_ri(lo));
-        const uint4 b2 = *reinterpret_cast<const uint4 *>(sm.img + lz_ri(lo + 16));
-        const uint4 c2 = *reinterpret_cast<const uint4 *>(sm.img + lz_ri(lo + 32));
-        const uint32_t d[12] = {a.x, a.y, a.z, a.w, b2.x, b2.y, b2.z, b2.w, c2.x, c2.y, c2.z, c2.w};
-        m = sieve16(d, nref1);
-      }
-      sv16[q] = (uint16_t)m;
-    }
-    svf = upto > svf ? upto : svf;
-  };
-#endif
 
   uint32_t base = 0;  // output offset of the chunk's first token
 #ifdef SBH_LZ_PROBE
   uint64_t tp0 = __builtin_readcyclecounter(), t_pre = 0, t_rounds = 0, t_init = 0, t_w = 0, t_ch = 0, t_mk = 0, t_b1 = 0;
   uint32_t nrounds = 0, njumps = 0, nlong = 0;
 #endif
-#ifndef SBH_LZ_TOUCH
-#define SBH_LZ_TOUCH 1  // k_lz: the next chunk's tokens touched into L2 while this chunk's load
-#endif
-#ifndef SBH_LZ_PREFETCH
-// the next chunk's tokens loaded one chunk ahead (0: at the chunk's top).  At the ring's 80 VGPRs
-// the prefetched tokens were spilled to scratch right after their load (which then waited for
-// them): off for the ring (A/B r05za: k_lz -5% B, -6% D, -5% E, output identical)
-#define SBH_LZ_PREFETCH (!SBH_LZ_RING)
-#endif
-static_assert(!(SBH_LZ_CARRY && SBH_LZ_PREFETCH), "the token prefetch assumes chunks of LZ_CHUNK tokens");
-  uint32_t xn[LZ_TPT];  // next chunk's tokens, loaded one chunk ahead
-#pragma unroll
-  for (uint32_t k = 0; k < LZ_TPT; ++k) xn[k] = LZ_TPT * t + k < n ? tk[LZ_TPT * t + k] : 0;
-#if SBH_LZ_CARRY
-  uint32_t c0n = 0;  // the next chunk's first token
+  uint32_t c0n = 0;  // the next chunk's first token (past this chunk's LZ_CHUNK, or at its cut)
   for (uint32_t c0 = 0; c0 < n; c0 = c0n) {
     c0n = c0 + LZ_CHUNK;
-#else
-  for (uint32_t c0 = 0; c0 < n; c0 += LZ_CHUNK) {
-#endif
 #ifdef SBH_LZ_PROBE
     uint64_t ta = __builtin_readcyclecounter();
 #endif
@@ -2872,13 +2670,14 @@ static_assert(!(SBH_LZ_CARRY && SBH_LZ_PREFETCH), "the token prefetch assumes ch
     uint32_t x[LZ_TPT], len[LZ_TPT], dist[LZ_TPT], off[LZ_TPT];
     bool match[LZ_TPT];
     uint32_t mysum = 0;
-#if !SBH_LZ_PREFETCH
     // all of the thread's token loads first, every lane loading (the index clamped): a load under
     // a branch, or one after the previous token's decoding, was waited for before the next one
     // was issued -- LZ_TPT HBM round trips per chunk instead of one
+    // (measured and removed: the next chunk's tokens loaded one chunk ahead -- at the ring's 80
+    // VGPRs they were spilled to scratch right after their load, which then waited for them;
+    // A/B r05za, output identical: without it k_lz -5% B, -6% D, -5% E)
 #pragma unroll
     for (uint32_t k = 0; k < LZ_TPT; ++k) x[k] = tk[min(i0 + k, n - 1)];
-#if SBH_LZ_TOUCH
     // the next chunk's tokens (as if this chunk is not cut) touched into L2, a dword per 128-byte
     // line, behind this chunk's own loads: their wait covers the touch, and the next chunk's
     // loads then come from L2 instead of HBM
@@ -2888,29 +2687,20 @@ static_assert(!(SBH_LZ_CARRY && SBH_LZ_PREFETCH), "the token prefetch assumes ch
       if (t < LZ_CHUNK / 32 && nx0 < n)
         asm volatile("global_load_dword %0, %1, off" : "=v"(tch) : "v"(tk + nx0) : "memory");
     }
-#endif
-#endif
 #pragma unroll
     for (uint32_t k = 0; k < LZ_TPT; ++k) {
-#if SBH_LZ_PREFETCH
-      x[k] = xn[k];
-      xn[k] = i0 + LZ_CHUNK + k < n ? tk[i0 + LZ_CHUNK + k] : 0;
-#endif
       match[k] = i0 + k < n && (x[k] & TOK_MATCH) != 0;
       len[k] = i0 + k >= n ? 0 : match[k] ? (x[k] >> 16) & 0x1ff : 1 + ((x[k] >> 24) & 1u);  // (TOK_PAIR: 2)
       dist[k] = x[k] & 0xffff;
       mysum += len[k];
     }
-#if !SBH_LZ_PREFETCH && SBH_LZ_TOUCH
     asm volatile("" ::"v"(tch));  // (live until the tokens' wait above has covered it)
-#endif
     for (uint32_t w = t; w < SB_WORDS; w += LZ_THREADS) sm.pp.sbits[w] = 0;  // ordered by the scan's barrier
     uint32_t chunk_len;
     off[0] = base + block_scan<LZ_THREADS>(mysum, wsum, &chunk_len);
 #pragma unroll
     for (uint32_t k = 1; k < LZ_TPT; ++k) off[k] = off[k - 1] + len[k - 1];
     const uint32_t chunk_end = base + chunk_len;
-#if SBH_EMIT_NOCHK
     // too far back (zlib's "invalid distance too far back"): a match reaching before the block's
     // first byte fails the block as the serial decoder would (INF_DATA); the Huffman passes no
     // longer test each distance code (a block another path already failed keeps its status)
@@ -2927,33 +2717,26 @@ static_assert(!(SBH_LZ_CARRY && SBH_LZ_PREFETCH), "the token prefetch assumes ch
       }
       if (far && bl.status[b] == INF_OK) bl.status[b] = INF_DATA;
     }
-#endif
 #ifdef SBH_LZ_PROBE
     const uint64_t tb = __builtin_readcyclecounter();
     t_pre += tb - ta;
 #endif
-    // Passes over the chunk's output, each at most PTR_CAP bytes (from its 16-byte granule):
-    // a pass takes the tokens that START in [pb, pe) and pe is the start of the first token
-    // that would end past the pass's slots.  One pass when the chunk fits (the common
-    // case); long-match chunks take a few instead of a slower resolution.
-    uint32_t pb = base;
-    [[maybe_unused]] uint32_t cend = chunk_end;  // (SBH_LZ_CARRY) where this chunk's pass ended
-    for (;;) {
-#if SBH_LZ_RING
-      // every byte before pb is final (the scan's or the last pass's barrier): its whole granules
+    // The chunk's pass, at most PTR_CAP bytes of output (from its 16-byte granule): it takes the
+    // tokens that START in [pb, pe), and pe is the start of the first token that would end past
+    // the pass's slots -- the chunk's end when the chunk fits (the common case).
+    const uint32_t pb = base;
+    uint32_t cend;  // where this chunk's pass ended
+    {
+      // every byte before pb is final (the scan's barrier): its whole granules
       // leave the ring for U before the ring wraps onto them
       lz_flush(fl, (sh + pb) & ~15u);
-#if SBH_LZ_SIEVE
-      if (sv16 && fl >= 48) lz_sieve(fl / 16 - 2, ~0u);
-#endif
-#endif
       // slots start at the 16-byte LDS granule holding `pb`, so that each thread's 16
       // slots are one granule of the image
       const uint32_t lead = (sh + pb) & 15, abase = pb - lead;
       uint32_t pe = chunk_end;
-#if SBH_LZ_CARRY
       // (carry: a chunk is one pass; the tokens from the cut on start the next chunk, so every
-      // chunk but the last of a block fills its pass instead of leaving a short second one)
+      // chunk but the last of a block fills its pass instead of leaving a short second one.
+      // Removed with it: further passes over the rest of a cut chunk.)
       static_assert(LZ_CHUNK <= 2048 && 65536u + 16u + 258u < (1u << 21), "cut keys: offset << 11 | token");
       if (chunk_end - abase > PTR_CAP) {  // uniform: cut the chunk
         uint32_t cut = ~0u;
@@ -2964,15 +2747,6 @@ static_assert(!(SBH_LZ_CARRY && SBH_LZ_PREFETCH), "the token prefetch assumes ch
         pe = key >> 11;
         c0n = c0 + (key & 0x7ffu);
       }
-#else
-      if (chunk_end - abase > PTR_CAP) {  // uniform: cut the chunk
-        uint32_t cut = chunk_end;
-#pragma unroll
-        for (uint32_t k = 0; k < LZ_TPT; ++k)
-          if (i0 + k < n && off[k] >= pb && off[k] + len[k] - abase > PTR_CAP) cut = min(cut, off[k]);
-        pe = block_min<LZ_THREADS>(cut, sm.pp.wmin);
-      }
-#endif
       const uint32_t plen = pe - pb;
 #ifdef SBH_LZ_PROBE
       nrounds += pe != chunk_end || pb != base;
@@ -2982,17 +2756,14 @@ static_assert(!(SBH_LZ_CARRY && SBH_LZ_PREFETCH), "the token prefetch assumes ch
       // Tokens mark their starts: one slot write (a literal points at itself, a short
       // match at its source) and one start bit each; the bytes inside a short match get
       // their pointers in the slot pass below, from the nearest start.
-      // a match the wave marks byte by byte: longer than LZ_SHORT, or overlapping itself
-      // (dist < len: its bytes repeat a period shorter than the match, a mod per byte)
+      // wide: a match longer than LZ_SHORT, marked apart (below).
+      // (measured and removed: overlapping short matches (dist < len) also marked byte by byte by
+      // the wave -- A/B r04c: k_lz +5% B, +26% D, +10% E; a thread's start bits ORed per word
+      // first, at most 3 atomics instead of one per token -- A/B r04e: k_lz +0.5..3%)
       bool wide[LZ_TPT];
 #pragma unroll
       for (uint32_t k = 0; k < LZ_TPT; ++k)
-        wide[k] = match[k] && (len[k] > LZ_SHORT || (SBH_LZ_OVL_WAVE && dist[k] < len[k]));
-#if SBH_LZ_SBMASK
-      // start bits gathered per word first: a thread's short tokens span at most 3 words (2 x 32
-      // bytes), so 3 atomics at most (one when they share a word) instead of one per token
-      uint32_t wA = ~0u, mA = 0, mB = 0, mC = 0;
-#endif
+        wide[k] = match[k] && len[k] > LZ_SHORT;
 #pragma unroll
       for (uint32_t k = 0; k < LZ_TPT; ++k) {
         if (i0 + k >= n || wide[k] || !(off[k] - pb < plen)) continue;
@@ -3006,27 +2777,11 @@ static_assert(!(SBH_LZ_CARRY && SBH_LZ_PREFETCH), "the token prefetch assumes ch
           if (x[k] & TOK_PAIR) {
             uint32_t ib = ia + 1;
             asm volatile("" : "+v"(ib));
-            sm.img[SBH_LZ_RING && ib == LZ_IMG ? 0u : ib] = (uint8_t)(x[k] >> 16);
+            sm.img[ib == LZ_IMG ? 0u : ib] = (uint8_t)(x[k] >> 16);
           }
         }
-#if SBH_LZ_SBMASK
-        const uint32_t w = d >> 5, bit = 1u << (d & 31);
-        wA = wA == ~0u ? w : wA;
-        const uint32_t r = w - wA;
-        mA |= r == 0 ? bit : 0u;
-        mB |= r == 1 ? bit : 0u;
-        mC |= r == 2 ? bit : 0u;
-        if (r > 2)  // (a long match between this thread's short tokens)
-          __hip_atomic_fetch_or(&sbits[w], bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#else
         __hip_atomic_fetch_or(&sbits[d >> 5], 1u << (d & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#endif
       }
-#if SBH_LZ_SBMASK
-      if (mA) __hip_atomic_fetch_or(&sbits[wA], mA, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      if (mB) __hip_atomic_fetch_or(&sbits[wA + 1], mB, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      if (mC) __hip_atomic_fetch_or(&sbits[wA + 2], mC, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#endif
       // long matches.  Few in a wave (short-read data: one or two): the wave writes every byte's
       // pointer, match by match.  Many (long reads): each thread marks its own with a start every
       // 32 bytes (a pointer and a start bit each), so the slot pass finds every byte's start
@@ -3043,11 +2798,9 @@ static_assert(!(SBH_LZ_CARRY && SBH_LZ_PREFETCH), "the token prefetch assumes ch
         if ((uint32_t)__builtin_popcountll(lm) >= LZ_LMARK_MIN) {
           if (mine) {
             uint32_t D = dist[k];
-#if SBH_LZ_NOHOIST
             // (opaque to the compiler, which otherwise computes the mod below for every token of
             // every chunk, ahead of this branch: ~36 VALU per chunk and wave)
             asm volatile("" : "+v"(D));
-#endif
             const uint32_t d0 = off[k] - abase, L = len[k];
             const bool ov = D != 0 && D < L;  // (D = 0: a too-far-back match, marked at itself)
             uint32_t r = 0;  // 32 m mod D (ov)
@@ -3092,7 +2845,7 @@ static_assert(!(SBH_LZ_CARRY && SBH_LZ_PREFETCH), "the token prefetch assumes ch
 #endif
       // slot pass: every byte's pointer from its token's start (at most LZ_SHORT - 1
       // slots back): byte j of a match that starts at slot s and copies from v points at
-      // v + j, or v + (j mod (s - v)) when the match overlaps itself (rare); a literal
+      // v + j (at v when the distance s - v is 1); a literal
       // start points at itself.  Each thread owns up to NHP half granules (8 slots) and
       // keeps their pointers in registers for the chase below.
       const uint32_t nh = (plen + lead + PTR_HALF - 1) / PTR_HALF;
@@ -3114,7 +2867,6 @@ static_assert(!(SBH_LZ_CARRY && SBH_LZ_PREFETCH), "the token prefetch assumes ch
         uint32_t st = low ? wi * 32 + 31 - __builtin_clz(low) : prev ? wi * 32 - 1 - __builtin_clz(prev) : s0;
         const uint32_t wb = cur >> sh8;
         uint32_t sidx[PTR_HALF], v[PTR_HALF];
-#if SBH_LZ_SLOT128
         // the start values: the window's own 8 slots in one 16-byte read (lane h at 16 h bytes: no
         // bank conflicts, where 8 u16 reads at a 16-byte lane stride were 4-way), the nearest start
         // before the window in one u16 read; each slot takes its last start's value
@@ -3129,62 +2881,19 @@ static_assert(!(SBH_LZ_CARRY && SBH_LZ_PREFETCH), "the token prefetch assumes ch
           vl = s ? (k & 1 ? od[k >> 1] >> 16 : od[k >> 1] & 0xffffu) : vl;
           v[k] = vl;
         }
-#else
-#pragma unroll
-        for (uint32_t k = 0; k < PTR_HALF; ++k) {
-          st = (wb >> k) & 1u ? s0 + k : st;
-          sidx[k] = st;
-        }
-#pragma unroll
-        for (uint32_t k = 0; k < PTR_HALF; ++k) v[k] = p16[sidx[k]];
-#endif
-#if SBH_LZ_OVL_WAVE
-        // (no byte of a short start-marked match reaches past its distance: overlapping matches
-        // had every byte marked with its final offset by the wave)
-#pragma unroll
-        for (uint32_t k = 0; k < PTR_HALF; ++k) {
-          const bool in = k - klo < khi - klo;
-          c[hh][k] = in ? v[k] + (s0 + k - sidx[k]) : g0 + k;
-        }
-#elif !SBH_LZ_MOD
-        // byte j of every match points at v + j = its position - distance: inside the match
-        // itself when the match overlaps (j >= distance), which is still an earlier byte of the
-        // same value; the chase follows it
-#pragma unroll
-        for (uint32_t k = 0; k < PTR_HALF; ++k) {
-          const bool in = k - klo < khi - klo;
-          c[hh][k] = in ? v[k] + (s0 + k - sidx[k]) : g0 + k;
-        }
-#else
-        uint32_t ovl = 0;  // slots of overlapping matches
 #pragma unroll
         for (uint32_t k = 0; k < PTR_HALF; ++k) {
           const uint32_t j = s0 + k - sidx[k], dd = abase + sidx[k] - v[k];
           const bool in = k - klo < khi - klo;
-#if SBH_LZ_RUN1 && SBH_LZ_MOD2
           // distance 1 (a run of one byte value): every byte points at the source byte (A/B r04h:
           // k_lz -9.1% B, -6.2% D, -4.6% E); a longer overlap (d >= 2) keeps v + j, an earlier
           // byte of the match itself, which the chase follows -- no mod at all (A/B r04m2: k_lz
           // -6.5% B, -6.4% D, -9.2% E; v + j is position - d, always an earlier byte of equal value)
+          // (measured and removed: v + (j mod d) for every overlap byte, and for those at d >= 2
+          // only; v + j for every byte, distance 1 included, a longer chase -- A/B r04p: k_lz
+          // +4% B, +2% D against the mod)
           c[hh][k] = in ? v[k] + (dd == 1 ? 0u : j) : g0 + k;
-#elif SBH_LZ_RUN1
-          // a match at distance 1 (a run of one byte value): every byte copies its source byte,
-          // no mod needed
-          const bool one = dd == 1;
-          // (dd = 0: a literal pair's second byte or a too-far-back match -- its own slot, final)
-          ovl |= (in && j != 0 && dd != 0 && j >= dd && !one) ? 1u << k : 0u;
-          c[hh][k] = in ? v[k] + (one ? 0u : j) : g0 + k;
-#else
-          ovl |= (in && j != 0 && dd != 0 && j >= dd) ? 1u << k : 0u;
-          c[hh][k] = in ? v[k] + j : g0 + k;
-#endif
         }
-        if (ovl) {
-#pragma unroll
-          for (uint32_t k = 0; k < PTR_HALF; ++k)
-            if ((ovl >> k) & 1u) c[hh][k] = v[k] + mod_small(s0 + k - sidx[k], abase + sidx[k] - v[k]);
-        }
-#endif
 #pragma unroll
         for (uint32_t k = 0; k < PTR_HALF; ++k)  // in the pass, not a literal, not final yet
           pend[hh] |= (c[hh][k] != g0 + k && c[hh][k] >= pb) ? 1u << k : 0u;
@@ -3210,20 +2919,12 @@ static_assert(!(SBH_LZ_CARRY && SBH_LZ_PREFETCH), "the token prefetch assumes ch
       // position.
       auto gather8 = [&](const uint32_t *cp, uint32_t g0) {
         uint32_t w[2];
-#if SBH_LZ_RING
         const uint8_t *rb = sm.img;
 #pragma unroll
         for (uint32_t q = 0; q < 2; ++q)
           w[q] = (uint32_t)rb[lz_ri(sh + cp[4 * q])] | (uint32_t)rb[lz_ri(sh + cp[4 * q + 1])] << 8 |
                  (uint32_t)rb[lz_ri(sh + cp[4 * q + 2])] << 16 | (uint32_t)rb[lz_ri(sh + cp[4 * q + 3])] << 24;
         *reinterpret_cast<uint2 *>(sm.img + lz_ri(sh + g0)) = make_uint2(w[0], w[1]);
-#else
-#pragma unroll
-        for (uint32_t q = 0; q < 2; ++q)
-          w[q] = (uint32_t)img[cp[4 * q]] | (uint32_t)img[cp[4 * q + 1]] << 8 | (uint32_t)img[cp[4 * q + 2]] << 16 |
-                 (uint32_t)img[cp[4 * q + 3]] << 24;
-        *reinterpret_cast<uint2 *>(img + g0) = make_uint2(w[0], w[1]);
-#endif
       };
       const uint32_t p16a = (uint32_t)reinterpret_cast<uintptr_t>(p16);
       [[maybe_unused]] const uint32_t choff = uni(p16a) - 2u * abase;  // LDS address of pointer c: choff + 2 c
@@ -3271,35 +2972,19 @@ static_assert(!(SBH_LZ_CARRY && SBH_LZ_PREFETCH), "the token prefetch assumes ch
 #ifdef SBH_LZ_PROBE
       t_ch += __builtin_readcyclecounter() - tc;
 #endif
-#if SBH_LZ_CARRY
       cend = pe;
-      break;  // (one pass per chunk)
-#endif
-      if (pe == chunk_end) break;
-      __syncthreads();  // the pass's slots and start bits are reused by the next pass
-      for (uint32_t w = t; w < SB_WORDS; w += LZ_THREADS) sm.pp.sbits[w] = 0;
-      pb = pe;
-      __syncthreads();
     }
-#if SBH_LZ_CARRY
     base = cend;  // (chunk_end unless cut: the cut token starts the next chunk)
-#else
-    base += chunk_len;
-#endif
-#if !SBH_LZ_NO_END_BAR
-    __syncthreads();  // slots / wsum are reused by the next chunk
-#endif
-    // (without it: the next chunk's slot writes all come after its scan's barrier, which every
-    // wave reaches only once done with this chunk; its wsum / sbits writes before that barrier
-    // touch nothing this chunk still reads -- wsum was read before this chunk's marks, sbits
-    // before its chase)
+    // (no barrier at a chunk's end: the next chunk's slot writes all come after its scan's barrier,
+    // which every wave reaches only once done with this chunk; its wsum / sbits writes before that
+    // barrier touch nothing this chunk still reads -- wsum was read before this chunk's marks,
+    // sbits before its chase.  Measured and removed: the barrier -- A/B: without it k_lz -3% B,
+    // -2% D, -3% E)
 #ifdef SBH_LZ_PROBE
     t_rounds += __builtin_readcyclecounter() - tb;
 #endif
   }
-#if SBH_LZ_NO_END_BAR
   __syncthreads();  // the image is complete
-#endif
 #ifdef SBH_LZ_PROBE
   {
     uint32_t tot = 0;
@@ -3316,11 +3001,7 @@ static_assert(!(SBH_LZ_CARRY && SBH_LZ_PREFETCH), "the token prefetch assumes ch
   // write the image: 16-byte granules aligned to the flat address (the ring: those not yet written)
   const uint64_t g0 = g0u;
   const uint32_t ngran = (sh + usize + 15) / 16;
-#if SBH_LZ_RING
   const uint32_t q0 = fl / 16;
-#else
-  const uint32_t q0 = 0;
-#endif
   for (uint32_t q = q0 + t; q < ngran; q += LZ_THREADS) {
     const uint32_t lo = q * 16;  // image offset (relative to sm.img) of the granule
     if (lo >= sh && lo + 16 <= sh + usize) {
@@ -3332,9 +3013,6 @@ static_assert(!(SBH_LZ_CARRY && SBH_LZ_PREFETCH), "the token prefetch assumes ch
       }
     }
   }
-#if SBH_LZ_RING && SBH_LZ_SIEVE
-  if (sv16) lz_sieve(ngran, sh + usize);  // (the image is complete: the last barrier above)
-#endif
 }
 
 // The first block whose inflate status is not INF_OK (atomicMin; *first preset to ~0):
@@ -3359,29 +3037,18 @@ hipError_t launch_huff(const uint8_t *comp, DevBlocks blocks, uint64_t nblocks, 
   if (nblocks == 0) return hipSuccess;
   // the kernels index tokens by flat offset: tok[ustart_b] is block b's first token slot
   uint32_t *tok = reinterpret_cast<uint32_t *>(reinterpret_cast<uintptr_t>(tok_buf) - tok_base * 4);
-#ifdef SBH_HUFF_SERIAL  // (the A/B baseline: no lane-parallel stage to run apart)
-  const uint64_t grid = (nblocks + WAVES - 1) / WAVES;
-  if (stages & HUFF_SERIAL)
-    hipLaunchKernelGGL(k_huff_serial<false>, dim3((uint32_t)grid), dim3(WAVES * WAVE), 0, stream, comp, blocks, nblocks,
-                       tok);
-#else
   if (stages & HUFF_FAST) {
     const dim3 hdr_grid((uint32_t)((nblocks + HDR_WAVES - 1) / HDR_WAVES)), hdr_wg(WAVE * HDR_WAVES);
     hipLaunchKernelGGL(k_hdr<false>, hdr_grid, hdr_wg, 0, stream, comp, blocks, nblocks, tok);
     hipLaunchKernelGGL(k_huff, dim3((uint32_t)nblocks), dim3(HT), 0, stream, comp, blocks, nblocks, tok);
-#if SBH_TAIL
-#if SBH_TAIL_HDR
     hipLaunchKernelGGL(k_hdr<true>, hdr_grid, hdr_wg, 0, stream, comp, blocks, nblocks, tok);
-#endif
     hipLaunchKernelGGL(k_huff_tail, dim3((uint32_t)nblocks), dim3(TAIL_NT), 0, stream, comp, blocks, nblocks, tok);
-#endif
   }
   if (stages & HUFF_SERIAL) {
     const uint64_t grid = (nblocks + WAVES - 1) / WAVES;
     hipLaunchKernelGGL(k_huff_serial<true>, dim3((uint32_t)grid), dim3(WAVES * WAVE), 0, stream, comp, blocks, nblocks,
                        tok);
   }
-#endif
   return hipGetLastError();
 }
 
@@ -3389,14 +3056,9 @@ hipError_t launch_lz(const uint8_t *comp, DevBlocks blocks, uint64_t nblocks, co
                      uint64_t tok_base, uint8_t *U, hipStream_t stream, uint32_t *sieve, uint32_t nref1) {
   if (nblocks == 0) return hipSuccess;
   const uint32_t *tok = reinterpret_cast<const uint32_t *>(reinterpret_cast<uintptr_t>(tok_buf) - tok_base * 4);
-  if (!SBH_LZ_SIEVE || !SBH_LZ_RING) sieve = nullptr;
-#ifdef SBH_LZ_PAD  // occupancy probe: dynamic LDS that leaves one workgroup per CU
-  hipLaunchKernelGGL(k_lz, dim3((uint32_t)nblocks), dim3(LZ_THREADS), SBH_LZ_PAD, stream, comp, blocks, nblocks, tok, U,
-                     sieve, nref1);
-#else
+  sieve = nullptr;  // (k_lz writes no sieve: see the note above k_lz)
   hipLaunchKernelGGL(k_lz, dim3((uint32_t)nblocks), dim3(LZ_THREADS), 0, stream, comp, blocks, nblocks, tok, U, sieve,
                      nref1);
-#endif
   return hipGetLastError();
 }
 

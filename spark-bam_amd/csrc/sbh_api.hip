@@ -66,7 +66,7 @@ hipError_t build_chain(const uint8_t *comp, uint64_t n, const uint64_t *cand, ui
 hipError_t launch_eager(const uint8_t *U, uint64_t u_pad, uint64_t begin, uint64_t end, const uint64_t *seg_end,
                         uint32_t nseg, uint32_t open_last, const int32_t *ctg, int32_t nctg, int32_t rtc,
                         uint32_t *bits, unsigned long long *counters, hipStream_t st, uint64_t front,
-                        uint64_t *defer_pos, uint64_t defer_cap, uint64_t *xq_pos, uint64_t xq_cap, TileSum *tsum,
+                        uint64_t *defer_pos, uint64_t defer_cap, uint64_t *xq_pos, uint64_t xq_cap,
                         const uint32_t *sieve = nullptr);
 hipError_t launch_eager_xq(const uint8_t *U, uint64_t begin, const uint64_t *seg_end, uint32_t nseg,
                            uint32_t open_last, const int32_t *ctg, int32_t nctg, int32_t rtc, uint32_t *bits,
@@ -84,7 +84,7 @@ hipError_t launch_first_set(const uint32_t *bits, uint64_t begin, uint64_t from,
 hipError_t launch_verify_chain_count(const uint8_t *U, const uint32_t *bits, uint64_t begin, uint64_t bits_end,
                                      uint64_t from, uint64_t E, uint64_t total, unsigned long long *n_anom,
                                      unsigned long long *first_anom, unsigned long long *exit_pos,
-                                     unsigned long long *n_set, const TileSum *tsum, hipStream_t st,
+                                     unsigned long long *n_set, hipStream_t st,
                                      const unsigned long long *from_dev = nullptr, uint32_t *chunk_cnt = nullptr);
 hipError_t launch_chain_walk(const uint8_t *U, uint64_t first, uint64_t E, uint64_t total,
                              unsigned long long *count, unsigned long long *last, hipStream_t st);
@@ -187,12 +187,11 @@ struct sbh_shard {
   DBuf<int32_t> ctg;
   int32_t nctg = -1;
   DBuf<uint32_t> bits;
-  DBuf<TileSum> tsum;
   // k_lz's first-filter bitmap for k_eager (launch_lz's sieve), valid for the inflated bytes and
   // the contig count it was computed with (sieve_nref1 = contigs + 1; 0: none)
   DBuf<uint32_t> sieve;
   uint32_t sieve_nref1 = 0;
-  bool pipe_fallback = false;  // run_pipelined redid the eager pass (a deferral overflow)  // per quarter eager tile of bits (from bits_begin): the chain proof's summaries
+  bool pipe_fallback = false;  // run_pipelined redid the eager pass (a deferral overflow)
   // chain marking (pointer doubling) over the set bits of [cm_first, cm_E) when the bitmap
   // is not the chain: node positions, per-word prefix counts, jumps, marks and their prefix
   DBuf<uint64_t> cm_pos, cm_wcnt, cm_wpre, cm_mark, cm_mpre;
@@ -554,7 +553,7 @@ int sbh_shard_destroy(sbh_shard *sh) {
   sh->counts.release(); sh->cfirst.release(); sh->offs.release(); sh->cand.release(); sh->v.release(); sh->rank.release();
   sh->tmp.release(); sh->J0.release(); sh->J1.release(); sh->on.release(); sh->d_seg.release();
   sh->U.release(); sh->u_pad_clean = ~0ull; sh->ctg.release(); sh->bits.release(); sh->words.release(); sh->close_pos.release();
-  sh->close_word.release(); sh->ctr.release(); sh->opix.release(); sh->tsum.release(); sh->sieve.release();
+  sh->close_word.release(); sh->ctr.release(); sh->opix.release(); sh->sieve.release();
   sh->cc.release();
   sh->comp2.release(); sh->aux2.release();
   for (hipStream_t st : sh->pf_stream) (void)hipStreamDestroy(st);
@@ -1000,8 +999,9 @@ static bool split_cc_on() {
   return !(e && e[0] == '0');
 }
 
-// SBH_SIEVE=1 (with k_lz built -DSBH_LZ_SIEVE=1): k_lz leaves k_eager's first filter as a bitmap
-// (measured slower, DESIGN.md §10: off by default; k_eager sweeps refIDs itself)
+// SBH_SIEVE=1: k_eager reads its first filter from a bitmap k_lz left (measured slower, DESIGN.md
+// §10: k_lz's writer is removed, so nothing fills the bitmap; off by default, k_eager sweeps
+// refIDs itself)
 static bool sieve_on() {
   const char *e = std::getenv("SBH_SIEVE");
   return e && e[0] == '1';
@@ -1250,13 +1250,6 @@ static uint64_t xq_cap() {
   const char *e = std::getenv("SBH_XQ");
   return e && e[0] == '0' ? 0 : XQ_CAP_MAX;
 }
-// SBH_TSUM=1: k_eager writes per-quarter-tile chain summaries and the chain proof reads them
-// instead of every true position's record length from U (its 4.8x line over-read).  Off by
-// default: measured (r04g, config B) the proof 0.46 -> 0.36 ms per step but k_eager 3.00 -> 3.24 ms.
-static bool tsum_on() {
-  const char *e = std::getenv("SBH_TSUM");
-  return SBH_TSUM_CODE && e && e[0] == '1';
-}
 
 static int eager_range(sbh_shard *sh, uint64_t begin, uint64_t end, int32_t rtc, uint64_t *n_true) {
   sbh_ctx *ctx = sh->ctx;
@@ -1264,7 +1257,6 @@ static int eager_range(sbh_shard *sh, uint64_t begin, uint64_t end, int32_t rtc,
   const uint64_t nwords = (end - begin + 31) / 32;
   sh->chain_ok = sh->cm_valid = false;
   HIPCHK(ctx, sh->bits.ensure(nwords + 1));
-  if (tsum_on()) HIPCHK(ctx, sh->tsum.ensure((end - begin + EAGER_TILE - 1) / EAGER_TILE * 4 + 4));
   HIPCHK(ctx, sh->xq.ensure(2 * XQ_CAP_MAX));
   unsigned long long *c = sh->ctr.p;
   HIPCHK(ctx, hipMemsetAsync(c, 0, 48, st));
@@ -1272,7 +1264,7 @@ static int eager_range(sbh_shard *sh, uint64_t begin, uint64_t end, int32_t rtc,
   mark(sh, 4);
   HIPCHK(ctx, launch_eager(sh->U.p, sh->utotal + sh->pad, begin, end, sh->d_seg.p, (uint32_t)sh->seg_end.size(),
                            sh->open_last ? 1 : 0, sh->ctg.p, sh->nctg, rtc, sh->bits.p, c, st, ~0ull, nullptr, 0,
-                           sh->xq.p, xq_cap(), tsum_on() ? sh->tsum.p : nullptr,
+                           sh->xq.p, xq_cap(),
                            sh->sieve_nref1 && sh->sieve_nref1 == (uint32_t)sh->nctg + 1 ? sh->sieve.p : nullptr));
   HIPCHK(ctx, launch_eager_xq(sh->U.p, begin, sh->d_seg.p, (uint32_t)sh->seg_end.size(), sh->open_last ? 1 : 0,
                               sh->ctg.p, sh->nctg, rtc, sh->bits.p, c, sh->xq.p, xq_cap(), st));
@@ -1492,7 +1484,7 @@ static int count_records_impl(sbh_shard *sh, uint64_t first, uint64_t E, uint64_
       // verify bitmap == chain and count the set bits in one pass (k_verify_chain_w: wave-
       // cooperative successors, so sparse bitmaps of long records cost no word-by-word scans)
       HIPCHK(ctx, launch_verify_chain_count(sh->U.p, sh->bits.p, sh->bits_begin, sh->bits_end, first, E, total, c,
-                                            c + 1, c + 3, c + 2, tsum_on() ? sh->tsum.p : nullptr, st, nullptr,
+                                            c + 1, c + 3, c + 2, st, nullptr,
                                             sh->cc.p));
       HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + 16, c, 32, hipMemcpyDeviceToHost, st));
       // The proof walks the set bits of [first, E), and `first` need not be one of them: a caller's
@@ -1985,7 +1977,6 @@ static int run_pipelined(sbh_shard *sh, uint64_t E, int32_t rtc, uint64_t *n_tru
   auto wait = [](hipStream_t s, hipEvent_t e, hipStream_t on) { return s == on ? hipSuccess : hipStreamWaitEvent(s, e, 0); };
   HIPCHK(ctx, sh->tok.ensure(P.tok_len));
   HIPCHK(ctx, sh->bits.ensure((E + 31) / 32 + 1));
-  if (tsum_on()) HIPCHK(ctx, sh->tsum.ensure((E + EAGER_TILE - 1) / EAGER_TILE * 4 + 4));
   HIPCHK(ctx, sh->defer.ensure(DEFER_CAP));
   HIPCHK(ctx, sh->xq.ensure(2 * XQ_CAP_MAX));
   HIPCHK(ctx, zero_u_pad(sh, sa));
@@ -2042,8 +2033,7 @@ static int run_pipelined(sbh_shard *sh, uint64_t E, int32_t rtc, uint64_t *n_tru
       HIPCHK(ctx, hipEventRecord(e[4], se));
       HIPCHK(ctx, launch_eager(sh->U.p, sh->utotal + sh->pad, e_done, hi, sh->d_seg.p, (uint32_t)sh->seg_end.size(),
                                sh->open_last ? 1 : 0, sh->ctg.p, sh->nctg, rtc, sh->bits.p + e_done / 32, c, se,
-                               front, sh->defer.p, DEFER_CAP, sh->xq.p, xq_cap(),
-                               tsum_on() ? sh->tsum.p + e_done / EAGER_SUB : nullptr, sv));
+                               front, sh->defer.p, DEFER_CAP, sh->xq.p, xq_cap(), sv));
       HIPCHK(ctx, hipEventRecord(e[5], se));
       eager_launched[i] = 1;
       e_done = hi;
@@ -2144,7 +2134,7 @@ int sbh_run_shard(sbh_shard *sh, uint64_t index_start, uint64_t own_end_file, in
   auto tail_launch = [&](hipStream_t s) -> hipError_t {
     hipError_t e = launch_first_set(sh->bits.p, 0, 0, hi0, tbest, s);
     if (e == hipSuccess)
-      e = launch_verify_chain_count(sh->U.p, sh->bits.p, 0, E, 0, E0, total0, tc, tc + 1, tc + 3, tc + 2, nullptr, s,
+      e = launch_verify_chain_count(sh->U.p, sh->bits.p, 0, E, 0, E0, total0, tc, tc + 1, tc + 3, tc + 2, s,
                                     tbest, sh->cc.p);
     return e;
   };

@@ -19,12 +19,12 @@ from deflate_build import (DIST_EXTRA, LEN_EXTRA, Bits, dynamic_block, expand, f
                            member, raw_bits, stored_block)
 
 # Constants of spark-bam_amd/csrc/inflate.hip the cases are built around (mirrored here only):
-LIT_FAST = 10          # inflate.hip:36   SBH_LIT_FAST (10-bit literal/length lookup)
-HT = 256               # inflate.hip:959  SBH_HT (k_huff lanes per BGZF block)
-STAGE_DW = 6144        # inflate.hip:962  SBH_STAGE_DW (deflate dwords staged in LDS)
-PAR_MIN_USIZE = 4096   # inflate.hip:969  smaller blocks decode serially
-MIN_SLICE = 128        # inflate.hip:971  SBH_MIN_SLICE (bits per lane at least)
-HDR_OUT_DW = 2404      # inflate.hip:976-979  HDR_SENT (2048) + sent[320] + pk[32] + 4
+LIT_FAST = 10          # inflate.hip:38   LIT_FAST (10-bit literal/length lookup)
+HT = 256               # inflate.hip:952  SBH_HT (k_huff lanes per BGZF block)
+STAGE_DW = 6144        # inflate.hip:955  SBH_STAGE_DW (deflate dwords staged in LDS)
+PAR_MIN_USIZE = 4096   # inflate.hip:962  smaller blocks decode serially
+MIN_SLICE = 128        # inflate.hip:964  SBH_MIN_SLICE (bits per lane at least)
+HDR_OUT_DW = 2404      # inflate.hip:969-972  HDR_SENT (2048) + sent[320] + pk[32] + 4
 PAR, STORED, SERIAL = 0, 1, 2  # sbh_inflate_paths
 OK, SIZE, DATA, BAD_ISIZE = "ok", "inflate_size", "inflate_data", "bad_isize"
 

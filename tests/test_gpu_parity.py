@@ -445,17 +445,16 @@ def test_chain_count_with_false_positive_bits(ctx, synth_files, name, marking, m
 
 
 @pytest.mark.parametrize("name", ["adversarial", "short_l6", "short_l0", "long"])
-def test_chain_proof_tile_summaries(ctx, synth_files, name, monkeypatch):
-    """The chain proof (k_verify_chain_w) reading k_eager's per-tile summaries gives the same
-    counts, exits and anomaly counts as reading every true position's length from U
-    (SBH_TSUM=1 vs 0), over the whole file (sbh_run_shard, pipelined eager) and over sub-ranges
-    that start and end inside tiles or on tile edges (sbh_check_eager's bitmap)."""
+def test_chain_proof_whole_file_and_subranges(ctx, synth_files, name):
+    """The chain proof (k_verify_chain_w) counts the oracle's record chain over the whole file
+    (sbh_run_shard, pipelined eager) and over sub-ranges that start and end inside tiles or on
+    tile edges (sbh_check_eager's bitmap), with the same counts, exits and anomaly counts in two
+    runs on two fresh shards."""
     data = synth_files[name]
     of = OracleFile(data)
     tile = 16384
 
-    def run(flag):
-        monkeypatch.setenv("SBH_TSUM", flag)
+    def run(which):
         sh = load(ctx, data, of.contig_len)
         try:
             r = sh.run(0, data.size)
@@ -471,16 +470,16 @@ def test_chain_proof_tile_summaries(ctx, synth_files, name, monkeypatch):
                     e = min(e, of.flat_size)
                     want = int(np.count_nonzero((chain >= f) & (chain < e)))
                     got = sh.count_records(f, e)
-                    assert got == want, (name, flag, f, e)
+                    assert got == want, (name, which, f, e)
                     out.append((f, e, got, sh.chain_from(f, e)))
             return out, len(chain)
         finally:
             sh.close()
 
-    on, n_chain = run("1")
-    off, _ = run("0")
-    assert on == off
-    assert on[0][0] == n_chain
+    one, n_chain = run(1)
+    two, _ = run(2)
+    assert one == two
+    assert one[0][0] == n_chain
 
 
 @pytest.mark.parametrize("name", FIXTURES)
