@@ -980,8 +980,8 @@ __global__ __launch_bounds__(T) void k_eager(const uint8_t *__restrict__ U, uint
 
 struct FullOut {
   uint32_t *words;                 // optional: word per position
-  unsigned long long *counts;      // [21][19]
-  unsigned long long *rbe;         // [21][64]
+  unsigned long long *counts;      // [ctr::FULL_NNZ][ctr::FULL_FLAGS]
+  unsigned long long *rbe;         // [ctr::FULL_NNZ][ctr::FULL_RBE]
   unsigned long long *n_success;
   unsigned long long *n_unknown;
   unsigned long long *min_unknown;
@@ -1217,8 +1217,9 @@ __global__ __launch_bounds__(T, SBH_FULL_WGS) void k_full(const uint8_t *__restr
   // (measured and removed: replicas packed as 16-bit counter pairs, a row of 10 words per nnz --
   // the same LDS as 4 unpacked replicas gives 8, halving the lanes that add to one address in one
   // instruction, and a failing position adds once per flag pair, not per flag: A/B 7.53 -> 7.72 ms)
-  constexpr uint32_t RW = 19;  // words per nnz row
-  constexpr uint32_t NREP = SBH_FULL_NREP, REP = 21 * RW + 2;  // (odd stride: replica bases on distinct banks)
+  constexpr uint32_t RW = ctr::FULL_FLAGS;  // words per nnz row
+  // (odd stride: replica bases on distinct banks)
+  constexpr uint32_t NREP = SBH_FULL_NREP, REP = ctr::FULL_NNZ * RW + 2;
   constexpr uint32_t SLOWCAP = 512;
   __shared__ uint4 ldsv[FNV];
   __shared__ uint32_t bname[FBW], bop[FBW];
@@ -1434,7 +1435,7 @@ __global__ __launch_bounds__(T, SBH_FULL_WGS) void k_full(const uint8_t *__restr
   __syncthreads();
   const uint32_t nc = ncl < FCCAP ? ncl : FCCAP;
   if (threadIdx.x == 0) cbase = nc ? atomicAdd(o.close_n, (unsigned long long)nc) : 0;
-  for (uint32_t i = threadIdx.x; i < 21 * 19; i += T) {
+  for (uint32_t i = threadIdx.x; i < ctr::FULL_COUNTS_N; i += T) {
     uint32_t t = 0;
 #pragma unroll
     for (uint32_t r = 0; r < NREP; ++r)
@@ -1972,11 +1973,14 @@ hipError_t launch_eager(const uint8_t *U, uint64_t u_pad, uint64_t begin, uint64
   if (end <= begin) return hipSuccess;
   Segs sg{seg_end, nseg, open_last};
   Ctg c{ctg, nctg};
-  EagerOut o{bits,   counters,     counters + 1, counters + 2, front, defer_pos, counters + 3, defer_cap,
-             xq_pos, counters + 4, xq_cap,       counters + TRUE_SPREAD_OFF, sieve};
+  EagerOut o{bits, counters + ctr::EAGER_TRUE, counters + ctr::EAGER_HALO_N, counters + ctr::EAGER_HALO_FIRST, front,
+             defer_pos, counters + ctr::EAGER_DEFER_N, defer_cap,
+             xq_pos, counters + ctr::EAGER_XQ_N, xq_cap,
+             counters + TRUE_SPREAD_OFF, sieve};
   hipLaunchKernelGGL(k_eager, dim3(ngrid(end - begin, ETILE)), dim3(T), 0, st, U, u_pad, begin, end, sg, c,
                      rtc, o);
-  hipLaunchKernelGGL(k_fold_true, dim3(1), dim3(WAVE), 0, st, counters + TRUE_SPREAD_OFF, counters);
+  hipLaunchKernelGGL(k_fold_true, dim3(1), dim3(WAVE), 0, st, counters + TRUE_SPREAD_OFF,
+                     counters + ctr::EAGER_TRUE);
   return hipGetLastError();
 }
 
@@ -1989,15 +1993,16 @@ hipError_t launch_eager_defer(const uint8_t *U, uint64_t begin, const uint64_t *
   if (cap == 0) return hipSuccess;
   Segs sg{seg_end, nseg, open_last};
   Ctg c{ctg, nctg};
-  EagerOut o{bits, counters, counters + 1, counters + 2, ~0ull, nullptr, nullptr, 0, nullptr, nullptr, 0};
+  EagerOut o{bits, counters + ctr::EAGER_TRUE, counters + ctr::EAGER_HALO_N, counters + ctr::EAGER_HALO_FIRST, ~0ull,
+             nullptr, nullptr, 0, nullptr, nullptr, 0};
   hipLaunchKernelGGL(k_eager_defer, dim3(ngrid(cap, 256)), dim3(256), 0, st, U, begin, sg, c, rtc, defer_pos,
-                     counters + 3, o);
+                     counters + ctr::EAGER_DEFER_N, o);
   return hipGetLastError();
 }
 
 hipError_t launch_full(const uint8_t *U, uint64_t u_pad, uint64_t begin, uint64_t end, const uint64_t *seg_end,
                        uint32_t nseg, uint32_t open_last, const int32_t *ctg, int32_t nctg, int32_t rtc,
-                       uint32_t *words, unsigned long long *counters /* [2+21*19+21*64+2] */,
+                       uint32_t *words, unsigned long long *counters /* [0, ctr::FULL_END) */,
                        uint64_t *close_pos, uint32_t *close_word, uint64_t close_cap, uint32_t *op_words,
                        uint64_t op_cap_words, hipStream_t st) {
   if (end <= begin) return hipSuccess;
@@ -2022,12 +2027,12 @@ hipError_t launch_full(const uint8_t *U, uint64_t u_pad, uint64_t begin, uint64_
   }
   FullOut o;
   o.words = words;
-  o.n_success = counters + 0;
-  o.n_unknown = counters + 1;
-  o.min_unknown = counters + 2;
-  o.close_n = counters + 3;
-  o.counts = counters + 4;
-  o.rbe = counters + 4 + 21 * 19;
+  o.n_success = counters + ctr::FULL_SUCCESS;
+  o.n_unknown = counters + ctr::FULL_UNKNOWN_N;
+  o.min_unknown = counters + ctr::FULL_UNKNOWN_MIN;
+  o.close_n = counters + ctr::FULL_CLOSE_N;
+  o.counts = counters + ctr::FULL_COUNTS;
+  o.rbe = counters + ctr::FULL_COUNTS + ctr::FULL_COUNTS_N;  // (= ctr::FULL_RBE_HIST)
   o.close_pos = close_pos;
   o.close_word = close_word;
   o.close_cap = close_cap;
@@ -2100,8 +2105,8 @@ hipError_t launch_chain_mark(const uint8_t *U, const uint32_t *bits, uint64_t be
   return hipGetLastError();
 }
 
-// The wave-cooperative exact pass over the long-record queue (counters[4] = its device
-// count, counters[5] = the survivors of the lane pre-test in xq_pos[cap, 2 cap)); fixed
+// The wave-cooperative exact pass over the long-record queue (ctr::EAGER_XQ_N = its device
+// count, ctr::EAGER_XQ_LIVE = the survivors of the lane pre-test in xq_pos[cap, 2 cap)); fixed
 // grids stride over the device counts, so no host round trip is needed.  bits: the bitmap
 // from `begin`.  xq_pos holds 2 * cap entries.
 hipError_t launch_eager_xq(const uint8_t *U, uint64_t begin, const uint64_t *seg_end, uint32_t nseg,
@@ -2110,11 +2115,12 @@ hipError_t launch_eager_xq(const uint8_t *U, uint64_t begin, const uint64_t *seg
   if (cap == 0) return hipSuccess;
   Segs sg{seg_end, nseg, open_last};
   Ctg c{ctg, nctg};
-  EagerOut o{bits, counters, counters + 1, counters + 2, ~0ull, nullptr, nullptr, 0, nullptr, nullptr, 0};
-  hipLaunchKernelGGL(k_eager_xq_pre, dim3(512), dim3(256), 0, st, U, sg, xq_pos, counters + 4, cap, xq_pos + cap,
-                     counters + 5);
-  hipLaunchKernelGGL(k_eager_xq, dim3(8192), dim3(256), 0, st, U, begin, sg, c, rtc, xq_pos + cap, counters + 5,
-                     cap, o);
+  EagerOut o{bits, counters + ctr::EAGER_TRUE, counters + ctr::EAGER_HALO_N, counters + ctr::EAGER_HALO_FIRST, ~0ull,
+             nullptr, nullptr, 0, nullptr, nullptr, 0};
+  hipLaunchKernelGGL(k_eager_xq_pre, dim3(512), dim3(256), 0, st, U, sg, xq_pos, counters + ctr::EAGER_XQ_N, cap,
+                     xq_pos + cap, counters + ctr::EAGER_XQ_LIVE);
+  hipLaunchKernelGGL(k_eager_xq, dim3(8192), dim3(256), 0, st, U, begin, sg, c, rtc, xq_pos + cap,
+                     counters + ctr::EAGER_XQ_LIVE, cap, o);
   return hipGetLastError();
 }
 

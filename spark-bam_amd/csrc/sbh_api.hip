@@ -93,7 +93,6 @@ hipError_t launch_chain_walk(const uint8_t *U, uint64_t first, uint64_t E, uint6
 using namespace sbh;
 
 struct StreamCache;  // sbh_run_stream's window shard, buffers and copy stream (kept between calls)
-static void stream_cache_free(StreamCache *sc);
 
 // Threading (include/sparkbam.h): one context serves every thread of its process on its device
 // -- a Spark executor's concurrent tasks share it (jni/Native.scala Device).  What a context holds
@@ -127,23 +126,47 @@ thread_local ErrRec t_err;
 namespace {
 
 template <typename T>
-struct DBuf {  // grow-only device buffer
+struct DBuf {  // grow-only device buffer, freed with its owner (movable, not copyable)
   T *p = nullptr;
   uint64_t cap = 0;
+  bool lent = false;  // p is another buffer's memory (lend): never freed or regrown through this one
+  DBuf() = default;
+  DBuf(const DBuf &) = delete;
+  DBuf &operator=(const DBuf &) = delete;
+  DBuf(DBuf &&o) noexcept : p(o.p), cap(o.cap), lent(o.lent) { o.forget(); }
+  DBuf &operator=(DBuf &&o) noexcept {
+    if (this != &o) {
+      release();
+      p = o.p, cap = o.cap, lent = o.lent;
+      o.forget();
+    }
+    return *this;
+  }
+  ~DBuf() { release(); }
   hipError_t ensure(uint64_t n) {
     if (n <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
+    if (lent) return hipErrorInvalidValue;  // (the lender sizes its memory)
+    release();
     hipError_t e = hipMalloc(reinterpret_cast<void **>(&p), std::max<uint64_t>(n, 1) * sizeof(T));
     if (e == hipSuccess) cap = n;
     return e;
   }
+  // frees now what the destructor would free later (a lent pointer is only dropped)
   void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
+    if (p && !lent) (void)hipFree(p);
+    forget();
   }
+  // borrow q[0, c) from its owner, which must outlive the loan; unlend() ends it
+  void lend(T *q, uint64_t c) {
+    release();
+    p = q, cap = c, lent = true;
+  }
+  void unlend() {
+    if (lent) forget();
+  }
+
+ private:
+  void forget() { p = nullptr, cap = 0, lent = false; }
 };
 
 }  // namespace
@@ -237,16 +260,6 @@ struct sbh_shard {
     sbh_records_sizes sz{};
     bool valid = false;
     bool decoded = false;  // the columns were decoded (else only the starts, sbh_split_records decode = 0)
-    void release() {
-      for (auto *b : {&pos, &wcnt, &wpre, &nm, &cg, &sq, &ax, &nmo, &cgo, &sqo, &axo, &keep, &kpre, &pos2, &vpos,
-                      &bt_in, &bt_rbase, &bt_cnt, &bt_off})
-        b->release();
-      iv_b.release(); iv_e.release(); iv_ref.release();
-      for (auto *b : {&ref_id, &p0, &nref, &npos, &tlen}) b->release();
-      flag.release(); bin.release(); mapq.release(); qual.release(); aux.release();
-      names.release(); seq.release(); cigar.release();
-      valid = false;
-    }
   } rec;
   // BAI construction (sbh_bai_scan / fetch): per-record keys, windows, starts, the scan's input and
   // prefix, the runs and the linear-index minima of the last scan
@@ -257,11 +270,6 @@ struct sbh_shard {
     int32_t edges[4] = {-1, 0, -1, 0};
     bool valid = false;
     bool off_ok = false;  // lin_off holds the window prefix of the current contig lengths
-    void release() {
-      for (auto *b : {&pos, &key, &win, &vbeg, &flg, &pre, &ridx, &lin, &lin_off, &aux}) b->release();
-      runs.release();
-      valid = off_ok = false;
-    }
   } bai;
   // SAM text of the last decoded scan (sbh_records_sam_scan / fetch): per-row line lengths and
   // their prefix, the host-row flags and their prefix, the text; the reference names; the host
@@ -274,11 +282,6 @@ struct sbh_shard {
     std::vector<char> h_text;
     sbh_sam_sizes sz{};
     bool valid = false;
-    void release() {
-      for (auto *b : {&len, &off, &hostf, &hpre, &rows, &rbytes, &goff, &ref_off}) b->release();
-      text.release(); refs.release(); gbuf.release();
-      valid = false;
-    }
   } sam;
   std::vector<int32_t> h_ctg;  // host copy of the contig lengths (sbh_set_contigs)
   // batched splits (sbh_split_starts) and check-bam truth (sbh_check_records)
@@ -312,31 +315,53 @@ struct sbh_shard {
   DevBlocks dev_blocks() {
     return DevBlocks{b_cstart.p, b_csize.p, b_hsize.p, b_usize.p, b_ustart.p, b_flags.p, b_status.p, b_ntok.p};
   }
+
+  // What is not a DBuf is let go here; the DBuf members (and rec, bai, sam) free themselves after
+  // this body, in their own destructors -- that is, after the streams below are gone.  That order
+  // is sound only because the shard's stream is synchronised first (every entry point joins the
+  // other streams into it before it returns), so nothing on the device still uses the memory;
+  // the extra streams are drained as well for a call that failed between its launches.
+  ~sbh_shard() {
+    if (pf_active) (void)shard_prefetch_finish(this, false);  // (joins the copy threads)
+    if (ctx) (void)hipSetDevice(ctx->device);
+    (void)hipStreamSynchronize(st);
+    for (hipEvent_t e : pf_ev) (void)hipEventDestroy(e);
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : pev)
+      if (e) (void)hipEventDestroy(e);
+    for (hipStream_t s : pf_stream) (void)hipStreamDestroy(s);
+    for (hipStream_t s : {s_lz, s_eg, cs})
+      if (s) {
+        (void)hipStreamSynchronize(s);
+        (void)hipStreamDestroy(s);
+      }
+    for (uint8_t *q : pf_pin) (void)hipHostFree(q);
+    if (sp_pin) (void)hipHostFree(sp_pin);
+    if (h_ctr) (void)hipHostFree(h_ctr);
+    if (own_st && st) (void)hipStreamDestroy(st);
+  }
 };
 
 struct StreamCache {
-  sbh_shard *sh = nullptr;
+  sbh_shard *sh = nullptr;  // the window shard: its comp is lent one of buf[] while a call runs
   DBuf<uint8_t> buf[2];
   hipStream_t cs = nullptr;
   hipEvent_t done[2] = {nullptr, nullptr}, c0[2] = {nullptr, nullptr};
+  // (the caller has set the device; buf[] free themselves after the copy stream has drained)
+  ~StreamCache() {
+    if (cs) (void)hipStreamSynchronize(cs);
+    if (sh) {
+      sh->comp.unlend();
+      delete sh;
+    }
+    for (int i = 0; i < 2; ++i) {
+      if (done[i]) (void)hipEventDestroy(done[i]);
+      if (c0[i]) (void)hipEventDestroy(c0[i]);
+    }
+    if (cs) (void)hipStreamDestroy(cs);
+  }
 };
-
-static void stream_cache_free(StreamCache *sc) {
-  if (sc->cs) (void)hipStreamSynchronize(sc->cs);
-  if (sc->sh) {
-    sc->sh->comp.p = nullptr;
-    sc->sh->comp.cap = 0;
-    sbh_shard_destroy(sc->sh);
-  }
-  sc->buf[0].release();
-  sc->buf[1].release();
-  for (int i = 0; i < 2; ++i) {
-    if (sc->done[i]) (void)hipEventDestroy(sc->done[i]);
-    if (sc->c0[i]) (void)hipEventDestroy(sc->c0[i]);
-  }
-  if (sc->cs) (void)hipStreamDestroy(sc->cs);
-  delete sc;
-}
 
 static int vfail(sbh_ctx *ctx, int code, std::initializer_list<int64_t> fields, const char *fmt, va_list ap) {
   if (ctx) {
@@ -391,6 +416,23 @@ static int set_device(sbh_ctx *ctx) {
   return SBH_OK;
 }
 
+// The shard's resident bytes are now [file_off, file_off + n) of the file (sbh_shard_load, a
+// prefetched window taken into use): every state derived from the old bytes is void.
+static void resident_changed(sbh_shard *sh, uint64_t file_off, uint64_t n) {
+  sh->file_off = file_off;
+  sh->n = n;
+  sh->at_eof = file_off + n == sh->file_size;
+  sh->sieve_nref1 = 0;
+  sh->indexed = sh->inflated = sh->bits_valid = sh->chain_ok = sh->cm_valid = false;
+  sh->rec.valid = false;
+  sh->bai.valid = false;
+  sh->sam.valid = false;
+  sh->ncand = 0;
+  sh->scan_from = ~0ull;
+  sh->hb.clear();
+  sh->nblocks = sh->utotal = 0;
+}
+
 extern "C" {
 
 static int records_positions(sbh_shard *sh, uint64_t first, uint64_t E, uint64_t total, uint64_t n, int32_t anomalies,
@@ -437,7 +479,7 @@ int sbh_ctx_destroy(sbh_ctx *ctx) {
   if (!ctx) return SBH_OK;
   if (!ctx->sc_free.empty()) {
     (void)hipSetDevice(ctx->device);
-    for (StreamCache *sc : ctx->sc_free) stream_cache_free(sc);
+    for (StreamCache *sc : ctx->sc_free) delete sc;
     ctx->sc_free.clear();
   }
   if (ctx->own_stream && ctx->stream) {
@@ -515,7 +557,10 @@ int sbh_shard_create(sbh_ctx *ctx, const void *src, uint64_t n, uint64_t file_of
     }
     sh->own_st = true;
   } else {
-    sh->st = sh->st;
+    // The caller gave the context a stream (sbh_ctx_set_stream), and sparkbam.h says the shard
+    // then enqueues on it.  It does not: the shard runs on the null stream (the line here used
+    // to read `sh->st = sh->st`).  Kept as it behaves; DESIGN.md lists it as an open item.
+    sh->st = nullptr;
   }
   sh->file_off = file_offset;
   sh->n = n;
@@ -540,50 +585,7 @@ int sbh_shard_create(sbh_ctx *ctx, const void *src, uint64_t n, uint64_t file_of
 }
 
 int sbh_shard_destroy(sbh_shard *sh) {
-  if (!sh) return SBH_OK;
-  if (sh->pf_active) (void)shard_prefetch_finish(sh, false);
-  (void)hipSetDevice(sh->ctx->device);
-  (void)hipStreamSynchronize(sh->st);
-  sh->comp.release();
-  sh->b_cstart.release(); sh->b_ustart.release(); sh->usz.release(); sh->blkpack.release();
-  sh->b_csize.release(); sh->b_hsize.release(); sh->b_usize.release(); sh->b_flags.release();
-  sh->b_status.release();
-  sh->b_ntok.release();
-  sh->tok.release();
-  sh->counts.release(); sh->cfirst.release(); sh->offs.release(); sh->cand.release(); sh->v.release(); sh->rank.release();
-  sh->tmp.release(); sh->J0.release(); sh->J1.release(); sh->on.release(); sh->d_seg.release();
-  sh->U.release(); sh->u_pad_clean = ~0ull; sh->ctg.release(); sh->bits.release(); sh->words.release(); sh->close_pos.release();
-  sh->close_word.release(); sh->ctr.release(); sh->opix.release(); sh->sieve.release();
-  sh->cc.release();
-  sh->comp2.release(); sh->aux2.release();
-  for (hipStream_t st : sh->pf_stream) (void)hipStreamDestroy(st);
-  for (uint8_t *p : sh->pf_pin) (void)hipHostFree(p);
-  for (hipEvent_t e : sh->pf_ev) (void)hipEventDestroy(e);
-  for (hipEvent_t &e : sh->ev)
-    if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t &e : sh->pev)
-    if (e) (void)hipEventDestroy(e);
-  if (sh->s_lz) (void)hipStreamDestroy(sh->s_lz);
-  if (sh->s_eg) (void)hipStreamDestroy(sh->s_eg);
-  if (sh->cs) (void)hipStreamDestroy(sh->cs);
-  sh->defer.release();
-  sh->xq.release();
-  sh->rec.release();
-  sh->bai.release();
-  sh->sam.release();
-  for (auto *b : {&sh->sp_start, &sh->sp_end, &sh->sp_first, &sh->sp_E, &sh->sp_vpos, &sh->t_rb, &sh->t_re,
-                  &sh->t_fp, &sh->t_fn})
-    b->release();
-  sh->sp_code.release();
-  sh->sp_count.release();
-  sh->sp_pack.release();
-  if (sh->sp_pin) (void)hipHostFree(sh->sp_pin);
-  sh->tbits.release();
-  sh->cm_pos.release(); sh->cm_wcnt.release(); sh->cm_wpre.release(); sh->cm_mark.release(); sh->cm_mpre.release();
-  sh->cm_j.release(); sh->cm_j2.release(); sh->cm_j0.release();
-  if (sh->h_ctr) (void)hipHostFree(sh->h_ctr);
-  if (sh->own_st && sh->st) (void)hipStreamDestroy(sh->st);
-  delete sh;
+  delete sh;  // (~sbh_shard; a null shard is fine)
   return SBH_OK;
 }
 
@@ -611,18 +613,7 @@ int sbh_shard_load(sbh_shard *sh, const void *src, uint64_t n, uint64_t file_off
   if (cs != sh->st) HIPCHK(ctx, hipStreamSynchronize(cs));
   HIPCHK(ctx, hipMemsetAsync(sh->comp.p + n, 0, sh->pad, sh->st));
   HIPCHK(ctx, hipStreamSynchronize(sh->st));
-  sh->file_off = file_offset;
-  sh->n = n;
-  sh->at_eof = file_offset + n == sh->file_size;
-  sh->sieve_nref1 = 0;
-  sh->indexed = sh->inflated = sh->bits_valid = sh->chain_ok = sh->cm_valid = false;
-  sh->rec.valid = false;
-  sh->bai.valid = false;
-  sh->sam.valid = false;
-  sh->ncand = 0;
-  sh->scan_from = ~0ull;
-  sh->hb.clear();
-  sh->nblocks = sh->utotal = 0;
+  resident_changed(sh, file_offset, n);
   return SBH_OK;
 }
 
@@ -751,18 +742,7 @@ int shard_prefetch_finish(sbh_shard *sh, bool use, double *copy_ms) {
   HIPCHK(ctx, hipStreamSynchronize(sh->st));  // (no kernel may still read the old bytes)
   std::swap(sh->comp, sh->comp2);
   std::swap(sh->sp_vpos, sh->aux2);
-  sh->file_off = sh->pf_off;
-  sh->n = sh->pf_n;
-  sh->at_eof = sh->file_off + sh->n == sh->file_size;
-  sh->sieve_nref1 = 0;
-  sh->indexed = sh->inflated = sh->bits_valid = sh->chain_ok = sh->cm_valid = false;
-  sh->rec.valid = false;
-  sh->bai.valid = false;
-  sh->sam.valid = false;
-  sh->ncand = 0;
-  sh->scan_from = ~0ull;
-  sh->hb.clear();
-  sh->nblocks = sh->utotal = 0;
+  resident_changed(sh, sh->pf_off, sh->pf_n);
   return SBH_OK;
 }
 
@@ -779,12 +759,12 @@ int sbh_find_block_start(sbh_shard *sh, uint64_t start, int32_t k, uint64_t *out
   int rc = set_device(ctx);
   if (rc) return rc;
   const uint64_t rel = start - sh->file_off;
-  unsigned long long *best = sh->ctr.p;
+  unsigned long long *best = sh->ctr.p + ctr::FBS_BEST;
   HIPCHK(ctx, hipMemsetAsync(best, 0xff, 8, sh->st));
   HIPCHK(ctx, launch_find_block_start(sh->comp.p, sh->n, rel, k, sh->at_eof ? 1 : 0, best, sh->st));
-  HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr, best, 8, hipMemcpyDeviceToHost, sh->st));
+  HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::FBS_BEST, best, 8, hipMemcpyDeviceToHost, sh->st));
   HIPCHK(ctx, hipStreamSynchronize(sh->st));
-  const unsigned long long b = sh->h_ctr[0];
+  const unsigned long long b = sh->h_ctr[ctr::FBS_BEST];
   // HeaderSearchFailedException(path, start, positionsAttempted): the search tried every
   // pos < MAX_BLOCK_SIZE (FindBlockStart.scala:18-35)
   if (b == ~0ull)
@@ -819,7 +799,7 @@ int sbh_index(sbh_shard *sh, uint64_t start, uint64_t *n_blocks, uint64_t *flat_
   const uint64_t n = sh->n;
   const uint64_t srel = sh->scan_from >= sh->file_off && sh->scan_from <= start ? sh->scan_from - sh->file_off : 0;
   // the start must itself be a header (its 18 bytes come back with the candidate count)
-  uint8_t *h18 = reinterpret_cast<uint8_t *>(sh->h_ctr + 512);  // pinned
+  uint8_t *h18 = reinterpret_cast<uint8_t *>(sh->h_ctr + ctr::H_INDEX_HDR18);  // pinned
   auto start_is_header = [&]() -> int {
     if (sbh_header_make(h18, 18, nullptr, nullptr) != SBH_OK) {
       // HeaderParseException(idx, actual, expected): the first byte Header.make's checks
@@ -849,16 +829,16 @@ int sbh_index(sbh_shard *sh, uint64_t start, uint64_t *n_blocks, uint64_t *flat_
     HIPCHK(ctx, sh->tmp.ensure(scan_tmp_words(nchunks + 1) + scan_tmp_words(1 << 24)));
     HIPCHK(ctx, launch_cand_count(sh->comp.p, n, srel, sh->counts.p, sh->cfirst.p, nchunks, st));
     HIPCHK(ctx, scan_exclusive_u64(sh->counts.p, sh->offs.p, nchunks + 1, sh->tmp.p, st));
-    HIPCHK(ctx, hipMemcpyAsync(&sh->h_ctr[0], sh->offs.p + nchunks, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::H_INDEX_NCAND, sh->offs.p + nchunks, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
     if ((rc = start_is_header()) != SBH_OK) return rc;
-    nc = sh->h_ctr[0];
+    nc = sh->h_ctr[ctr::H_INDEX_NCAND];
   }
   uint64_t nchain = 0;
   // the 18 bytes after the last chain block (the next header, checked below), written by
   // k_chain_emit and copied back with the block table
   uint8_t *next18_dev = reinterpret_cast<uint8_t *>(sh->ctr.p + CTR_NEXT18);
-  uint8_t *nx = reinterpret_cast<uint8_t *>(sh->h_ctr + 516);  // pinned
+  uint8_t *nx = reinterpret_cast<uint8_t *>(sh->h_ctr + ctr::H_INDEX_NEXT18);  // pinned
   if (nc) {
     HIPCHK(ctx, sh->cand.ensure(nc));
     HIPCHK(ctx, sh->J0.ensure(nc));
@@ -963,24 +943,23 @@ int sbh_get_blocks(sbh_shard *sh, uint64_t first, uint64_t count, sbh_block *out
 // After the inflate kernels on `st`: the first block whose status is not INF_OK decides the
 // error (the reference's exception for that block); 8 bytes come back, not every status.
 // `extra`/`extra_dst`/`extra_n` ride along in the same round trip.
-// whole_ctr: the caller set ctr[0, CTR_RUN_WORDS) from ctr_run_template (fb = ~0 included), and
+// whole_ctr: the caller set ctr[0, CTR_RUN_WORDS) from the run template (fb = ~0 included), and
 // those words all come back to h_ctr in one copy (the eager counters, the step tail's answers)
-constexpr uint32_t CTR_RUN_WORDS = 101;
 static int inflate_status(sbh_shard *sh, hipStream_t st, uint64_t *bad_block, const void *extra = nullptr,
                           void *extra_dst = nullptr, size_t extra_n = 0, bool whole_ctr = false) {
   sbh_ctx *ctx = sh->ctx;
-  unsigned long long *fb = sh->ctr.p + 100;
+  unsigned long long *fb = sh->ctr.p + ctr::FIRST_BAD;
   HIPCHK(ctx, launch_first_bad(sh->b_status.p, sh->nblocks, fb, st, !whole_ctr));
   if (whole_ctr) {
     HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr, sh->ctr.p, CTR_RUN_WORDS * 8, hipMemcpyDeviceToHost, st));
   } else {
-    HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + 100, fb, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::FIRST_BAD, fb, 8, hipMemcpyDeviceToHost, st));
     if (extra_n) HIPCHK(ctx, hipMemcpyAsync(extra_dst, extra, extra_n, hipMemcpyDeviceToHost, st));
   }
   HIPCHK(ctx, hipStreamSynchronize(st));
-  const uint64_t i = sh->h_ctr[100];
+  const uint64_t i = sh->h_ctr[ctr::FIRST_BAD];
   if (i == ~0ull) return SBH_OK;
-  uint32_t *hs = reinterpret_cast<uint32_t *>(sh->h_ctr + 101);
+  uint32_t *hs = reinterpret_cast<uint32_t *>(sh->h_ctr + ctr::H_BAD_STATUS);
   HIPCHK(ctx, hipMemcpyAsync(hs, sh->b_status.p + i, 4, hipMemcpyDeviceToHost, st));
   HIPCHK(ctx, hipStreamSynchronize(st));
   if (bad_block) *bad_block = i;
@@ -1109,14 +1088,15 @@ int sbh_verify_crc(sbh_shard *sh, uint64_t *n_bad, uint64_t *first_bad) {
   int rc = set_device(ctx);
   if (rc) return rc;
   hipStream_t st = sh->st;
-  unsigned long long *c = sh->ctr.p + 32;
-  HIPCHK(ctx, hipMemsetAsync(c, 0, 8, st));
-  HIPCHK(ctx, hipMemsetAsync(c + 1, 0xff, 8, st));
-  HIPCHK(ctx, launch_block_crc(sh->comp.p, sh->dev_blocks(), sh->nblocks, sh->U.p, c, c + 1, st));
-  HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + 32, c, 16, hipMemcpyDeviceToHost, st));
+  unsigned long long *nbad = sh->ctr.p + ctr::CRC_BAD_N, *fbad = sh->ctr.p + ctr::CRC_FIRST_BAD;
+  HIPCHK(ctx, hipMemsetAsync(nbad, 0, 8, st));
+  HIPCHK(ctx, hipMemsetAsync(fbad, 0xff, 8, st));
+  HIPCHK(ctx, launch_block_crc(sh->comp.p, sh->dev_blocks(), sh->nblocks, sh->U.p, nbad, fbad, st));
+  // (CRC_BAD_N and CRC_FIRST_BAD)
+  HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::CRC_BAD_N, nbad, 2 * 8, hipMemcpyDeviceToHost, st));
   HIPCHK(ctx, hipStreamSynchronize(st));
-  *n_bad = sh->h_ctr[32];
-  if (first_bad) *first_bad = sh->h_ctr[32] ? sh->hb[sh->h_ctr[33]].start : 0;
+  *n_bad = sh->h_ctr[ctr::CRC_BAD_N];
+  if (first_bad) *first_bad = sh->h_ctr[ctr::CRC_BAD_N] ? sh->hb[sh->h_ctr[ctr::CRC_FIRST_BAD]].start : 0;
   return SBH_OK;
 }
 
@@ -1259,8 +1239,8 @@ static int eager_range(sbh_shard *sh, uint64_t begin, uint64_t end, int32_t rtc,
   HIPCHK(ctx, sh->bits.ensure(nwords + 1));
   HIPCHK(ctx, sh->xq.ensure(2 * XQ_CAP_MAX));
   unsigned long long *c = sh->ctr.p;
-  HIPCHK(ctx, hipMemsetAsync(c, 0, 48, st));
-  HIPCHK(ctx, hipMemsetAsync(c + 2, 0xff, 8, st));
+  HIPCHK(ctx, hipMemsetAsync(c + ctr::EAGER_TRUE, 0, ctr::EAGER_END * 8, st));
+  HIPCHK(ctx, hipMemsetAsync(c + ctr::EAGER_HALO_FIRST, 0xff, 8, st));
   mark(sh, 4);
   HIPCHK(ctx, launch_eager(sh->U.p, sh->utotal + sh->pad, begin, end, sh->d_seg.p, (uint32_t)sh->seg_end.size(),
                            sh->open_last ? 1 : 0, sh->ctg.p, sh->nctg, rtc, sh->bits.p, c, st, ~0ull, nullptr, 0,
@@ -1269,17 +1249,19 @@ static int eager_range(sbh_shard *sh, uint64_t begin, uint64_t end, int32_t rtc,
   HIPCHK(ctx, launch_eager_xq(sh->U.p, begin, sh->d_seg.p, (uint32_t)sh->seg_end.size(), sh->open_last ? 1 : 0,
                               sh->ctg.p, sh->nctg, rtc, sh->bits.p, c, sh->xq.p, xq_cap(), st));
   mark(sh, 5);
-  HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr, c, 24, hipMemcpyDeviceToHost, st));
+  // (the true count and the two need-halo words)
+  HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::EAGER_TRUE, c + ctr::EAGER_TRUE, (ctr::EAGER_HALO_FIRST + 1) * 8,
+                             hipMemcpyDeviceToHost, st));
   HIPCHK(ctx, hipStreamSynchronize(st));
   sh->bits_valid = true;
   sh->bits_begin = begin;
   sh->bits_end = end;
   sh->bits_rtc = rtc;
-  if (n_true) *n_true = sh->h_ctr[0];
-  if (sh->h_ctr[1]) {
+  if (n_true) *n_true = sh->h_ctr[ctr::EAGER_TRUE];
+  if (sh->h_ctr[ctr::EAGER_HALO_N]) {
     sh->bits_valid = false;
     return fail(ctx, SBH_E_NEED_HALO, "%llu positions (first %llu) need bytes past the shard",
-                sh->h_ctr[1], sh->h_ctr[2]);
+                sh->h_ctr[ctr::EAGER_HALO_N], sh->h_ctr[ctr::EAGER_HALO_FIRST]);
   }
   return SBH_OK;
 }
@@ -1325,10 +1307,10 @@ int sbh_check_full(sbh_shard *sh, uint64_t begin, uint64_t end, int32_t rtc, uin
   if (rc) return rc;
   sbh_ctx *ctx = sh->ctx;
   hipStream_t st = sh->st;
-  const uint64_t nctr = 4 + 21 * 19 + 21 * 64;
+  const uint64_t nctr = ctr::FULL_END;
   unsigned long long *c = sh->ctr.p;
   HIPCHK(ctx, hipMemsetAsync(c, 0, nctr * 8, st));
-  HIPCHK(ctx, hipMemsetAsync(c + 2, 0xff, 8, st));
+  HIPCHK(ctx, hipMemsetAsync(c + ctr::FULL_UNKNOWN_MIN, 0xff, 8, st));
   uint32_t *words = nullptr;
   if (out_words) {
     HIPCHK(ctx, sh->words.ensure(end - begin + 1));
@@ -1348,14 +1330,14 @@ int sbh_check_full(sbh_shard *sh, uint64_t begin, uint64_t end, int32_t rtc, uin
                           sh->close_word.p, cap, sh->opix.p, sh->opix.cap, st));
   HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr, c, nctr * 8, hipMemcpyDeviceToHost, st));
   HIPCHK(ctx, hipStreamSynchronize(st));
-  if (sh->h_ctr[1])
-    return fail(ctx, SBH_E_NEED_HALO, "%llu positions (first %llu) need bytes past the shard", sh->h_ctr[1],
-                sh->h_ctr[2]);
-  if (n_success) *n_success = sh->h_ctr[0];
-  const uint64_t nclose = sh->h_ctr[3];
+  if (sh->h_ctr[ctr::FULL_UNKNOWN_N])
+    return fail(ctx, SBH_E_NEED_HALO, "%llu positions (first %llu) need bytes past the shard",
+                sh->h_ctr[ctr::FULL_UNKNOWN_N], sh->h_ctr[ctr::FULL_UNKNOWN_MIN]);
+  if (n_success) *n_success = sh->h_ctr[ctr::FULL_SUCCESS];
+  const uint64_t nclose = sh->h_ctr[ctr::FULL_CLOSE_N];
   if (n_close) *n_close = nclose;
-  if (counts) for (int i = 0; i < 21 * 19; ++i) counts[i] = sh->h_ctr[4 + i];
-  if (rbe_hist) for (int i = 0; i < 21 * 64; ++i) rbe_hist[i] = sh->h_ctr[4 + 21 * 19 + i];
+  if (counts) for (int i = 0; i < (int)ctr::FULL_COUNTS_N; ++i) counts[i] = sh->h_ctr[ctr::FULL_COUNTS + i];
+  if (rbe_hist) for (int i = 0; i < (int)ctr::FULL_RBE_N; ++i) rbe_hist[i] = sh->h_ctr[ctr::FULL_RBE_HIST + i];
   const uint64_t ncopy = std::min<uint64_t>(nclose, cap);
   if (ncopy && (close_flat || close_word)) {
     // positions arrive in atomic order: sort them on the host
@@ -1413,31 +1395,31 @@ int sbh_find_record_start(sbh_shard *sh, uint64_t from, int32_t rtc, int32_t max
       rc = eager_range(sh, lo, hi, rtc, nullptr);
       if (rc == SBH_E_NEED_HALO) {
         // unknowns are fine only if a true position precedes the first unknown
-        const uint64_t first_unknown = sh->h_ctr[2];
-        unsigned long long *best = sh->ctr.p + 8;
+        const uint64_t first_unknown = sh->h_ctr[ctr::EAGER_HALO_FIRST];
+        unsigned long long *best = sh->ctr.p + ctr::FRS_BEST;
         HIPCHK(ctx, hipMemsetAsync(best, 0xff, 8, st));
         sh->bits_valid = true;
         HIPCHK(ctx, launch_first_set(sh->bits.p, lo, lo, first_unknown, best, st));
-        HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + 8, best, 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::FRS_BEST, best, 8, hipMemcpyDeviceToHost, st));
         HIPCHK(ctx, hipStreamSynchronize(st));
         sh->bits_valid = false;
-        if (sh->h_ctr[8] != ~0ull) {
-          *out_flat = sh->h_ctr[8];
-          if (out_delta) *out_delta = (int32_t)(sh->h_ctr[8] - from);
+        if (sh->h_ctr[ctr::FRS_BEST] != ~0ull) {
+          *out_flat = sh->h_ctr[ctr::FRS_BEST];
+          if (out_delta) *out_delta = (int32_t)(sh->h_ctr[ctr::FRS_BEST] - from);
           return SBH_OK;
         }
         return rc;
       }
       if (rc) return rc;
     }
-    unsigned long long *best = sh->ctr.p + 8;
+    unsigned long long *best = sh->ctr.p + ctr::FRS_BEST;
     HIPCHK(ctx, hipMemsetAsync(best, 0xff, 8, st));
     HIPCHK(ctx, launch_first_set(sh->bits.p, sh->bits_begin, lo, hi, best, st));
-    HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + 8, best, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::FRS_BEST, best, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
-    if (sh->h_ctr[8] != ~0ull) {
-      *out_flat = sh->h_ctr[8];
-      if (out_delta) *out_delta = (int32_t)(sh->h_ctr[8] - from);
+    if (sh->h_ctr[ctr::FRS_BEST] != ~0ull) {
+      *out_flat = sh->h_ctr[ctr::FRS_BEST];
+      if (out_delta) *out_delta = (int32_t)(sh->h_ctr[ctr::FRS_BEST] - from);
       return SBH_OK;
     }
     lo = hi;
@@ -1453,8 +1435,8 @@ int sbh_find_record_start(sbh_shard *sh, uint64_t from, int32_t rtc, int32_t max
 // the stream end) -- what the next shard's first record must equal when stitching.
 
 // `known`: the four chain-proof counters (anomalies, first anomaly, set bits, exit) that a
-// k_verify_chain_w launch over this same [first, E) and bitmap already left in h_ctr[16..19]
-// (sbh_run_shard's tail): the proof is not run again.
+// k_verify_chain_w launch over this same [first, E) and bitmap already left in
+// h_ctr[ctr::PROOF_ANOM, ctr::PROOF_END) (sbh_run_shard's tail): the proof is not run again.
 static int count_records_impl(sbh_shard *sh, uint64_t first, uint64_t E, uint64_t *count, int32_t *anomalies,
                               uint64_t *exit_flat = nullptr, bool known = false) {
   sbh_ctx *ctx = sh->ctx;
@@ -1469,48 +1451,49 @@ static int count_records_impl(sbh_shard *sh, uint64_t first, uint64_t E, uint64_
     if (exit_flat) *exit_flat = first;
     return SBH_OK;
   }
-  unsigned long long *c = sh->ctr.p + 16;
+  unsigned long long *c = sh->ctr.p;
   const bool covered = sh->bits_valid && sh->bits_begin <= first && E <= sh->bits_end;
   if (covered) {
-    // counters c[0..3]: anomalies, first anomaly, set bits in [first, E), chain exit
-    unsigned long long *init = sh->h_ctr + 600;  // pinned
+    // the proof counters: anomalies, first anomaly, set bits in [first, E), chain exit
+    unsigned long long *init = sh->h_ctr + ctr::H_PROOF_INIT;  // pinned
     init[0] = 0;
     init[1] = ~0ull;
     init[2] = 0;
     init[3] = ~0ull;
     if (!known) {
-      HIPCHK(ctx, hipMemcpyAsync(c, init, 32, hipMemcpyHostToDevice, st));
+      HIPCHK(ctx, hipMemcpyAsync(c + ctr::PROOF_ANOM, init, 4 * 8, hipMemcpyHostToDevice, st));
       HIPCHK(ctx, sh->cc.ensure((sh->bits_end - sh->bits_begin + 31) / 32 / VC_CHUNK + 2));
       // verify bitmap == chain and count the set bits in one pass (k_verify_chain_w: wave-
       // cooperative successors, so sparse bitmaps of long records cost no word-by-word scans)
-      HIPCHK(ctx, launch_verify_chain_count(sh->U.p, sh->bits.p, sh->bits_begin, sh->bits_end, first, E, total, c,
-                                            c + 1, c + 3, c + 2, st, nullptr,
-                                            sh->cc.p));
-      HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + 16, c, 32, hipMemcpyDeviceToHost, st));
+      HIPCHK(ctx, launch_verify_chain_count(sh->U.p, sh->bits.p, sh->bits_begin, sh->bits_end, first, E, total,
+                                            c + ctr::PROOF_ANOM, c + ctr::PROOF_FIRST_ANOM, c + ctr::PROOF_EXIT,
+                                            c + ctr::PROOF_SET, st, nullptr, sh->cc.p));
+      HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::PROOF_ANOM, c + ctr::PROOF_ANOM, 4 * 8, hipMemcpyDeviceToHost, st));
       // The proof walks the set bits of [first, E), and `first` need not be one of them: a caller's
       // record start (a BAI chunk, a stitched exit) that the eager checker rejects.  Set bits
       // further on that chain among themselves are then a suffix of the chain, not the chain,
       // so first's own bit comes back with the counters and a clear one is an anomaly at `first`.
       const uint64_t fbit = first - sh->bits_begin;
-      sh->h_ctr[604] = 0;
-      HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + 604, sh->bits.p + fbit / 32, 4, hipMemcpyDeviceToHost, st));
+      sh->h_ctr[ctr::H_PROOF_FIRST_WORD] = 0;
+      HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::H_PROOF_FIRST_WORD, sh->bits.p + fbit / 32, 4, hipMemcpyDeviceToHost,
+                                 st));
       HIPCHK(ctx, hipStreamSynchronize(st));
-      if (!((sh->h_ctr[604] >> (fbit & 31)) & 1)) {
-        ++sh->h_ctr[16];
-        sh->h_ctr[17] = std::min<uint64_t>(sh->h_ctr[17], first);
+      if (!((sh->h_ctr[ctr::H_PROOF_FIRST_WORD] >> (fbit & 31)) & 1)) {
+        ++sh->h_ctr[ctr::PROOF_ANOM];
+        sh->h_ctr[ctr::PROOF_FIRST_ANOM] = std::min<uint64_t>(sh->h_ctr[ctr::PROOF_FIRST_ANOM], first);
       }
     }
-    const uint64_t n = sh->h_ctr[18];
-    if (sh->h_ctr[16] == 0 && sh->h_ctr[19] != ~0ull) {
+    const uint64_t n = sh->h_ctr[ctr::PROOF_SET];
+    if (sh->h_ctr[ctr::PROOF_ANOM] == 0 && sh->h_ctr[ctr::PROOF_EXIT] != ~0ull) {
       sh->chain_ok = true;
       sh->cc_ok = true;  // (this proof's chunk counts, or the run's tail proof's over the same range)
       sh->chain_first = first;
       sh->chain_E = E;
       *count = n;
-      if (exit_flat) *exit_flat = sh->h_ctr[19];
+      if (exit_flat) *exit_flat = sh->h_ctr[ctr::PROOF_EXIT];
       return SBH_OK;
     }
-    if (anomalies) *anomalies = (int32_t)std::min<uint64_t>(sh->h_ctr[16], INT32_MAX);
+    if (anomalies) *anomalies = (int32_t)std::min<uint64_t>(sh->h_ctr[ctr::PROOF_ANOM], INT32_MAX);
     // the bitmap is not exactly the chain (false positives / rejected chain records): mark
     // the chain through the set bits by pointer doubling; the exact walk only when the
     // chain leaves the set bits
@@ -1527,35 +1510,36 @@ static int count_records_impl(sbh_shard *sh, uint64_t first, uint64_t E, uint64_
       HIPCHK(ctx, sh->tmp.ensure(std::max(scan_tmp_words(nw), scan_tmp_words(n + 1))));
       HIPCHK(ctx, launch_rec_positions_bits(sh->bits.p, sh->bits_begin, first, E, sh->cm_wcnt.p, sh->cm_wpre.p,
                                             sh->tmp.p, sh->cm_pos.p, st));
-      HIPCHK(ctx, hipMemsetAsync(c + 6, 0xff, 8, st));
-      uint32_t *code = reinterpret_cast<uint32_t *>(sh->h_ctr + 22);
+      HIPCHK(ctx, hipMemsetAsync(c + ctr::MARK_EXIT, 0xff, 8, st));
+      uint32_t *code = reinterpret_cast<uint32_t *>(sh->h_ctr + ctr::H_MARK_CODE);
       HIPCHK(ctx, launch_chain_mark(sh->U.p, sh->bits.p, sh->bits_begin, first, E, total, sh->cm_pos.p,
-                                    sh->cm_wpre.p, n, sh->cm_j.p, sh->cm_j2.p, sh->cm_j0.p, sh->cm_mark.p, c + 6,
-                                    code, st));
+                                    sh->cm_wpre.p, n, sh->cm_j.p, sh->cm_j2.p, sh->cm_j0.p, sh->cm_mark.p,
+                                    c + ctr::MARK_EXIT, code, st));
       HIPCHK(ctx, hipMemsetAsync(sh->cm_mark.p + n, 0, 8, st));
       HIPCHK(ctx, scan_exclusive_u64(sh->cm_mark.p, sh->cm_mpre.p, n + 1, sh->tmp.p, st));
-      HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + 23, sh->cm_mpre.p + n, 8, hipMemcpyDeviceToHost, st));
-      HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + 24, sh->cm_pos.p, 8, hipMemcpyDeviceToHost, st));
-      HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + 25, c + 6, 8, hipMemcpyDeviceToHost, st));
+      HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::H_MARK_COUNT, sh->cm_mpre.p + n, 8, hipMemcpyDeviceToHost, st));
+      HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::H_MARK_FIRST, sh->cm_pos.p, 8, hipMemcpyDeviceToHost, st));
+      HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::H_MARK_EXIT, c + ctr::MARK_EXIT, 8, hipMemcpyDeviceToHost, st));
       HIPCHK(ctx, hipStreamSynchronize(st));
-      if (*code == (uint32_t)n && sh->h_ctr[24] == first) {
+      if (*code == (uint32_t)n && sh->h_ctr[ctr::H_MARK_FIRST] == first) {
         sh->cm_valid = true;
         sh->cm_first = first;
         sh->cm_E = E;
         sh->cm_n = n;
-        *count = sh->h_ctr[23];
-        if (exit_flat) *exit_flat = sh->h_ctr[25];
+        *count = sh->h_ctr[ctr::H_MARK_COUNT];
+        if (exit_flat) *exit_flat = sh->h_ctr[ctr::H_MARK_EXIT];
         // set bits off the chain (false positives); 0 means the bitmap is the chain
         if (anomalies) *anomalies = (int32_t)std::min<uint64_t>(n - *count, INT32_MAX);
         return SBH_OK;
       }
     }
   }
-  HIPCHK(ctx, launch_chain_walk(sh->U.p, first, E, total, c + 4, c + 5, st));
-  HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + 20, c + 4, 16, hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, launch_chain_walk(sh->U.p, first, E, total, c + ctr::WALK_COUNT, c + ctr::WALK_EXIT, st));
+  // (WALK_COUNT and WALK_EXIT)
+  HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::WALK_COUNT, c + ctr::WALK_COUNT, 2 * 8, hipMemcpyDeviceToHost, st));
   HIPCHK(ctx, hipStreamSynchronize(st));
-  *count = sh->h_ctr[20];
-  if (exit_flat) *exit_flat = sh->h_ctr[21];
+  *count = sh->h_ctr[ctr::WALK_COUNT];
+  if (exit_flat) *exit_flat = sh->h_ctr[ctr::WALK_EXIT];
   return SBH_OK;
 }
 
@@ -1657,7 +1641,7 @@ static int split_starts_impl(sbh_shard *sh, const uint64_t *starts, const uint64
     sh->bits_begin = 0;
     sh->bits_end = sh->utotal;
     sh->bits_rtc = rtc;
-    if (rc == SBH_E_NEED_HALO) sh->bits_end = std::min<uint64_t>(sh->utotal, sh->h_ctr[2]);
+    if (rc == SBH_E_NEED_HALO) sh->bits_end = std::min<uint64_t>(sh->utotal, sh->h_ctr[ctr::EAGER_HALO_FIRST]);
   }
   auto rel_start = [&](uint64_t i) -> uint64_t {  // (a start off the shard: host path, flagged below)
     return starts[i] < sh->file_off || starts[i] >= end_res ? 0 : starts[i] - sh->file_off;
@@ -1892,18 +1876,19 @@ static int check_records_impl(sbh_shard *sh, const uint64_t *range_begin, const 
   const uint64_t cap_fp = fp_flat ? fp_cap : 0, cap_fn = fn_flat ? fn_cap : 0;
   HIPCHK(ctx, sh->t_fp.ensure(cap_fp + 1));
   HIPCHK(ctx, sh->t_fn.ensure(cap_fn + 1));
-  unsigned long long *acc = sh->ctr.p + 40;  // tp, fp, fn, fp slots, fn slots, unknown
-  HIPCHK(ctx, hipMemsetAsync(acc, 0, 6 * 8, st));
+  unsigned long long *acc = sh->ctr.p + ctr::TRUTH;  // tp, fp, fn, fp slots, fn slots, unknown
+  constexpr size_t acc_bytes = (ctr::TRUTH_END - ctr::TRUTH) * 8;
+  HIPCHK(ctx, hipMemsetAsync(acc, 0, acc_bytes, st));
   HIPCHK(ctx, launch_truth_scatter(sh->sp_vpos.p, n_rec, sh->b_cstart.p, sh->b_ustart.p, sh->nblocks, sh->file_off,
-                                   hb0, end, sh->tbits.p, acc + 5, st));
+                                   hb0, end, sh->tbits.p, acc + (ctr::TRUTH_UNKNOWN - ctr::TRUTH), st));
   HIPCHK(ctx, launch_truth_compare(sh->bits.p, sh->bits_begin, sh->tbits.p, hb0, end, sh->t_rb.p, sh->t_re.p,
                                    n_ranges, acc, sh->t_fp.p, cap_fp, sh->t_fn.p, cap_fn, st));
-  HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + 40, acc, 6 * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::TRUTH, acc, acc_bytes, hipMemcpyDeviceToHost, st));
   HIPCHK(ctx, hipStreamSynchronize(st));
-  out[0] = sh->h_ctr[40];
-  out[1] = sh->h_ctr[41];
-  out[2] = sh->h_ctr[42];
-  out[3] = sh->h_ctr[45];
+  out[0] = sh->h_ctr[ctr::TRUTH_TP];
+  out[1] = sh->h_ctr[ctr::TRUTH_FP];
+  out[2] = sh->h_ctr[ctr::TRUTH_FN];
+  out[3] = sh->h_ctr[ctr::TRUTH_UNKNOWN];
   // the mismatch lists arrive in atomic order and are sorted here; when there are more
   // mismatches than the cap, the listed ones are a (sorted) subset
   auto fetch = [&](uint64_t *dst, const uint64_t *src, uint64_t cap, uint64_t total) -> int {
@@ -1982,12 +1967,13 @@ static int run_pipelined(sbh_shard *sh, uint64_t E, int32_t rtc, uint64_t *n_tru
   HIPCHK(ctx, zero_u_pad(sh, sa));
   unsigned long long *c = sh->ctr.p;
   {
-    // ctr[0, CTR_RUN_WORDS) in one copy: k_eager's counters [0, 6) (first-unknown [2] = ~0), the
-    // step tail's FindRecordStart best [8] = ~0 and chain-proof counters [16, 20) = {0, ~0, 0, ~0},
-    // k_first_bad's [100] = ~0; the rest (per-call regions) zero
-    unsigned long long *tpl = sh->h_ctr + 1024;  // pinned
+    // ctr[0, CTR_RUN_WORDS) in one copy: k_eager's counters (the first need-halo position = ~0),
+    // the step tail's FindRecordStart best = ~0 and chain-proof counters = {0, ~0, 0, ~0},
+    // k_first_bad's = ~0; the rest (per-call regions) zero
+    unsigned long long *tpl = sh->h_ctr + ctr::H_RUN_TPL;  // pinned
     std::memset(tpl, 0, CTR_RUN_WORDS * 8);
-    tpl[2] = tpl[8] = tpl[17] = tpl[19] = tpl[100] = ~0ull;
+    tpl[ctr::EAGER_HALO_FIRST] = tpl[ctr::FRS_BEST] = tpl[ctr::PROOF_FIRST_ANOM] = tpl[ctr::PROOF_EXIT] =
+        tpl[ctr::FIRST_BAD] = ~0ull;
     HIPCHK(ctx, set_words(reinterpret_cast<uint64_t *>(c), reinterpret_cast<const uint64_t *>(tpl), CTR_RUN_WORDS, sa));
   }
   sh->inflated = sh->bits_valid = sh->chain_ok = sh->cm_valid = false;
@@ -2070,9 +2056,9 @@ static int run_pipelined(sbh_shard *sh, uint64_t E, int32_t rtc, uint64_t *n_tru
     sh->pipe_ms[2] = es;
   }
   if (std::getenv("SBH_XQ_DEBUG"))
-    fprintf(stderr, "[sbh] eager: deferred %llu, long-record queue %llu (%llu past the pre-test)\n", sh->h_ctr[3],
-            sh->h_ctr[4], sh->h_ctr[5]);
-  if (sh->h_ctr[3] > DEFER_CAP) {  // deferral overflow: plain pass
+    fprintf(stderr, "[sbh] eager: deferred %llu, long-record queue %llu (%llu past the pre-test)\n",
+            sh->h_ctr[ctr::EAGER_DEFER_N], sh->h_ctr[ctr::EAGER_XQ_N], sh->h_ctr[ctr::EAGER_XQ_LIVE]);
+  if (sh->h_ctr[ctr::EAGER_DEFER_N] > DEFER_CAP) {  // deferral overflow: plain pass
     sh->pipe_fallback = true;
     return eager_range(sh, 0, E, rtc, n_true);
   }
@@ -2080,11 +2066,11 @@ static int run_pipelined(sbh_shard *sh, uint64_t E, int32_t rtc, uint64_t *n_tru
   sh->bits_begin = 0;
   sh->bits_end = E;
   sh->bits_rtc = rtc;
-  if (n_true) *n_true = sh->h_ctr[0];
-  if (sh->h_ctr[1]) {
+  if (n_true) *n_true = sh->h_ctr[ctr::EAGER_TRUE];
+  if (sh->h_ctr[ctr::EAGER_HALO_N]) {
     sh->bits_valid = false;
-    return fail(ctx, SBH_E_NEED_HALO, "%llu positions (first %llu) need bytes past the shard", sh->h_ctr[1],
-                sh->h_ctr[2]);
+    return fail(ctx, SBH_E_NEED_HALO, "%llu positions (first %llu) need bytes past the shard",
+                sh->h_ctr[ctr::EAGER_HALO_N], sh->h_ctr[ctr::EAGER_HALO_FIRST]);
   }
   return SBH_OK;
 }
@@ -2126,16 +2112,17 @@ int sbh_run_shard(sbh_shard *sh, uint64_t index_start, uint64_t own_end_file, in
   const uint64_t total0 = sh->seg_end.empty() ? 0 : sh->seg_end[0];
   const uint64_t hi0 = std::min(std::min<uint64_t>(total0, (uint64_t)std::max(mrs, 0)), E);
   const uint64_t E0 = std::min(E, total0);
-  unsigned long long *tbest = sh->ctr.p + 8, *tc = sh->ctr.p + 16;
+  unsigned long long *tbest = sh->ctr.p + ctr::FRS_BEST, *c = sh->ctr.p;
   bool tail = rtc >= 0 && hi0 > 0;
   if (tail && sh->cc.ensure((E + 31) / 32 / VC_CHUNK + 2) != hipSuccess) tail = false;
-  // (tbest and tc start as run_pipelined's counter template sets them, and come back to h_ctr[8]
-  // and h_ctr[16, 20) with its one status copy)
+  // (tbest and the proof counters start as run_pipelined's counter template sets them, and come
+  // back to the same words of h_ctr with its one status copy)
   auto tail_launch = [&](hipStream_t s) -> hipError_t {
     hipError_t e = launch_first_set(sh->bits.p, 0, 0, hi0, tbest, s);
     if (e == hipSuccess)
-      e = launch_verify_chain_count(sh->U.p, sh->bits.p, 0, E, 0, E0, total0, tc, tc + 1, tc + 3, tc + 2, s,
-                                    tbest, sh->cc.p);
+      e = launch_verify_chain_count(sh->U.p, sh->bits.p, 0, E, 0, E0, total0, c + ctr::PROOF_ANOM,
+                                    c + ctr::PROOF_FIRST_ANOM, c + ctr::PROOF_EXIT, c + ctr::PROOF_SET, s, tbest,
+                                    sh->cc.p);
     return e;
   };
   rc = tail ? run_pipelined(sh, E, rtc, &res->n_true, tail_launch) : run_pipelined(sh, E, rtc, &res->n_true);
@@ -2147,19 +2134,20 @@ int sbh_run_shard(sbh_shard *sh, uint64_t index_start, uint64_t own_end_file, in
   uint64_t first = 0;
   int32_t delta = 0;
   sh->run_first = ~0ull;
-  if (tail && sh->h_ctr[8] != ~0ull) {
-    first = sh->h_ctr[8];
+  if (tail && sh->h_ctr[ctr::FRS_BEST] != ~0ull) {
+    first = sh->h_ctr[ctr::FRS_BEST];
     sh->run_first = first;
     rc = SBH_OK;
-    if (first < E0 && sh->h_ctr[16] == 0 && sh->h_ctr[19] != ~0ull) {  // count_records_impl's proof, done
+    // (count_records_impl's proof, done)
+    if (first < E0 && sh->h_ctr[ctr::PROOF_ANOM] == 0 && sh->h_ctr[ctr::PROOF_EXIT] != ~0ull) {
       sh->cm_valid = false;
       sh->chain_ok = true;
       sh->cc_ok = true;
       sh->chain_first = first;
       sh->chain_E = E0;
-      res->count = sh->h_ctr[18];
+      res->count = sh->h_ctr[ctr::PROOF_SET];
       res->anomalies = 0;
-      res->exit_flat = sh->h_ctr[19];
+      res->exit_flat = sh->h_ctr[ctr::PROOF_EXIT];
     } else {
       // (the tail's proof covered [first, E0) of this bitmap: its counters are reused when first
       // lies in the first segment, which is the range count_records_impl proves)
@@ -2241,16 +2229,17 @@ int sbh_run_stream(sbh_ctx *ctx, const void *host, uint64_t n, uint64_t file_off
 static int verify_crc_prefix(sbh_shard *sh, uint64_t nb, uint64_t *n_bad, uint64_t *first_bad, float *ms) {
   sbh_ctx *ctx = sh->ctx;
   hipStream_t st = sh->st;
-  unsigned long long *c = sh->ctr.p + 32;
-  HIPCHK(ctx, hipMemsetAsync(c, 0, 8, st));
-  HIPCHK(ctx, hipMemsetAsync(c + 1, 0xff, 8, st));
+  unsigned long long *nbad = sh->ctr.p + ctr::CRC_BAD_N, *fbad = sh->ctr.p + ctr::CRC_FIRST_BAD;
+  HIPCHK(ctx, hipMemsetAsync(nbad, 0, 8, st));
+  HIPCHK(ctx, hipMemsetAsync(fbad, 0xff, 8, st));
   mark(sh, 7);
-  HIPCHK(ctx, launch_block_crc(sh->comp.p, sh->dev_blocks(), nb, sh->U.p, c, c + 1, st));
+  HIPCHK(ctx, launch_block_crc(sh->comp.p, sh->dev_blocks(), nb, sh->U.p, nbad, fbad, st));
   mark(sh, 8);
-  HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + 32, c, 16, hipMemcpyDeviceToHost, st));
+  // (CRC_BAD_N and CRC_FIRST_BAD)
+  HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::CRC_BAD_N, nbad, 2 * 8, hipMemcpyDeviceToHost, st));
   HIPCHK(ctx, hipStreamSynchronize(st));
-  *n_bad = sh->h_ctr[32];
-  *first_bad = sh->h_ctr[32] ? sh->hb[sh->h_ctr[33]].start : 0;
+  *n_bad = sh->h_ctr[ctr::CRC_BAD_N];
+  *first_bad = sh->h_ctr[ctr::CRC_BAD_N] ? sh->hb[sh->h_ctr[ctr::CRC_FIRST_BAD]].start : 0;
   *ms = 0.f;
   if (sh->ev_ok) (void)hipEventElapsedTime(ms, sh->ev[7], sh->ev[8]);
   return SBH_OK;
@@ -2322,7 +2311,7 @@ int sbh_run_stream2(sbh_ctx *ctx, const void *host, uint64_t n, uint64_t file_of
       if (e == hipSuccess) e = hipEventCreate(&scp->c0[i]);
     }
     if (e != hipSuccess) {
-      stream_cache_free(scp);
+      delete scp;
       return res->status = fail(ctx, SBH_E_HIP, "run_stream2: %s", hipGetErrorString(e));
     }
   }
@@ -2339,8 +2328,7 @@ int sbh_run_stream2(sbh_ctx *ctx, const void *host, uint64_t n, uint64_t file_of
     StreamCache &R;
     ~Detach() {
       if (R.cs) (void)hipStreamSynchronize(R.cs);
-      R.sh->comp.p = nullptr;
-      R.sh->comp.cap = 0;
+      R.sh->comp.unlend();
     }
   } detach{R};
   sbh_shard *sh = R.sh;
@@ -2424,8 +2412,7 @@ int sbh_run_stream2(sbh_ctx *ctx, const void *host, uint64_t n, uint64_t file_of
     const uint64_t ld = load_end(hi);
     HIPCHK(ctx, hipStreamWaitEvent(sh->st, R.done[cur], 0));
     HIPCHK(ctx, hipMemsetAsync(R.buf[cur].p + win_len[cur], 0, pad, sh->st));
-    sh->comp.p = R.buf[cur].p;
-    sh->comp.cap = R.buf[cur].cap;
+    sh->comp.lend(R.buf[cur].p, R.buf[cur].cap);
     sh->file_off = lo;
     sh->n = ld - lo;
     sh->at_eof = ld == file_size;
@@ -2506,9 +2493,8 @@ int sbh_run_stream2(sbh_ctx *ctx, const void *host, uint64_t n, uint64_t file_of
       account(0);
       account(1);
       halo *= 4;
+      sh->comp.unlend();
       for (auto &b : R.buf) b.release();
-      sh->comp.p = nullptr;
-      sh->comp.cap = 0;
       HIPCHK(ctx, size_bufs());
       HIPCHK(ctx, enqueue(cur, lo, load_end(hi)));
       prefetch = true;
@@ -2593,8 +2579,7 @@ int sbh_run_stream2(sbh_ctx *ctx, const void *host, uint64_t n, uint64_t file_of
     if (it == sh->hb.end()) return res->status = fail(ctx, SBH_E_NEED_HALO, "halo %llu holds no block past %llu",
                                                      (unsigned long long)halo, (unsigned long long)hi);
     start = it->start;
-    sh->comp.p = nullptr;
-    sh->comp.cap = 0;
+    sh->comp.unlend();
     lo = lo2;
     hi = hi2;
     cur = 1 - cur;
@@ -2887,14 +2872,14 @@ int sbh_split_records_batch(sbh_shard *sh, const uint64_t *starts, const uint64_
   // pass below measures every record against the resident bytes' end; where empty blocks cut
   // the stream into segments, each record against its own segment's end first (sbh_split_records
   // measures a split's records against the end of the segment its first record lies in).
-  unsigned long long *bad = sh->ctr.p + 25;
+  unsigned long long *bad = sh->ctr.p + ctr::REC_SEG_BAD;
   if (rows && (decode ? sh->seg_end.size() > 1 : !sh->at_eof)) {
     HIPCHK(ctx, hipMemsetAsync(bad, 0xff, 8, st));
     HIPCHK(ctx, launch_rec_seg_check(sh->U.p, decode ? R.pos.p : R.pos.p + rows - 1, decode ? rows : 1, sh->d_seg.p,
                                      (uint32_t)sh->seg_end.size(), bad, st));
-    HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + 25, bad, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::REC_SEG_BAD, bad, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
-    if (sh->h_ctr[25] != ~0ull)
+    if (sh->h_ctr[ctr::REC_SEG_BAD] != ~0ull)
       return sh->at_eof ? fail(ctx, SBH_E_BAD_RECORD, "a record of the batch runs over the end of the stream")
                         : fail(ctx, SBH_E_NEED_HALO, "a record of the batch runs past the shard");
   }
@@ -2944,17 +2929,18 @@ static int records_finish(sbh_shard *sh, uint64_t n, uint64_t total, sbh_records
     HIPCHK(ctx, of[k]->ensure(n + 1));
     HIPCHK(ctx, hipMemsetAsync(sz[k]->p + n, 0, 8, st));
   }
-  unsigned long long *bad = sh->ctr.p + 24;
+  unsigned long long *bad = sh->ctr.p + ctr::REC_BAD;
   HIPCHK(ctx, hipMemsetAsync(bad, 0xff, 8, st));
   HIPCHK(ctx, launch_rec_sizes(sh->U.p, R.pos.p, n, total, R.nm.p, R.cg.p, R.sq.p, R.ax.p, bad, st));
   HIPCHK(ctx, sh->tmp.ensure(scan_tmp_words(n + 1)));
   for (int k = 0; k < 4; ++k) HIPCHK(ctx, scan_exclusive_u64(sz[k]->p, of[k]->p, n + 1, sh->tmp.p, st));
   uint64_t tot[4] = {0, 0, 0, 0};
   for (int k = 0; k < 4; ++k) HIPCHK(ctx, hipMemcpyAsync(&tot[k], of[k]->p + n, 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + 24, bad, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::REC_BAD, bad, 8, hipMemcpyDeviceToHost, st));
   HIPCHK(ctx, hipStreamSynchronize(st));
-  if (sh->h_ctr[24] != ~0ull) return fail(ctx, SBH_E_BAD_RECORD, "record %llu of the range is malformed",
-                                          (unsigned long long)sh->h_ctr[24]);
+  if (sh->h_ctr[ctr::REC_BAD] != ~0ull)
+    return fail(ctx, SBH_E_BAD_RECORD, "record %llu of the range is malformed",
+                (unsigned long long)sh->h_ctr[ctr::REC_BAD]);
   HIPCHK(ctx, R.ref_id.ensure(n)); HIPCHK(ctx, R.p0.ensure(n)); HIPCHK(ctx, R.nref.ensure(n));
   HIPCHK(ctx, R.npos.ensure(n)); HIPCHK(ctx, R.tlen.ensure(n)); HIPCHK(ctx, R.flag.ensure(n));
   HIPCHK(ctx, R.bin.ensure(n)); HIPCHK(ctx, R.mapq.ensure(n));
@@ -3121,21 +3107,22 @@ int sbh_records_sam_scan(sbh_shard *sh, const char *ref_names, const uint64_t *r
   HIPCHK(ctx, sh->tmp.ensure(scan_tmp_words(n + 1)));
   HIPCHK(ctx, hipMemsetAsync(S.len.p + n, 0, 8, st));
   HIPCHK(ctx, hipMemsetAsync(S.hostf.p + n, 0, 8, st));
-  unsigned long long *bad = sh->ctr.p + 48;  // [48] first malformed row
+  unsigned long long *bad = sh->ctr.p + ctr::SAM_BAD;  // first malformed row
   HIPCHK(ctx, hipMemsetAsync(bad, 0xff, 8, st));
   HIPCHK(ctx, launch_sam_sizes(sh->U.p, R.pos.p, n, R.nmo.p, R.cgo.p, R.sqo.p, R.axo.p, S.refs.p, S.ref_off.p, n_ref,
                                S.len.p, S.hostf.p, bad, st));
   HIPCHK(ctx, scan_exclusive_u64(S.hostf.p, S.hpre.p, n + 1, sh->tmp.p, st));
   HIPCHK(ctx, scan_exclusive_u64(S.len.p, S.off.p, n + 1, sh->tmp.p, st));  // (speculative: right when n_host == 0)
-  HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + 48, bad, 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + 49, S.hpre.p + n, 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + 50, S.off.p + n, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::SAM_BAD, bad, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::H_SAM_NHOST, S.hpre.p + n, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::H_SAM_TOTAL, S.off.p + n, 8, hipMemcpyDeviceToHost, st));
   HIPCHK(ctx, hipStreamSynchronize(st));
-  if (sh->h_ctr[48] != ~0ull)
-    return fail_with(ctx, SBH_E_BAD_RECORD, {(int64_t)sh->h_ctr[48]}, "record %llu of the scan has a malformed CIGAR or tag area",
-                     (unsigned long long)sh->h_ctr[48]);
-  const uint64_t n_host = sh->h_ctr[49];
-  uint64_t total = sh->h_ctr[50];
+  if (sh->h_ctr[ctr::SAM_BAD] != ~0ull)
+    return fail_with(ctx, SBH_E_BAD_RECORD, {(int64_t)sh->h_ctr[ctr::SAM_BAD]},
+                     "record %llu of the scan has a malformed CIGAR or tag area",
+                     (unsigned long long)sh->h_ctr[ctr::SAM_BAD]);
+  const uint64_t n_host = sh->h_ctr[ctr::H_SAM_NHOST];
+  uint64_t total = sh->h_ctr[ctr::H_SAM_TOTAL];
   if (n_host) {
     for (auto *b : {&S.rows, &S.rbytes}) HIPCHK(ctx, b->ensure(n_host));
     HIPCHK(ctx, S.goff.ensure(n_host + 1));
@@ -3168,9 +3155,9 @@ int sbh_records_sam_scan(sbh_shard *sh, const char *ref_names, const uint64_t *r
     HIPCHK(ctx, hipMemcpyAsync(S.rbytes.p, hlen.data(), 8 * n_host, hipMemcpyHostToDevice, st));
     HIPCHK(ctx, launch_sam_scatter(S.rows.p, S.rbytes.p, n_host, n, S.len.p, st));
     HIPCHK(ctx, scan_exclusive_u64(S.len.p, S.off.p, n + 1, sh->tmp.p, st));
-    HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + 50, S.off.p + n, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::H_SAM_TOTAL, S.off.p + n, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
-    total = sh->h_ctr[50];
+    total = sh->h_ctr[ctr::H_SAM_TOTAL];
   }
   HIPCHK(ctx, S.text.ensure(total));
   HIPCHK(ctx, launch_sam_emit(sh->U.p, R.pos.p, n, R.nmo.p, R.cgo.p, R.sqo.p, R.axo.p, S.refs.p, S.ref_off.p, n_ref,
@@ -3265,8 +3252,9 @@ int sbh_bai_scan(sbh_shard *sh, uint64_t first, uint64_t end_flat, sbh_bai_sizes
   HIPCHK(ctx, B.lin.ensure(lin_size));
   HIPCHK(ctx, B.aux.ensure(8));
   HIPCHK(ctx, sh->tmp.ensure(scan_tmp_words(n + 1)));
-  unsigned long long *err = sh->ctr.p + 40;  // rows: [40] does not fit, [41] unsorted, [42] off its reference
-  HIPCHK(ctx, hipMemsetAsync(err, 0xff, 24, st));
+  unsigned long long *err = sh->ctr.p + ctr::BAI_ERR;  // rows: does not fit, unsorted, off its reference
+  constexpr size_t err_bytes = (ctr::BAI_ERR_END - ctr::BAI_ERR) * 8;
+  HIPCHK(ctx, hipMemsetAsync(err, 0xff, err_bytes, st));
   HIPCHK(ctx, hipMemsetAsync(B.aux.p, 0xff, 24, st));
   if (lin_size) HIPCHK(ctx, hipMemsetAsync(B.lin.p, 0xff, 8 * lin_size, st));
   uint64_t nruns = 0, no_coor = 0;
@@ -3277,17 +3265,19 @@ int sbh_bai_scan(sbh_shard *sh, uint64_t first, uint64_t end_flat, sbh_bai_sizes
                                 sh->file_off, B.key.p, B.win.p, B.vbeg.p, B.flg.p, B.aux.p, err, st));
     HIPCHK(ctx, launch_bai_heads(B.key.p, B.win.p, B.vbeg.p, n, B.lin_off.p, B.flg.p, B.lin.p, st));
     HIPCHK(ctx, scan_exclusive_u64(B.flg.p, B.pre.p, n + 1, sh->tmp.p, st));
-    HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + 40, err, 24, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + 43, B.pre.p + n, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + 44, B.aux.p, 24, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::BAI_ERR, err, err_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::H_BAI_NRUNS, B.pre.p + n, 8, hipMemcpyDeviceToHost, st));
+    // (aux's three words: the edges are the last two)
+    HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::H_BAI_AUX, B.aux.p, 3 * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
-    const uint64_t unfit = sh->h_ctr[40], uns = sh->h_ctr[41], off_ref = sh->h_ctr[42];
+    const uint64_t unfit = sh->h_ctr[ctr::BAI_UNFIT], uns = sh->h_ctr[ctr::BAI_UNSORTED],
+                   off_ref = sh->h_ctr[ctr::BAI_OFF_REF];
     const uint64_t bad = std::min(unfit, off_ref);
     if (bad != ~0ull || uns != ~0ull) {
       const uint64_t row = std::min(bad, uns);
-      HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + 47, B.vbeg.p + row, 8, hipMemcpyDeviceToHost, st));
+      HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::H_BAI_BAD_VPOS, B.vbeg.p + row, 8, hipMemcpyDeviceToHost, st));
       HIPCHK(ctx, hipStreamSynchronize(st));
-      const uint64_t v = sh->h_ctr[47];
+      const uint64_t v = sh->h_ctr[ctr::H_BAI_BAD_VPOS];
       if (bad <= uns) {
         // only a record that does not fit can be cured by more resident bytes
         if (unfit < off_ref && !sh->at_eof)
@@ -3298,7 +3288,7 @@ int sbh_bai_scan(sbh_shard *sh, uint64_t first, uint64_t end_flat, sbh_bai_sizes
       return fail_with(ctx, SBH_E_UNSORTED, {(int64_t)v},
                        "record %llu of the scan (%llu:%u) is out of coordinate order", (unsigned long long)row, (unsigned long long)(v >> 16), (unsigned)(v & 0xffff));
     }
-    nruns = sh->h_ctr[43] & 0xffffffffull;
+    nruns = sh->h_ctr[ctr::H_BAI_NRUNS] & 0xffffffffull;
     HIPCHK(ctx, B.ridx.ensure(nruns));
     HIPCHK(ctx, B.runs.ensure(nruns));
     HIPCHK(ctx, launch_bai_runs(B.flg.p, B.pre.p, n, nruns, B.key.p, B.vbeg.p, B.aux.p, B.ridx.p, B.runs.p, st));
@@ -3309,9 +3299,12 @@ int sbh_bai_scan(sbh_shard *sh, uint64_t first, uint64_t end_flat, sbh_bai_sizes
       no_coor = last.n_mapped + last.n_unmapped;
       --nruns;
     }
-    B.edges[0] = (int32_t)(sh->h_ctr[45] >> 32), B.edges[1] = (int32_t)(uint32_t)sh->h_ctr[45];
-    if (sh->h_ctr[46] != ~0ull)
-      B.edges[2] = (int32_t)(sh->h_ctr[46] >> 32), B.edges[3] = (int32_t)(uint32_t)sh->h_ctr[46];
+    B.edges[0] = (int32_t)(sh->h_ctr[ctr::H_BAI_FIRST_EDGE] >> 32);
+    B.edges[1] = (int32_t)(uint32_t)sh->h_ctr[ctr::H_BAI_FIRST_EDGE];
+    if (sh->h_ctr[ctr::H_BAI_LAST_EDGE] != ~0ull) {
+      B.edges[2] = (int32_t)(sh->h_ctr[ctr::H_BAI_LAST_EDGE] >> 32);
+      B.edges[3] = (int32_t)(uint32_t)sh->h_ctr[ctr::H_BAI_LAST_EDGE];
+    }
   }
   B.sz = sbh_bai_sizes{n, nruns, no_coor, lin_size};
   B.valid = true;
@@ -3371,10 +3364,8 @@ int sbh_bgzf_compress_level(sbh_ctx *ctx, const void *src, uint64_t n, int src_o
     DBuf<uint64_t> offs, info;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     hipStream_t own = nullptr;
-    ~Bufs() {
+    ~Bufs() {  // (the buffers free themselves after this, the call's own stream drained)
       if (own) (void)hipStreamSynchronize(own);
-      in.release(), slots.release(), packed.release(), recs.release(), prev.release(), toks.release(), sizes.release(),
-          offs.release(), info.release();
       if (e0) (void)hipEventDestroy(e0);
       if (e1) (void)hipEventDestroy(e1);
       if (own) (void)hipStreamDestroy(own);

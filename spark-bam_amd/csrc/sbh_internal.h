@@ -227,30 +227,100 @@ hipError_t launch_zdeflate(const uint8_t *src, uint64_t n, uint64_t b0, uint32_t
 hipError_t launch_member_footer(const uint8_t *src, uint64_t n, uint64_t b0, uint64_t nblocks, uint32_t nbatch,
                                 uint8_t *slots, uint64_t stride, const uint32_t *sizes, hipStream_t st);
 
-// Batched splits and check-bam truth comparison (splits.hip).
 // The shard's counter buffer (sbh_shard::ctr, device, CTR_WORDS u64, zeroed by
-// sbh_shard_create) and its pinned host mirror h_ctr.  Entry points run one at a time on the
-// shard's stream and copy their results out before returning, so the per-call regions
-// below may overlap each other; the persistent regions may not overlap anything.
-//   per call  [0, CTR_CALL_END)   k_eager (n_true, deferred, xq) / k_full (n_success,
-//                                 n_unknown, min_unknown, close_n, Counts [4, 403),
-//                                 rbe [403, 1747)); FindRecordStart best [8]; chain walk
-//                                 [16, 20); chain marks [20, 26); block CRCs [32, 34);
-//                                 check-records [40, 46); BAI scan [40, 48); first bad block [100]
-//   persistent [CTR_TRUE_SPREAD, +CTR_TRUE_WORDS)  k_eager's per-wave true counts: must be
-//                                 zero before every k_eager launch; k_fold_true folds them
-//                                 into n_true and zeroes them again
-//   per call  [CTR_NEXT18, +4)    the 18 bytes after an index's last chained block, at byte
-//                                 NEXT18_NONLIN the linear chain's "not linear" flag (u8), at
-//                                 byte NEXT18_NEMPTY the chain's empty-block count (u32), then
-//                                 the linear chain's start index (u64, device only)
+// sbh_shard_create) and its pinned host mirror h_ctr (same size, same indices).  Entry points
+// run one at a time on the shard's stream and copy their results out before returning, so
+// regions used within one call may share words with another call's; the one persistent
+// region may overlap nothing.
 constexpr uint32_t CTR_WORDS = 4096;
-constexpr uint32_t NEXT18_NONLIN = 18, NEXT18_NEMPTY = 20;
-constexpr uint32_t CTR_CALL_END = 4 + 21 * 19 + 21 * 64;
+// persistent [CTR_TRUE_SPREAD, +CTR_TRUE_WORDS): k_eager's per-wave true counts, zero before
+// every k_eager launch; k_fold_true folds them into the true count and zeroes them again
 constexpr uint32_t CTR_TRUE_SPREAD = 2048, CTR_TRUE_WORDS = 64 * 16;
+// per call [CTR_NEXT18, +4): the 18 bytes after an index's last chained block, at byte
+// NEXT18_NONLIN the linear chain's "not linear" flag (u8), at byte NEXT18_NEMPTY the chain's
+// empty-block count (u32), then the linear chain's start index (u64, device only)
 constexpr uint32_t CTR_NEXT18 = CTR_TRUE_SPREAD + CTR_TRUE_WORDS;
-static_assert(CTR_CALL_END <= CTR_TRUE_SPREAD && CTR_NEXT18 + 4 <= CTR_WORDS, "counter buffer layout");
+constexpr uint32_t NEXT18_NONLIN = 18, NEXT18_NEMPTY = 20;
+// sbh_run_shard sets ctr[0, CTR_RUN_WORDS) from one template (h_ctr + H_RUN_TPL) and brings
+// the same words back in one copy with the inflate status
+constexpr uint32_t CTR_RUN_WORDS = 101;
 
+// The slots of [0, CTR_CALL_END), by owner.  A name without H_ is a word a kernel writes (its
+// result lands at the same index of h_ctr); an H_ name exists only in h_ctr.
+namespace ctr {
+// eager checker (launch_eager, _defer, _xq; eager_range, run_pipelined)
+constexpr uint32_t EAGER_TRUE = 0, EAGER_HALO_N = 1, EAGER_HALO_FIRST = 2;  // need-halo: count, min position
+constexpr uint32_t EAGER_DEFER_N = 3, EAGER_XQ_N = 4, EAGER_XQ_LIVE = 5;    // xq: queued, past the pre-test
+constexpr uint32_t EAGER_END = 6;
+// full checker (launch_full, sbh_check_full): Counts[nnz][flag] and the reads-before-error
+// histogram [nnz][rbe] behind four scalars.  Shares [0, FULL_END) with everything below:
+// sbh_check_full zeroes it, runs and copies it out within the call.
+constexpr uint32_t FULL_NNZ = SBH_NNZ_MAX, FULL_FLAGS = 19, FULL_RBE = SBH_RBE_MAX;
+constexpr uint32_t FULL_SUCCESS = 0, FULL_UNKNOWN_N = 1, FULL_UNKNOWN_MIN = 2, FULL_CLOSE_N = 3;
+constexpr uint32_t FULL_COUNTS = 4, FULL_COUNTS_N = FULL_NNZ * FULL_FLAGS;
+constexpr uint32_t FULL_RBE_HIST = FULL_COUNTS + FULL_COUNTS_N, FULL_RBE_N = FULL_NNZ * FULL_RBE;
+constexpr uint32_t FULL_END = FULL_RBE_HIST + FULL_RBE_N;
+// FindBlockStart's best (sbh_find_block_start); sbh_index lands its candidate count in the
+// same word of the mirror (h_ctr only)
+constexpr uint32_t FBS_BEST = 0, H_INDEX_NCAND = 0;
+// FindRecordStart's best (sbh_find_record_start, sbh_run_shard's tail)
+constexpr uint32_t FRS_BEST = 8;
+// chain proof (k_verify_chain_w).  Not only per call: sbh_run_shard's tail writes these and its
+// status copy leaves them in h_ctr, where count_records_impl(known = true) -- called by
+// sbh_run_shard next, nothing else having run on the shard -- reads them instead of proving again.
+constexpr uint32_t PROOF_ANOM = 16, PROOF_FIRST_ANOM = 17, PROOF_SET = 18, PROOF_EXIT = 19, PROOF_END = 20;
+// chain walk (k_chain_walk): records, exit
+constexpr uint32_t WALK_COUNT = 20, WALK_EXIT = 21;
+// chain mark (launch_chain_mark): the exit and, in the word behind it, the verdict (u32) on
+// the device; h_ctr only: the verdict's landing place, the marked count, the first node and
+// the exit's copy
+constexpr uint32_t MARK_EXIT = 22, MARK_CODE = 23;
+constexpr uint32_t H_MARK_CODE = 22, H_MARK_COUNT = 23, H_MARK_FIRST = 24, H_MARK_EXIT = 25;
+// records: first malformed row of the size pass (records_finish) and of the batch's segment
+// check.  They share H_MARK_FIRST / H_MARK_EXIT: count_records_impl has read those before it
+// returns.
+constexpr uint32_t REC_BAD = 24, REC_SEG_BAD = 25;
+// block CRC (launch_block_crc): bad blocks, first bad block
+constexpr uint32_t CRC_BAD_N = 32, CRC_FIRST_BAD = 33;
+// check-records (launch_truth_scatter / _compare): tp, fp, fn, fp slots, fn slots, unknown
+constexpr uint32_t TRUTH = 40, TRUTH_TP = 40, TRUTH_FP = 41, TRUTH_FN = 42, TRUTH_UNKNOWN = 45;
+constexpr uint32_t TRUTH_END = 46;
+// BAI scan (sbh_bai_scan): three error rows on the device; h_ctr only: the run count, the
+// scan's three aux words (the edges are the last two) and the bad row's virtual offset.  Shares
+// [40, 48) with check-records: per call.
+constexpr uint32_t BAI_ERR = 40, BAI_UNFIT = 40, BAI_UNSORTED = 41, BAI_OFF_REF = 42, BAI_ERR_END = 43;
+constexpr uint32_t H_BAI_NRUNS = 43, H_BAI_AUX = 44, H_BAI_FIRST_EDGE = 45, H_BAI_LAST_EDGE = 46;
+constexpr uint32_t H_BAI_BAD_VPOS = 47;
+// SAM scan (sbh_records_sam_scan): first malformed row; h_ctr only: host rows, text bytes
+constexpr uint32_t SAM_BAD = 48, H_SAM_NHOST = 49, H_SAM_TOTAL = 50;
+// inflate status (launch_first_bad): the first block whose status is not INF_OK
+constexpr uint32_t FIRST_BAD = 100;
+// h_ctr only: that block's status (u32), fetched after the run's copy of [0, CTR_RUN_WORDS)
+constexpr uint32_t H_BAD_STATUS = 101;
+// h_ctr only, host scratch under the full checker's mirror (each written and read within one
+// call): the 18 bytes at an index's start and its next18 words (sbh_index); the proof
+// counters' initial values, an H2D source, and the bitmap word of the proof's first position
+// (count_records_impl); the run template
+constexpr uint32_t H_INDEX_HDR18 = 512, H_INDEX_NEXT18 = 516;
+constexpr uint32_t H_PROOF_INIT = 600, H_PROOF_FIRST_WORD = 604;
+constexpr uint32_t H_RUN_TPL = 1024;
+}  // namespace ctr
+constexpr uint32_t CTR_CALL_END = 4 + ctr::FULL_NNZ * ctr::FULL_FLAGS + ctr::FULL_NNZ * ctr::FULL_RBE;
+static_assert(CTR_CALL_END <= CTR_TRUE_SPREAD && CTR_NEXT18 + 4 <= CTR_WORDS, "counter buffer layout");
+static_assert(ctr::FULL_END == CTR_CALL_END, "the full checker's counters end the per-call region");
+// what the run template presets (the eager counters, FindRecordStart's best, the proof
+// counters, the first bad block) travels in the run's one copy each way ...
+static_assert(ctr::EAGER_END <= CTR_RUN_WORDS && ctr::FRS_BEST < CTR_RUN_WORDS &&
+                  ctr::PROOF_END <= CTR_RUN_WORDS && ctr::FIRST_BAD == CTR_RUN_WORDS - 1,
+              "the run template covers every slot it presets, the first bad block last");
+// ... and that copy must not land on the status word fetched after it
+static_assert(ctr::H_BAD_STATUS >= CTR_RUN_WORDS, "the bad block's status lies behind the run's copy");
+static_assert(ctr::H_RUN_TPL + CTR_RUN_WORDS <= CTR_WORDS, "the run template fits the mirror");
+static_assert(ctr::H_INDEX_HDR18 + 3 <= ctr::H_INDEX_NEXT18 && ctr::H_INDEX_NEXT18 + 3 <= ctr::H_PROOF_INIT &&
+                  ctr::H_PROOF_INIT + 4 <= ctr::H_PROOF_FIRST_WORD && ctr::H_PROOF_FIRST_WORD < ctr::H_RUN_TPL,
+              "host scratch regions are disjoint");
+
+// Batched splits and check-bam truth comparison (splits.hip).
 constexpr uint32_t SPLIT_OK = 0;    // first record and flat end decided on the device
 constexpr uint32_t SPLIT_HOST = 1;  // off the common path: the exact per-split host path decides
 constexpr uint32_t SPLIT_NOREAD = 2;  // FindBlockStart lands on an empty block: NoReadFoundException (no records)

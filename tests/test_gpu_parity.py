@@ -590,34 +590,79 @@ def test_split_parameters(golden, z, rtc):
             assert status[k] != 0, (s, e, z, rtc)
 
 
-def test_shard_lifecycle_frees_hbm(ctx):
-    """Creating and destroying shards (index, inflate, eager pass, whole run) leaves device
-    memory where it was: every buffer a shard grows is released by sbh_shard_destroy (ADVICE r04:
-    the eager tile-summary buffer was not)."""
+def _hbm_free():
+    """Free device memory now, as the HIP runtime libsparkbam_hip.so itself links reports it
+    (torch, when imported earlier in the run, brings its own libamdhip64.so: a second runtime
+    instance with no device state of ours)."""
     import ctypes as C
-    # the HIP runtime libsparkbam_hip.so itself links (torch, when imported earlier in the run,
-    # brings its own libamdhip64.so: a second runtime instance with no device state of ours)
     hip = C.CDLL("libamdhip64.so.7")
     free, total = C.c_size_t(), C.c_size_t()
+    assert hip.hipMemGetInfo(C.byref(free), C.byref(total)) == 0
+    return free.value
 
-    def free_now():
-        assert hip.hipMemGetInfo(C.byref(free), C.byref(total)) == 0
-        return free.value
 
+@pytest.fixture(scope="module")
+def lifecycle_file():
     import sys
     sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "tools"))
     import synth
     data = synth.make_bam(synth.params(0x5B4D0001), 100_000)[0]  # ~33 MB flat
-    of = OracleFile(data)
+    return data, OracleFile(data)
+
+
+def test_shard_lifecycle_frees_hbm(ctx, lifecycle_file):
+    """Creating and destroying shards leaves device memory where it was: every buffer a shard
+    grows -- by index, inflate, the eager pass and the whole run (the eager
+    tile-summary buffer was once forgotten), and by the batched splits, the record columns, the
+    SAM text, the BAI scan, the full checker, check-records and a reload -- is freed with it."""
+    data, of = lifecycle_file
+    splits = list(file_splits(data.size, data.size // 6 + 1))
+    seen = {}
 
     def cycle():
         sh = load(ctx, data, of.contig_len)
         sh.check_eager(0, of.flat_size)
         sh.run(0, data.size)
+        names, _, hdr_end = sb.bam_header(sh)
+        status, _, counts, _ = sh.split_starts(splits)
+        _, per, cols = sh.split_records_batch(splits, decode=False)
+        n = sh.records_scan(hdr_end, sh.flat_size)
+        text, line_off = sh.records_sam(names)
+        runs, _, _ = sh.bai_scan(hdr_end, sh.flat_size)
+        full = sh.check_full(0, 1 << 20)
+        tp, fp, fn, _, _, _ = sh.check_records([(hdr_end, sh.flat_size)], cols["vpos"])
+        sh.load(data, 0)
+        sh.index(0)
+        sh.inflate()
         sh.close()
+        # (every stage did its work: the buffers it grows were in use)
+        seen.update(splits=int(counts.sum()), batch=sum(s["rec_count"] for s in per), records=n,
+                    lines=line_off.size - 1, runs=runs.size, full=full["n_success"], truth=(tp, fp, fn))
+        assert not status.any() and text.size
 
     cycle()
-    before = free_now()
+    assert seen["splits"] == seen["batch"] == seen["records"] == seen["lines"] == 100_000, seen
+    assert seen["runs"] > 0 and seen["full"] > 0 and seen["truth"] == (100_000, 0, 0), seen
+    before = _hbm_free()
     for _ in range(12):
         cycle()
-    assert before - free_now() < (1 << 20), (before, free_now())
+    assert before - _hbm_free() < (1 << 20), (before, _hbm_free())
+
+
+def test_stream_lifecycle_frees_hbm(lifecycle_file):
+    """The same for a context that streamed a file through its window cache (the window shard,
+    the two window buffers lent to it in turn, the copy stream): closing the context frees it."""
+    data, of = lifecycle_file
+    window = data.size // 2 + 1  # two windows: both buffers hold bytes at once
+
+    def cycle():
+        c = sb.Context(0)
+        r, _ = c.run_stream(data, of.contig_len, index_start=0, window=window, halo=1 << 16)
+        c.close()
+        assert r["status"] == 0 and r["n_windows"] == 2 and r["count"] == 100_000, r
+
+    cycle()
+    before = _hbm_free()
+    for _ in range(12):
+        cycle()
+    assert before - _hbm_free() < (1 << 20), (before, _hbm_free())
