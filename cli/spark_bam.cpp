@@ -10,6 +10,8 @@
 //   spark-bam index-records BAM [OUT]                        (check/index/IndexRecords.scala)
 //   spark-bam index-bai     BAM [OUT]                        (the .bai samtools index writes; htslib hts.c)
 //   spark-bam view [-h] [-o FILE] BAM                        (the records as SAM text: htsjdk getSAMString)
+//   spark-bam view -b -o OUT [-f INT] [-F INT] [-q INT] [-r ROWS] [--level N] [--index-bai] BAM
+//                                                            (the records that pass, as a BAM gathered on the GPU)
 //   spark-bam check-blocks -s [-r RECORDS] [-l N] BAM        (cli/.../check/blocks/CheckBlocks.scala)
 //   spark-bam htsjdk-rewrite [-r READS] [-b] [-i] [--index-bai] BAM OUT  (cli/.../rewrite/HTSJDKRewrite.scala)
 //
@@ -249,7 +251,25 @@ struct Args {
   std::vector<std::pair<uint64_t, uint64_t>> read_ranges;
   bool has_read_ranges = false, idx_blocks = false, idx_records = false, idx_bai = false;
   bool sam_header = false;  // view -h: the BAM header text first
+  // view -b: BAM output of the records with (flag & -f) == -f, (flag & -F) == 0, mapq >= -q and an
+  // index in -r (read_ranges); --level as sbh_bgzf_compress_level; --index-bai (idx_bai) writes OUT.bai
+  bool bam_out = false;
+  uint32_t flag_require = 0, flag_exclude = 0;
+  int min_mapq = 0, level = SBH_LEVEL_HTSJDK;
 };
+
+// decimal or 0x hex
+long parse_int(const std::string &s) {
+  size_t used = 0;
+  long v = 0;
+  try {
+    v = std::stol(s, &used, 0);
+  } catch (const std::exception &) {
+    used = 0;
+  }
+  if (!used || used != s.size()) throw Error(SBH_E_ARG, "bad integer: " + s);
+  return v;
+}
 
 Args parse(int argc, char **argv) {
   Args a;
@@ -258,7 +278,10 @@ Args parse(int argc, char **argv) {
                 "usage: spark-bam <command> [options] <bam>\n"
                 "  commands: compute-splits count-reads check-bam full-check index-blocks index-records index-bai\n"
                 "            check-blocks htsjdk-rewrite view\n"
-                "  view [-h|--header] [-o FILE] <bam>: the records as SAM text (-h: the header text first)");
+                "  view [-h|--header] [-o FILE] <bam>: the records as SAM text (-h: the header text first)\n"
+                "  view -b -o OUT [-f INT] [-F INT] [-q INT] [-r ROWS] [--level N] [--index-bai] <bam>: the records with\n"
+                "       (flag & f) == f, (flag & F) == 0, mapq >= q and an index in ROWS (a-b,c-d: htsjdk-rewrite's -r)\n"
+                "       as a BAM at deflate level N (5: htsjdk's bytes; -1: the fast coder); --index-bai writes OUT.bai");
   a.cmd = argv[1];
   const bool rewrite = a.cmd == "htsjdk-rewrite";
   std::vector<std::string> pos;
@@ -274,6 +297,13 @@ Args parse(int argc, char **argv) {
     else if (rewrite && t == "--index-bai") a.idx_bai = true;
     else if (a.cmd == "view" && (t == "-h" || t == "--header")) a.sam_header = true;
     else if (a.cmd == "view" && (t == "-o" || t == "--output")) a.out = next();
+    else if (a.cmd == "view" && (t == "-b" || t == "--bam")) a.bam_out = true;
+    else if (a.cmd == "view" && (t == "-f" || t == "--require-flags")) a.flag_require = (uint32_t)parse_int(next());
+    else if (a.cmd == "view" && (t == "-F" || t == "--exclude-flags")) a.flag_exclude = (uint32_t)parse_int(next());
+    else if (a.cmd == "view" && (t == "-q" || t == "--min-mapq")) a.min_mapq = (int)parse_int(next());
+    else if (a.cmd == "view" && (t == "-r" || t == "--read-ranges")) { a.read_ranges = parse_ranges(next()); a.has_read_ranges = true; }
+    else if (a.cmd == "view" && (t == "-l" || t == "--level")) a.level = (int)parse_int(next());
+    else if (a.cmd == "view" && t == "--index-bai") a.idx_bai = true;
     else if (t == "-m" || t == "--max-split-size") { a.split = parse_bytes(next()); a.has_split = true; }
     else if (t == "-s" || t == "--spark-bam") a.s = true;
     else if (t == "-u" || t == "--upstream" || t == "--hadoop-bam") a.u = true;
@@ -290,6 +320,8 @@ Args parse(int argc, char **argv) {
   if (pos.empty()) throw Error(SBH_E_ARG, "missing BAM path");
   a.path = pos[0];
   if (pos.size() > 1) a.out = pos[1];
+  if (a.cmd == "view" && a.bam_out && a.out.empty())
+    throw Error(SBH_E_ARG, "usage: view -b needs -o OUT (a BAM is not written to the terminal)");
   return a;
 }
 
@@ -895,7 +927,12 @@ int index_bai(const Args &a) {
 // resident as index-bai holds it: the eager calls give the record starts, sbh_records_scan
 // decodes from the header's end, sbh_records_sam_scan renders on the device, the fetch brings the
 // text back.  -h: the BAM header text (the l_text bytes after the magic) first, verbatim.
+int view_bam(const Args &a);
+
 int view(const Args &a) {
+  if (a.bam_out) return view_bam(a);
+  if (a.has_read_ranges || a.flag_require || a.flag_exclude || a.min_mapq || a.idx_bai)
+    throw Error(SBH_E_ARG, "view: -f / -F / -q / -r / --index-bai select records for BAM output: they need -b");
   Loaded L(a.path);
   uint64_t seg_end = L.flat;
   for (const sbh_block &b : L.blocks)
@@ -932,6 +969,62 @@ int view(const Args &a) {
   const bool ok = fwrite(text.data(), 1, text.size(), f) == text.size() && fflush(f) == 0;
   if (f != stdout) fclose(f);
   if (!ok) throw Error(SBH_E_ARG, "short write to " + (a.out.empty() ? std::string("stdout") : a.out));
+  return 0;
+}
+
+// view -b: the records that pass the filters as a BAM, whole file resident.  The records are
+// selected and laid out behind the header on the device (sbh_records_bam_scan) and compressed
+// from device memory: only the header and the finished file cross to the host.
+int view_bam(const Args &a) {
+  if (a.out.empty()) throw Error(SBH_E_ARG, "usage: view -b needs -o OUT (a BAM is not written to the terminal)");
+  std::vector<uint8_t> out;
+  uint64_t size = 0, nb = 0;
+  {
+    Loaded L(a.path);
+    uint64_t seg_end = L.flat;
+    for (const sbh_block &b : L.blocks)
+      if (b.flags & SBH_BLOCK_EMPTY) { seg_end = b.ustart; break; }
+    std::vector<uint8_t> head(L.hdr.end);
+    if (L.hdr.end) chk(sbh_read_flat(L.sh, 0, L.hdr.end, head.data()), "read header");
+    sbh_records_sizes rs{};
+    if (seg_end > L.hdr.end) {
+      uint64_t n = 0;
+      chk(sbh_check_eager(L.sh, L.hdr.end, seg_end, a.reads_to_check, nullptr, &n), "eager");
+    }
+    chk(sbh_records_scan(L.sh, L.hdr.end, seg_end, &rs), "records scan");
+    // -r as given -> sorted, disjoint ranges
+    std::vector<std::pair<uint64_t, uint64_t>> rr = a.read_ranges;
+    std::sort(rr.begin(), rr.end());
+    std::vector<uint64_t> rb, re;
+    for (auto &r : rr) {
+      if (!re.empty() && r.first <= re.back()) re.back() = std::max(re.back(), r.second);
+      else { rb.push_back(r.first); re.push_back(r.second); }
+    }
+    sbh_record_filter f{};
+    f.flag_require = a.flag_require;
+    f.flag_exclude = a.flag_exclude;
+    f.min_mapq = a.min_mapq;
+    f.row_begin = rb.data();
+    f.row_end = re.data();
+    f.n_row_ranges = rb.size();
+    sbh_bam_sizes bs{};
+    chk(sbh_records_bam_scan(L.sh, head.data(), head.size(), &f, &bs), "bam scan");
+    out.resize(sbh_bgzf_compress_bound(bs.bytes));
+    chk(sbh_bgzf_compress_level(g_ctx, sbh_records_bam_device_ptr(L.sh), bs.bytes, 1, a.level, out.data(), out.size(), &size,
+                                &nb, nullptr),
+        "bgzf compress");
+  }
+  FILE *f = fopen(a.out.c_str(), "wb");
+  if (!f) throw Error(SBH_E_ARG, "cannot write " + a.out);
+  const bool ok = fwrite(out.data(), 1, size, f) == size;
+  fclose(f);
+  if (!ok) throw Error(SBH_E_ARG, "short write to " + a.out);
+  if (a.idx_bai) {
+    Args ix = a;
+    ix.path = a.out;
+    ix.out.clear();
+    index_bai(ix);
+  }
   return 0;
 }
 

@@ -111,7 +111,8 @@ const char *sbh_last_error(const sbh_ctx *ctx);
  *   SBH_E_INFLATE_SIZE         {block start, expected bytes}  -> IOException (Stream.scala:52-54)
  *   SBH_E_INFLATE_DATA         {block start}  -> DataFormatException
  *   SBH_E_UNSORTED             {virtual offset of the first offending record}  (sbh_bai_scan)
- *   SBH_E_BAD_RECORD           {row of the first malformed record}  (sbh_records_sam_scan only)
+ *   SBH_E_BAD_RECORD           {row of the first malformed record}  (sbh_records_sam_scan and
+ *                              sbh_records_bam_scan only)
  *   anything else              no fields */
 int32_t sbh_last_error_detail(const sbh_ctx *ctx, int32_t *code, int64_t *fields, int32_t cap);
 /* Use a caller-owned hipStream_t (e.g. torch.cuda.current_stream().cuda_stream). */
@@ -627,6 +628,57 @@ int sbh_records_sam_fetch(sbh_shard *sh, char *text /* [text_bytes] */, uint64_t
 int sbh_sam_render_host(const uint8_t *flat, uint64_t flat_size, const uint64_t *starts, uint64_t n,
                         const char *ref_names, const uint64_t *ref_name_off, int32_t n_ref,
                         char *text, uint64_t text_cap, uint64_t *line_off, uint64_t *bad_row);
+
+/* ---- BAM stream ---------------------------------------------------------------------------
+ * Selected records of the last scan as one uncompressed BAM stream in device memory: `head`, then
+ * the kept records' raw bytes [p, p + 4 + block_size) in row order, unchanged (bin is not
+ * recomputed, nothing is re-encoded) -- what sbh_bgzf_compress_level(..., src_on_device = 1, ...)
+ * turns into a BAM file and sbh_bai_scan of that file indexes, without the records leaving HBM.
+ * rows = the rows of the last valid scan on this shard (sbh_records_scan, sbh_records_scan_regions,
+ * sbh_split_records, sbh_split_records_batch), in their order; decode == 0 is enough (only the
+ * record starts and the flat bytes are read).  Rows need not be ascending or distinct in the flat
+ * stream: a record that overlapping BAI chunks deliver twice is written twice.
+ * A row is kept when (flag & flag_require) == flag_require, (flag & flag_exclude) == 0,
+ * mapq >= min_mapq and its index lies in one of the row ranges (csrc/bam_gather_core.h holds the
+ * definition for device and host).  Every row, kept or not, is validated as sbh_records_scan
+ * judges it: its 36 fixed bytes inside the stream, l_seq >= 0, block_size >= 32 + l_read_name +
+ * 4 n_cigar + (l_seq + 1) / 2 + l_seq, its end inside the stream.
+ * head: host memory copied to the front of the stream (the BAM header bytes, or the unfinished
+ * tail of an earlier window's stream when a file is written window by window: BGZF members are
+ * cut every 65498 bytes of the whole stream); rec_off[0] == head_bytes.
+ * The call leaves the scan's rows, columns and SAM text as they are; a new scan or sbh_shard_load
+ * invalidates the BAM stream.  It synchronises the shard's stream before it returns, so the
+ * context-level compress call may follow directly on sbh_records_bam_device_ptr (NULL without a
+ * valid BAM scan).  sbh_records_bam_fetch copies out what is asked for (any pointer may be NULL).
+ * Errors: SBH_E_STATE without a valid scan; SBH_E_ARG for a filter outside the ranges below or
+ * row ranges that are unsorted, overlapping or empty; SBH_E_BAD_RECORD {row} for the first invalid
+ * row -- SBH_E_NEED_HALO instead when that row merely runs past an open shard end (sbh_bai_scan's
+ * rule).  n == 0 or n_kept == 0 gives bytes = head_bytes and rec_off = [head_bytes]. */
+typedef struct {
+  uint32_t flag_require, flag_exclude;   /* both < 65536 */
+  int32_t  min_mapq;                     /* 0..255 */
+  int32_t  pad;
+  const uint64_t *row_begin, *row_end;   /* rows [row_begin[k], row_end[k]) of the last scan: sorted, disjoint,
+                                            non-empty; may reach past n (clipped).  n_row_ranges == 0: every row */
+  uint64_t n_row_ranges;
+} sbh_record_filter;
+typedef struct { uint64_t n, n_kept, bytes; } sbh_bam_sizes;   /* bytes = head_bytes + the kept records' bytes */
+
+int sbh_records_bam_scan(sbh_shard *sh, const uint8_t *head, uint64_t head_bytes,
+                         const sbh_record_filter *filter /* NULL: keep all */, sbh_bam_sizes *out);
+const void *sbh_records_bam_device_ptr(sbh_shard *sh);
+int sbh_records_bam_fetch(sbh_shard *sh, uint8_t *stream /*[bytes]*/, uint64_t *rec_off /*[n_kept+1]*/,
+                          uint64_t *rows /*[n_kept]: the scan row each kept record came from*/);
+/* Bytes [offset, offset + n) of the stream (a window's unfinished tail, without the rest). */
+int sbh_records_bam_read(sbh_shard *sh, uint64_t offset, uint64_t n, uint8_t *out);
+/* HOST ONLY, no context, no GPU (like sbh_sam_render_host): the same stream for the records at
+ * starts[] of a flat BAM stream.  rec_off (room for n + 1) and rows (room for n) may be NULL;
+ * out == NULL: sizes only (*n_kept, rec_off).  SBH_E_BAD_RECORD with *bad_row = the first invalid
+ * row, kept or not; SBH_E_ARG for a bad filter or when out_cap < the stream's bytes. */
+int sbh_bam_gather_host(const uint8_t *flat, uint64_t flat_size, const uint64_t *starts, uint64_t n,
+                        const uint8_t *head, uint64_t head_bytes, const sbh_record_filter *filter,
+                        uint8_t *out, uint64_t out_cap, uint64_t *rec_off, uint64_t *rows,
+                        uint64_t *n_kept, uint64_t *bad_row);
 
 /* ---- BGZF writer -------------------------------------------------
  * The block compressor behind HTSJDKRewrite (cli/src/main/scala/org/hammerlab/bam/rewrite/

@@ -45,6 +45,8 @@ EXPORTS = [
     "sbh_shard_load", "sbh_find_blocks", "sbh_check_stream", "sbh_split_records", "sbh_split_records_batch",
     "sbh_bai_scan", "sbh_bai_fetch", "sbh_bai_edges", "sbh_bai_bound", "sbh_bai_build",
     "sbh_records_sam_scan", "sbh_records_sam_fetch", "sbh_sam_render_host",
+    "sbh_records_bam_scan", "sbh_records_bam_device_ptr", "sbh_records_bam_fetch", "sbh_records_bam_read",
+    "sbh_bam_gather_host",
 ]
 LEVEL_HTSJDK, LEVEL_FAST = 5, -1  # sbh_bgzf_compress_level: htsjdk's zlib level 5 / this library's own coder
 
@@ -122,6 +124,15 @@ class SbhBaiSizes(C.Structure):
 
 class SbhSamSizes(C.Structure):
     _fields_ = [("n", C.c_uint64), ("text_bytes", C.c_uint64), ("n_host", C.c_uint64)]
+
+
+class SbhRecordFilter(C.Structure):
+    _fields_ = [("flag_require", C.c_uint32), ("flag_exclude", C.c_uint32), ("min_mapq", C.c_int32),
+                ("pad", C.c_int32), ("row_begin", C.c_void_p), ("row_end", C.c_void_p), ("n_row_ranges", C.c_uint64)]
+
+
+class SbhBamSizes(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("n_kept", C.c_uint64), ("bytes", C.c_uint64)]
 
 
 class SbhRecordsOut(C.Structure):  # host buffers (sbh_records_out); NULL = not copied
@@ -253,6 +264,10 @@ def lib():
         "sbh_records_sam_scan": [P, P, P, I32, C.POINTER(SbhSamSizes)],
         "sbh_records_sam_fetch": [P, P, P],
         "sbh_sam_render_host": [P, U64, P, U64, P, P, I32, P, U64, P, PU64],
+        "sbh_records_bam_scan": [P, P, U64, C.POINTER(SbhRecordFilter), C.POINTER(SbhBamSizes)],
+        "sbh_records_bam_fetch": [P, P, P, P],
+        "sbh_records_bam_read": [P, U64, U64, P],
+        "sbh_bam_gather_host": [P, U64, P, U64, P, U64, C.POINTER(SbhRecordFilter), P, U64, P, P, PU64, PU64],
         "sbh_bgzf_compress": [P, P, U64, I32, P, U64, PU64, PU64, C.POINTER(C.c_float)],
         "sbh_bgzf_compress_level": [P, P, U64, I32, I32, P, U64, PU64, PU64, C.POINTER(C.c_float)],
     }
@@ -272,7 +287,7 @@ def lib():
     L.sbh_last_error_detail.restype = I32
     L.sbh_version.argtypes = []
     L.sbh_version.restype = C.c_char_p
-    for name in ("sbh_shard_comp_device_ptr", "sbh_flat_device_ptr"):
+    for name in ("sbh_shard_comp_device_ptr", "sbh_flat_device_ptr", "sbh_records_bam_device_ptr"):
         getattr(L, name).argtypes = [P]
         getattr(L, name).restype = P
     _lib = L

@@ -309,6 +309,126 @@ def view(path_or_bytes, header=False, out=None, window=None, ctx=None, reads_to_
     return b"".join(parts) if out is None else total
 
 
+BGZF_PAYLOAD = 65498  # uncompressed bytes per member of the writer (htsjdk BlockCompressedOutputStream)
+BGZF_EOF_BYTES = 28
+
+
+def view_bam(path_or_bytes, out=None, flag_require=0, flag_exclude=0, min_mapq=0, rows=None, intervals=None,
+             bai=None, level=5, window=None, index=False, ctx=None, reads_to_check=DEFAULT_READS_TO_CHECK):
+    """The file's records that pass the filters, as a BAM file: the header, then every record with
+    (flag & flag_require) == flag_require, (flag & flag_exclude) == 0, mapq >= min_mapq and -- with
+    `rows`, a range or a collection of ints -- a record index in it, byte for byte as stored, cut
+    into 65498-byte BGZF members at `level` (htsjdk_rewrite's levels).  The records are selected
+    and laid out on the GPU (Shard.records_bam) and compressed from device memory: they do not
+    come to the host between inflate and deflate.
+
+    Whole file: iter_reads' walk, `window` compressed bytes at a time; rows count records across
+    the windows.  `intervals` (load_bam_intervals' strings; `bai` as there): only the records
+    load_bam_intervals returns, in its order, the other filters on top; rows then count those.
+
+    Members are cut every 65498 bytes of the whole stream, so a window compresses the largest
+    multiple of that from the device and hands the rest (< 65498 bytes) to the next window's
+    stream as its head; the last tail and the EOF member close the file.  The bytes do not depend
+    on `window`.
+
+    Returns the file bytes; with `out` (a path or a binary file object) writes them and returns
+    the byte count.  index=True: also the `.bai` of the result (bai.build_bai) -- returned as
+    (bam, bai), written to out + ".bai" when out is a path, or returned as (count, bai) when out
+    is a file object."""
+    data = _file_array(path_or_bytes)
+    own_ctx = ctx is None
+    ctx = ctx or Context(0)
+    from .records import row_ranges
+    want = None if rows is None else row_ranges(rows)
+    pieces = []
+    state = {"tail": None, "row_base": 0}
+
+    def gather(sh):
+        """The scan on sh -> (compressed whole members, the new tail, rows scanned); nothing is
+        committed here: a window that has to run again with a larger halo calls this again."""
+        base = state["row_base"]
+        f = {"flag_require": flag_require, "flag_exclude": flag_exclude, "min_mapq": min_mapq}
+        if want is not None:
+            f["rows"] = [(max(a - base, 0), b - base) for a, b in want if b > base]
+        sh.records_bam(state["tail"], f, want_bytes=False)
+        whole = sh.bam_size - sh.bam_size % BGZF_PAYLOAD
+        comp = b""
+        if whole:
+            comp = ctx.bgzf_compress(sh.bam_ptr(), whole, level=level)[0][:-BGZF_EOF_BYTES].tobytes()
+        return comp, sh.bam_read(whole, sh.bam_size).tobytes(), sh.bam_n
+
+    def commit(got):
+        comp, tail, n = got
+        pieces.append(comp)
+        state["tail"] = tail
+        state["row_base"] += n
+
+    try:
+        state["tail"] = _header_flat(ctx, data)
+        if intervals is None:
+            def deliver(sh, f, E, names):
+                sh.records_scan(f, E)
+                return gather(sh)
+            for got in _iter_windows(data, deliver, window, ctx=ctx, reads_to_check=reads_to_check):
+                commit(got)
+        else:
+            from .intervals import iter_interval_groups
+
+            def deliver_group(sh, chunks_flat, ivs):
+                sh.records_regions(chunks_flat, ivs, fetch=False)
+                return gather(sh)
+            for got in iter_interval_groups(path_or_bytes, intervals, deliver_group, ctx=ctx, bai=bai,
+                                            reads_to_check=reads_to_check)[0]:
+                commit(got)
+        # the last members (what is left is below one payload) and the EOF member
+        pieces.append(ctx.bgzf_compress(np.frombuffer(state["tail"], dtype=np.uint8), level=level)[0].tobytes())
+        result = b"".join(pieces)
+        bai_bytes = None
+        if index:
+            from .bai import build_bai
+            bai_bytes = build_bai(result, ctx=ctx)
+    finally:
+        if own_ctx:
+            ctx.close()
+    if out is None:
+        return (result, bai_bytes) if index else result
+    if isinstance(out, (str, os.PathLike)):
+        with open(out, "wb") as fh:
+            fh.write(result)
+        if index:
+            with open(str(out) + ".bai", "wb") as fh:
+                fh.write(bai_bytes)
+        return len(result)
+    out.write(result)
+    return (len(result), bai_bytes) if index else len(result)
+
+
+def _header_flat(ctx, data):
+    """The BAM header's bytes (magic, text, reference dictionary: flat[0, header_end)), from the
+    file's leading blocks inflated on the device."""
+    size = int(data.size)
+    n = min(size, 1 << 20)
+    while True:
+        sh = ctx.shard(np.ascontiguousarray(data[:n]), file_offset=0, file_size=size)
+        try:
+            sh.index(0)
+            sh.inflate()
+            flat = sh.read_flat(0, sh.flat_size)
+        finally:
+            sh.close()
+        try:
+            end = parse_bam_header(flat)[2]
+        except (IndexError, ValueError):
+            end = None
+            if n >= size:
+                raise
+        if end is not None and end <= flat.size:
+            return flat[:end].tobytes()
+        if n >= size:
+            raise SparkBamError(12, "truncated BAM header")
+        n = min(size, n * 4)
+
+
 def header_text(ctx, data):
     """The BAM header's text (the l_text bytes after the magic), from the file's leading blocks
     inflated on the device."""

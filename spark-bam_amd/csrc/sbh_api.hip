@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "sam_core.h"
+#include "bam_gather_core.h"
 #include "sbh_internal.h"
 
 namespace sbh {
@@ -283,6 +284,16 @@ struct sbh_shard {
     sbh_sam_sizes sz{};
     bool valid = false;
   } sam;
+  // BAM stream of the last scan's selected rows (sbh_records_bam_scan / fetch): per-row lengths and
+  // their prefix, keep | run head << 32 and its prefix, the kept rows' offsets and indices, the
+  // runs' (output, U) offsets, the device copy of the row ranges, the stream
+  struct Bam {
+    DBuf<uint64_t> len, off, kh, khpre, rec_off, rows, run_dst, run_src, ranges;
+    DBuf<uint8_t> out;
+    sbh_bam_sizes sz{};
+    uint64_t head_bytes = 0;
+    bool valid = false;
+  } bam;
   std::vector<int32_t> h_ctg;  // host copy of the contig lengths (sbh_set_contigs)
   // batched splits (sbh_split_starts) and check-bam truth (sbh_check_records)
   DBuf<uint64_t> sp_start, sp_end, sp_first, sp_E, sp_vpos;
@@ -316,7 +327,7 @@ struct sbh_shard {
     return DevBlocks{b_cstart.p, b_csize.p, b_hsize.p, b_usize.p, b_ustart.p, b_flags.p, b_status.p, b_ntok.p};
   }
 
-  // What is not a DBuf is let go here; the DBuf members (and rec, bai, sam) free themselves after
+  // What is not a DBuf is let go here; the DBuf members (and rec, bai, sam, bam) free themselves after
   // this body, in their own destructors -- that is, after the streams below are gone.  That order
   // is sound only because the shard's stream is synchronised first (every entry point joins the
   // other streams into it before it returns), so nothing on the device still uses the memory;
@@ -427,6 +438,7 @@ static void resident_changed(sbh_shard *sh, uint64_t file_off, uint64_t n) {
   sh->rec.valid = false;
   sh->bai.valid = false;
   sh->sam.valid = false;
+  sh->bam.valid = false;
   sh->ncand = 0;
   sh->scan_from = ~0ull;
   sh->hb.clear();
@@ -2607,6 +2619,7 @@ int sbh_records_scan(sbh_shard *sh, uint64_t first, uint64_t end_flat, sbh_recor
   auto &R = sh->rec;
   R.valid = false;
   sh->sam.valid = false;
+  sh->bam.valid = false;
   const uint64_t total = seg_end_of(sh, first);
   const uint64_t E = std::min(std::min(end_flat, sh->utotal), total);
   uint64_t n = 0;
@@ -2636,6 +2649,7 @@ int sbh_split_records(sbh_shard *sh, uint64_t start, uint64_t end, int32_t k, in
   auto &R = sh->rec;
   R.valid = R.decoded = false;
   sh->sam.valid = false;
+  sh->bam.valid = false;
   uint64_t b = 0;
   rc = sbh_find_block_start(sh, start, k, &b);
   if (rc) return rc;
@@ -2730,6 +2744,7 @@ int sbh_split_records_batch(sbh_shard *sh, const uint64_t *starts, const uint64_
   auto &R = sh->rec;
   R.valid = R.decoded = false;
   sh->sam.valid = false;
+  sh->bam.valid = false;
   // the chain starts at the first split whose FindBlockStart succeeds; a split before it keeps
   // its own failure (HeaderSearchFailedException(path, start, positionsAttempted))
   uint64_t j0 = 0, b = 0;
@@ -2978,6 +2993,7 @@ int sbh_records_scan_regions(sbh_shard *sh, const uint64_t *chunk_begin, const u
   auto &R = sh->rec;
   R.valid = false;
   sh->sam.valid = false;
+  sh->bam.valid = false;
   std::vector<uint64_t> cn(n_chunks, 0), cfirst(n_chunks, 0), cE(n_chunks, 0), ctot(n_chunks, 0);
   std::vector<int32_t> can(n_chunks, 0);
   uint64_t n = 0;
@@ -3205,6 +3221,125 @@ int sbh_sam_render_host(const uint8_t *flat, uint64_t flat_size, const uint64_t 
   uint64_t bad = sbh_sam::NO_ROW;
   const int rc = sbh_sam::render_host(flat, flat_size, starts, n, sbh_sam::Refs{ref_names, ref_name_off, n_ref}, text,
                                       text_cap, line_off, &bad);
+  if (bad_row) *bad_row = bad;
+  return rc == 0 ? SBH_OK : rc == 1 ? SBH_E_BAD_RECORD : SBH_E_ARG;
+}
+
+// ---- BAM stream (bam_gather.hip; validity and predicate in bam_gather_core.h) -----------------
+// Keep pass, two scans, index pass -- all launched before anything is read back, so one round trip
+// brings (first invalid row, first row past the end, kept bytes, kept rows | runs << 32); then the
+// stream is allocated, the head copied in and the runs copied behind it.
+static bool bam_filter_of(const sbh_record_filter *f, sbh_bam::Filter *F) {
+  *F = sbh_bam::Filter{0, 0, 0, nullptr, nullptr, 0};
+  if (f) *F = sbh_bam::Filter{f->flag_require, f->flag_exclude, f->min_mapq, f->row_begin, f->row_end, f->n_row_ranges};
+  return sbh_bam::filter_ok(*F);
+}
+
+int sbh_records_bam_scan(sbh_shard *sh, const uint8_t *head, uint64_t head_bytes, const sbh_record_filter *filter,
+                         sbh_bam_sizes *out) {
+  if (!sh || !out || (head_bytes && !head)) return SBH_E_ARG;
+  sbh_ctx *ctx = sh->ctx;
+  auto &R = sh->rec;
+  auto &B = sh->bam;
+  if (!R.valid) return fail(ctx, SBH_E_STATE, "records_bam_scan without a records scan");
+  sbh_bam::Filter F;
+  if (!bam_filter_of(filter, &F))
+    return fail(ctx, SBH_E_ARG, "record filter: flags < 65536, 0 <= min_mapq <= 255, row ranges sorted, disjoint and non-empty");
+  const uint64_t n = R.sz.n, nr = F.n_row_ranges;
+  if (n >= 0xffffffffull)
+    return fail(ctx, SBH_E_ARG, "records_bam_scan: %llu rows in one scan (scan in windows)", (unsigned long long)n);
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  hipStream_t st = sh->st;
+  B.valid = false;
+  uint64_t bytes = head_bytes, n_kept = 0, n_runs = 0;
+  for (auto *b : {&B.len, &B.off, &B.kh, &B.khpre, &B.rec_off, &B.rows, &B.run_dst, &B.run_src}) HIPCHK(ctx, b->ensure(n + 1));
+  if (n) {
+    HIPCHK(ctx, B.ranges.ensure(2 * nr));
+    if (nr) {
+      HIPCHK(ctx, hipMemcpyAsync(B.ranges.p, F.row_begin, 8 * nr, hipMemcpyHostToDevice, st));
+      HIPCHK(ctx, hipMemcpyAsync(B.ranges.p + nr, F.row_end, 8 * nr, hipMemcpyHostToDevice, st));
+    }
+    HIPCHK(ctx, sh->tmp.ensure(scan_tmp_words(n + 1)));
+    HIPCHK(ctx, hipMemsetAsync(B.len.p + n, 0, 8, st));
+    HIPCHK(ctx, hipMemsetAsync(B.kh.p + n, 0, 8, st));
+    unsigned long long *bad = sh->ctr.p + ctr::BAM_BAD;  // (BAM_PAST is the next word)
+    static_assert(ctr::BAM_PAST == ctr::BAM_BAD + 1, "one memset, one copy");
+    HIPCHK(ctx, hipMemsetAsync(bad, 0xff, 16, st));
+    HIPCHK(ctx, launch_bam_keep(sh->U.p, R.pos.p, n, sh->utotal, F.flag_require, F.flag_exclude, F.min_mapq, B.ranges.p,
+                                B.ranges.p + nr, nr, B.len.p, B.kh.p, bad, bad + 1, st));
+    HIPCHK(ctx, scan_exclusive_u64(B.len.p, B.off.p, n + 1, sh->tmp.p, st));
+    HIPCHK(ctx, scan_exclusive_u64(B.kh.p, B.khpre.p, n + 1, sh->tmp.p, st));
+    HIPCHK(ctx, launch_bam_index(R.pos.p, B.off.p, B.kh.p, B.khpre.p, n, head_bytes, B.rec_off.p, B.rows.p, B.run_dst.p,
+                                 B.run_src.p, st));
+    HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::BAM_BAD, bad, 16, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::H_BAM_BYTES, B.off.p + n, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::H_BAM_KH, B.khpre.p + n, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    const uint64_t row = sh->h_ctr[ctr::BAM_BAD];
+    if (row != ~0ull) {
+      // only a record that runs past the resident bytes can be cured by more of them
+      if (sh->h_ctr[ctr::BAM_PAST] == row && !sh->at_eof)
+        return fail(ctx, SBH_E_NEED_HALO, "record %llu of the scan may run past the shard", (unsigned long long)row);
+      return fail_with(ctx, SBH_E_BAD_RECORD, {(int64_t)row}, "record %llu of the scan does not fit its block or the stream",
+                       (unsigned long long)row);
+    }
+    bytes += sh->h_ctr[ctr::H_BAM_BYTES];
+    n_kept = sh->h_ctr[ctr::H_BAM_KH] & 0xffffffffull;
+    n_runs = sh->h_ctr[ctr::H_BAM_KH] >> 32;
+  } else {
+    HIPCHK(ctx, hipMemcpyAsync(B.rec_off.p, &head_bytes, 8, hipMemcpyHostToDevice, st));
+  }
+  HIPCHK(ctx, B.out.ensure(bytes + 16));
+  if (head_bytes) HIPCHK(ctx, hipMemcpyAsync(B.out.p, head, head_bytes, hipMemcpyHostToDevice, st));
+  HIPCHK(ctx, launch_bam_copy(sh->U.p, B.run_dst.p, B.run_src.p, n_runs, head_bytes, bytes, B.out.p, st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
+  B.sz = sbh_bam_sizes{n, n_kept, bytes};
+  B.head_bytes = head_bytes;
+  B.valid = true;
+  *out = B.sz;
+  return SBH_OK;
+}
+
+const void *sbh_records_bam_device_ptr(sbh_shard *sh) { return sh && sh->bam.valid ? sh->bam.out.p : nullptr; }
+
+int sbh_records_bam_fetch(sbh_shard *sh, uint8_t *stream, uint64_t *rec_off, uint64_t *rows) {
+  if (!sh) return SBH_E_ARG;
+  sbh_ctx *ctx = sh->ctx;
+  auto &B = sh->bam;
+  if (!B.valid) return fail(ctx, SBH_E_STATE, "records_bam_fetch without a records_bam_scan");
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  hipStream_t st = sh->st;
+  if (stream && B.sz.bytes) HIPCHK(ctx, hipMemcpyAsync(stream, B.out.p, B.sz.bytes, hipMemcpyDeviceToHost, st));
+  if (rec_off) HIPCHK(ctx, hipMemcpyAsync(rec_off, B.rec_off.p, 8 * (B.sz.n_kept + 1), hipMemcpyDeviceToHost, st));
+  if (rows && B.sz.n_kept) HIPCHK(ctx, hipMemcpyAsync(rows, B.rows.p, 8 * B.sz.n_kept, hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
+  return SBH_OK;
+}
+
+int sbh_records_bam_read(sbh_shard *sh, uint64_t offset, uint64_t n, uint8_t *out) {
+  if (!sh || (n && !out)) return SBH_E_ARG;
+  sbh_ctx *ctx = sh->ctx;
+  auto &B = sh->bam;
+  if (!B.valid) return fail(ctx, SBH_E_STATE, "records_bam_read without a records_bam_scan");
+  if (offset > B.sz.bytes || n > B.sz.bytes - offset) return fail(ctx, SBH_E_ARG, "records_bam_read past the stream");
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  if (n) HIPCHK(ctx, hipMemcpyAsync(out, B.out.p + offset, n, hipMemcpyDeviceToHost, sh->st));
+  HIPCHK(ctx, hipStreamSynchronize(sh->st));
+  return SBH_OK;
+}
+
+int sbh_bam_gather_host(const uint8_t *flat, uint64_t flat_size, const uint64_t *starts, uint64_t n, const uint8_t *head,
+                        uint64_t head_bytes, const sbh_record_filter *filter, uint8_t *out, uint64_t out_cap,
+                        uint64_t *rec_off, uint64_t *rows, uint64_t *n_kept, uint64_t *bad_row) {
+  if ((!flat && flat_size) || (!starts && n) || (!head && head_bytes) || !n_kept) return SBH_E_ARG;
+  sbh_bam::Filter F;
+  if (!bam_filter_of(filter, &F)) return SBH_E_ARG;
+  uint64_t bad = sbh_bam::NO_ROW, bytes = 0;
+  const int rc = sbh_bam::gather_host(flat, flat_size, starts, n, head, head_bytes, F, out, out_cap, rec_off, rows, n_kept,
+                                      &bytes, &bad);
   if (bad_row) *bad_row = bad;
   return rc == 0 ? SBH_OK : rc == 1 ? SBH_E_BAD_RECORD : SBH_E_ARG;
 }

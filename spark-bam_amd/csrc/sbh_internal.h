@@ -191,6 +191,20 @@ hipError_t launch_sam_gather(const uint8_t *U, const uint64_t *pos, const uint64
                              uint64_t m, uint8_t *out, hipStream_t st);
 hipError_t launch_sam_scatter(const uint64_t *rows, const uint64_t *vals, uint64_t m, uint64_t n, uint64_t *len,
                               hipStream_t st);
+// BAM stream of selected rows (bam_gather.hip; validity and predicate in bam_gather_core.h).  len / kh:
+// n + 1 words (the caller zeroes entry n); bad / past preset to ~0: the first invalid row, the first
+// row invalid only because the stream ends too early.  off / khpre: the exclusive scans of len / kh
+// (kh = keep | run head << 32, so n < 2^32).  rec_off, rows, run_dst, run_src: n + 1 words.
+hipError_t launch_bam_keep(const uint8_t *U, const uint64_t *pos, uint64_t n, uint64_t total, uint32_t flag_require,
+                           uint32_t flag_exclude, int32_t min_mapq, const uint64_t *row_begin, const uint64_t *row_end,
+                           uint64_t n_row_ranges, uint64_t *len, uint64_t *kh, unsigned long long *bad,
+                           unsigned long long *past, hipStream_t st);
+hipError_t launch_bam_index(const uint64_t *pos, const uint64_t *off, const uint64_t *kh, const uint64_t *khpre,
+                            uint64_t n, uint64_t head_bytes, uint64_t *rec_off, uint64_t *rows, uint64_t *run_dst,
+                            uint64_t *run_src, hipStream_t st);
+// out[head_bytes, bytes) from the runs; reads U below (the last run's end) + 32
+hipError_t launch_bam_copy(const uint8_t *U, const uint64_t *run_dst, const uint64_t *run_src, uint64_t n_runs,
+                           uint64_t head_bytes, uint64_t bytes, uint8_t *out, hipStream_t st);
 // BGZF footer CRC32 of every inflated, non-truncated block (crc.hip).
 hipError_t launch_block_crc(const uint8_t *comp, DevBlocks bl, uint64_t nblocks, const uint8_t *U,
                             unsigned long long *n_bad, unsigned long long *first_bad, hipStream_t st);
@@ -293,6 +307,9 @@ constexpr uint32_t H_BAI_NRUNS = 43, H_BAI_AUX = 44, H_BAI_FIRST_EDGE = 45, H_BA
 constexpr uint32_t H_BAI_BAD_VPOS = 47;
 // SAM scan (sbh_records_sam_scan): first malformed row; h_ctr only: host rows, text bytes
 constexpr uint32_t SAM_BAD = 48, H_SAM_NHOST = 49, H_SAM_TOTAL = 50;
+// BAM scan (sbh_records_bam_scan): first invalid row, first row that only runs past the stream's
+// end; h_ctr only: the kept records' bytes, kept rows | runs << 32
+constexpr uint32_t BAM_BAD = 51, BAM_PAST = 52, H_BAM_BYTES = 53, H_BAM_KH = 54;
 // inflate status (launch_first_bad): the first block whose status is not INF_OK
 constexpr uint32_t FIRST_BAD = 100;
 // h_ctr only: that block's status (u32), fetched after the run's copy of [0, CTR_RUN_WORDS)

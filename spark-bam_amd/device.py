@@ -5,9 +5,9 @@ import weakref
 
 import numpy as np
 
-from .records import pack_ref_names, record_columns
+from .records import pack_ref_names, record_columns, record_filter
 
-from ._lib import (SBH_OK, SbhBaiSizes, SbhBatchSplit, SbhBlock, SbhCheckOpts, SbhCheckResult, SbhRecordsOut,
+from ._lib import (SBH_OK, SbhBaiSizes, SbhBamSizes, SbhBatchSplit, SbhBlock, SbhCheckOpts, SbhCheckResult, SbhRecordsOut,
                    SbhRecordsSizes, SbhSamSizes, SbhShardResult, SbhSplitBatchResult, SbhSplitRecordsResult,
                    SbhStreamOpts, SbhStreamResult, SparkBamError, error_for, lib)
 
@@ -488,11 +488,12 @@ class Shard:
         self._c(lib().sbh_records_scan(self.h, first_flat, end_flat, C.byref(sz)))
         return self._records_fetch(sz)
 
-    def records_regions(self, chunks_flat, intervals):
+    def records_regions(self, chunks_flat, intervals, fetch=True):
         """loadBamIntervals' per-chunk record streams + region filter on the GPU
         (CanLoadBam.scala:123-152): chunks_flat = [(begin_flat, end_flat)] in chunk order;
         intervals = [(ref_idx, begin, end)] 0-based half-open, sorted and disjoint.
-        Returns the kept records' columns (same layout as records())."""
+        Returns the kept records' columns (same layout as records()); fetch=False leaves them
+        on the device (for records_sam / records_bam) and returns the number of records."""
         cb = np.ascontiguousarray([c[0] for c in chunks_flat], dtype=np.uint64)
         ce = np.ascontiguousarray([c[1] for c in chunks_flat], dtype=np.uint64)
         ir = np.ascontiguousarray([i[0] for i in intervals], dtype=np.int32)
@@ -501,7 +502,7 @@ class Shard:
         sz = SbhRecordsSizes()
         self._c(lib().sbh_records_scan_regions(self.h, _ptr(cb), _ptr(ce), cb.size, _ptr(ir), _ptr(ib),
                                                _ptr(ie), ir.size, C.byref(sz)))
-        return self._records_fetch(sz)
+        return self._records_fetch(sz) if fetch else sz.n
 
     def split_records(self, start, end, bgzf_blocks_to_check=5, reads_to_check=10, max_read_size=100000000,
                       decode=True, flat_out=None):
@@ -595,6 +596,43 @@ class Shard:
         line_off = np.zeros(sz.n + 1, dtype=np.uint64)
         self._c(lib().sbh_records_sam_fetch(self.h, _ptr(text) if text.size else None, _ptr(line_off)))
         return text, line_off
+
+    def records_bam(self, head=b"", filter=None, want_bytes=True):
+        """The rows of the last scan on this shard that `filter` keeps, as one uncompressed BAM
+        stream built on the GPU (sbh_records_bam_scan + sbh_records_bam_fetch): `head` (the BAM
+        header bytes, or an earlier window's unfinished tail), then the kept records' raw bytes
+        in row order.  filter: None or a dict (records.record_filter: flag_require, flag_exclude,
+        min_mapq, rows).  Returns (stream uint8, rec_off uint64 [n_kept + 1], rows uint64
+        [n_kept]: the scan row of each kept record).  want_bytes=False returns None and leaves the
+        stream on the device: bam_ptr() / bam_size are what Context.bgzf_compress takes.
+        `self.bam_n` / `self.bam_n_kept`: rows scanned and kept."""
+        hd = np.frombuffer(bytes(head), dtype=np.uint8)
+        f, keep = record_filter(filter)
+        sz = SbhBamSizes()
+        self._c(lib().sbh_records_bam_scan(self.h, _ptr(hd) if hd.size else None, int(hd.size),
+                                           C.byref(f) if f is not None else None, C.byref(sz)))
+        del keep
+        self.bam_n, self.bam_n_kept, self.bam_size = int(sz.n), int(sz.n_kept), int(sz.bytes)
+        if not want_bytes:
+            return None
+        stream = np.empty(sz.bytes, dtype=np.uint8)
+        rec_off = np.zeros(sz.n_kept + 1, dtype=np.uint64)
+        rows = np.zeros(sz.n_kept, dtype=np.uint64)
+        self._c(lib().sbh_records_bam_fetch(self.h, _ptr(stream) if stream.size else None, _ptr(rec_off),
+                                            _ptr(rows) if rows.size else None))
+        return stream, rec_off, rows
+
+    def bam_ptr(self):
+        """Device pointer of the last records_bam stream (sbh_records_bam_device_ptr; None when a
+        new scan or load has invalidated it)."""
+        return lib().sbh_records_bam_device_ptr(self.h)
+
+    def bam_read(self, begin, end):
+        """Bytes [begin, end) of the last records_bam stream."""
+        out = np.empty(int(end) - int(begin), dtype=np.uint8)
+        if out.size:
+            self._c(lib().sbh_records_bam_read(self.h, int(begin), int(out.size), _ptr(out)))
+        return out
 
     def bai_scan(self, first_flat, end_flat):
         """The BAI runs and linear-index minima of the records from first_flat while the start

@@ -287,6 +287,29 @@ def load_bam_intervals(path, intervals, split_size=DEFAULT_SPLIT_SIZE,
     bai: the index as a path or bytes; None reads path + ".bai"; the string "build" builds it
     in memory on the same context (bai.build_bai; in windows for a file too large to hold
     resident), for a BAM that has no index file."""
+    batches, (names, chunks, parts) = iter_interval_groups(
+        path, intervals, lambda sh, chunks_flat, ivs: sh.records_regions(chunks_flat, ivs), split_size,
+        estimated_compression_ratio, ctx, bai, reads_to_check, halo, merge_gap)
+    cols = _concat(list(batches))
+    # per-partition counts: a record belongs to the chunk whose [start, end) holds it
+    starts = np.asarray([c.start.to_htsjdk() for c in chunks], dtype=np.uint64)
+    which = np.searchsorted(starts, cols["vpos"], side="right") - 1
+    per_chunk = np.bincount(which, minlength=len(chunks)) if len(chunks) else np.zeros(0, np.int64)
+    counts, k = [], 0
+    for g in parts:
+        counts.append(int(per_chunk[k:k + len(g)].sum()))
+        k += len(g)
+    return IntervalReads(Reads(cols, names), parts, counts)
+
+
+def iter_interval_groups(path, intervals, deliver, split_size=DEFAULT_SPLIT_SIZE,
+                         estimated_compression_ratio=DEFAULT_COMPRESSION_RATIO, ctx=None, bai=None,
+                         reads_to_check=DEFAULT_READS_TO_CHECK, halo=1 << 18, merge_gap=1 << 20):
+    """load_bam_intervals' walk: the intervals' BAI chunks, grouped into device shards, each group
+    indexed, inflated and eager-checked; deliver(shard, chunks_flat, ivs) turns a group into what
+    is yielded (it runs again when the group is redone with a larger halo).  Returns (generator
+    of the groups' results in chunk order, (contig names, chunks, chunk partitions)); the work of
+    the generator runs as it is consumed, and it closes a context it created when it ends."""
     from .sharded import bytes_reader, file_reader, read_header
     build = isinstance(bai, str) and bai == "build"
     index = None if build else read_bai(bai if bai is not None else str(path) + ".bai")
@@ -314,42 +337,40 @@ def load_bam_intervals(path, intervals, split_size=DEFAULT_SPLIT_SIZE,
                 groups[-1][2].append(k)
             else:
                 groups.append([lo, hi, [k]])
-        batches = []
-        for lo, hi, ks in groups:
-            h = halo
-            while True:
-                end = min(size, hi + h)
-                sh = ctx.shard(read(lo, end), file_offset=lo, file_size=size)
-                try:
-                    sh.index(lo)
-                    sh.inflate()
-                    sh.set_contigs(lens)
-                    fl = [(_flat_of_pos(sh, chunks[k].start), _flat_of_pos(sh, chunks[k].end)) for k in ks]
-                    a, b = min(f[0] for f in fl), min(max(f[1] for f in fl), sh.flat_size)
-                    if b > a:
-                        sh.check_eager(a, b, reads_to_check, want_bits=False)
-                    cols = sh.records_regions(fl, ivs)
-                    batches.append(cols)
-                    break
-                except SparkBamError as err:
-                    if err.code not in (SBH_E_NEED_HALO, SBH_E_BAD_RECORD, SBH_E_NOT_FOUND) or end >= size:
-                        raise
-                    h *= 4
-                finally:
-                    sh.close()
-        cols = _concat(batches)
-        # per-partition counts: a record belongs to the chunk whose [start, end) holds it
-        starts = np.asarray([c.start.to_htsjdk() for c in chunks], dtype=np.uint64)
-        which = np.searchsorted(starts, cols["vpos"], side="right") - 1
-        per_chunk = np.bincount(which, minlength=len(chunks)) if len(chunks) else np.zeros(0, np.int64)
-        counts, k = [], 0
-        for g in parts:
-            counts.append(int(per_chunk[k:k + len(g)].sum()))
-            k += len(g)
-        return IntervalReads(Reads(cols, names), parts, counts)
-    finally:
+    except BaseException:
         if own_ctx:
             ctx.close()
+        raise
+
+    def run():
+        try:
+            for lo, hi, ks in groups:
+                h = halo
+                while True:
+                    end = min(size, hi + h)
+                    sh = ctx.shard(read(lo, end), file_offset=lo, file_size=size)
+                    try:
+                        sh.index(lo)
+                        sh.inflate()
+                        sh.set_contigs(lens)
+                        fl = [(_flat_of_pos(sh, chunks[k].start), _flat_of_pos(sh, chunks[k].end)) for k in ks]
+                        a, b = min(f[0] for f in fl), min(max(f[1] for f in fl), sh.flat_size)
+                        if b > a:
+                            sh.check_eager(a, b, reads_to_check, want_bits=False)
+                        got = deliver(sh, fl, ivs)
+                        break
+                    except SparkBamError as err:
+                        if err.code not in (SBH_E_NEED_HALO, SBH_E_BAD_RECORD, SBH_E_NOT_FOUND) or end >= size:
+                            raise
+                        h *= 4
+                    finally:
+                        sh.close()
+                yield got
+        finally:
+            if own_ctx:
+                ctx.close()
+
+    return run(), (names, chunks, parts)
 
 
 def _flat_of_pos(shard, pos):

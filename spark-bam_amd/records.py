@@ -155,6 +155,74 @@ def sam_text_host(flat, starts, ref_names, want_text=True):
     return text, line_off
 
 
+def record_filter(filter):
+    """sbh_record_filter from None (keep all) or a dict with any of flag_require, flag_exclude,
+    min_mapq and rows -- [(begin, end), ...] half-open row ranges, sorted and disjoint.  Returns
+    (ctypes struct or None, the arrays it points into)."""
+    from ._lib import SbhRecordFilter
+    if filter is None:
+        return None, ()
+    unknown = set(filter) - {"flag_require", "flag_exclude", "min_mapq", "rows"}
+    if unknown:
+        raise ValueError("record filter: unknown keys %s" % sorted(unknown))
+    rows = filter.get("rows")
+    rb = np.ascontiguousarray([a for a, _ in rows] if rows is not None else [], dtype=np.uint64)
+    re_ = np.ascontiguousarray([b for _, b in rows] if rows is not None else [], dtype=np.uint64)
+    if rows is not None and not rb.size:  # no rows asked for: one range no row lies in
+        rb, re_ = np.asarray([2 ** 64 - 2], np.uint64), np.asarray([2 ** 64 - 1], np.uint64)
+    f = SbhRecordFilter(int(filter.get("flag_require", 0)) & 0xFFFFFFFF, int(filter.get("flag_exclude", 0)) & 0xFFFFFFFF,
+                        int(filter.get("min_mapq", 0)), 0, rb.ctypes.data if rb.size else None,
+                        re_.ctypes.data if rb.size else None, int(rb.size))
+    return f, (rb, re_)
+
+
+def row_ranges(rows):
+    """Sorted, disjoint half-open ranges [(begin, end), ...] holding exactly the given row
+    indices (a range, or any iterable of ints; duplicates count once)."""
+    if isinstance(rows, range) and rows.step == 1:
+        return [(rows.start, rows.stop)] if rows.stop > rows.start else []
+    a = np.unique(np.fromiter((int(i) for i in rows), dtype=np.int64))
+    if not a.size:
+        return []
+    cut = np.flatnonzero(np.diff(a) != 1)
+    begins = np.concatenate(([a[0]], a[cut + 1]))
+    ends = np.concatenate((a[cut], [a[-1]])) + 1
+    return [(int(b), int(e)) for b, e in zip(begins, ends)]
+
+
+def bam_gather_host(flat, starts, head=b"", filter=None):
+    """The BAM stream Shard.records_bam builds on the GPU, gathered on the host by the library
+    (sbh_bam_gather_host: no GPU, the definition the device path shares): head, then the raw
+    bytes of the records at starts[] that the filter keeps.  Returns (stream uint8, rec_off
+    uint64 [n_kept + 1], rows uint64 [n_kept]).  Raises SparkBamError(SBH_E_BAD_RECORD) with
+    `.fields = (row,)` for the first invalid record, kept or not."""
+    import ctypes as C
+
+    from ._lib import SBH_OK, SparkBamError, lib
+    flat = np.ascontiguousarray(np.frombuffer(flat, dtype=np.uint8) if not isinstance(flat, np.ndarray) else flat)
+    st = np.ascontiguousarray(starts, dtype=np.uint64)
+    hd = np.frombuffer(bytes(head), dtype=np.uint8)
+    f, keep = record_filter(filter)
+    rec_off = np.zeros(st.size + 1, dtype=np.uint64)
+    rows = np.zeros(max(st.size, 1), dtype=np.uint64)
+    n_kept, bad = C.c_uint64(), C.c_uint64()
+    p = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None  # noqa: E731
+
+    def call(out):
+        rc = lib().sbh_bam_gather_host(p(flat), flat.size, p(st), st.size, p(hd), hd.size,
+                                       C.byref(f) if f is not None else None, None if out is None else p(out),
+                                       0 if out is None else out.size, p(rec_off), p(rows), C.byref(n_kept),
+                                       C.byref(bad))
+        if rc != SBH_OK:
+            raise SparkBamError(rc, "record %d is malformed" % bad.value if rc == 20 else "bam_gather_host", (bad.value,))
+    call(None)
+    out = np.empty(int(rec_off[n_kept.value]), dtype=np.uint8)
+    if out.size:
+        call(out)
+    del keep
+    return out, rec_off[:n_kept.value + 1].copy(), rows[:n_kept.value].copy()
+
+
 class Reads:
     """A decoded batch: fixed fields as arrays, variable-length fields packed."""
 
