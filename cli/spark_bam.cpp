@@ -10,7 +10,8 @@
 //   spark-bam index-records BAM [OUT]                        (check/index/IndexRecords.scala)
 //   spark-bam index-bai     BAM [OUT]                        (the .bai samtools index writes; htslib hts.c)
 //   spark-bam view [-h] [-o FILE] BAM                        (the records as SAM text: htsjdk getSAMString)
-//   spark-bam view -b -o OUT [-f INT] [-F INT] [-q INT] [-r ROWS] [--level N] [--index-bai] BAM
+//   spark-bam view -b -o OUT [-f INT] [-F INT] [-q INT] [-r ROWS] [--level N] [--index-bai] [--sort] BAM
+//   spark-bam sort [-o OUT] [--level N] [--index-bai] BAM [OUT]  (coordinate order, as samtools sort)
 //                                                            (the records that pass, as a BAM gathered on the GPU)
 //   spark-bam check-blocks -s [-r RECORDS] [-l N] BAM        (cli/.../check/blocks/CheckBlocks.scala)
 //   spark-bam htsjdk-rewrite [-r READS] [-b] [-i] [--index-bai] BAM OUT  (cli/.../rewrite/HTSJDKRewrite.scala)
@@ -253,7 +254,8 @@ struct Args {
   bool sam_header = false;  // view -h: the BAM header text first
   // view -b: BAM output of the records with (flag & -f) == -f, (flag & -F) == 0, mapq >= -q and an
   // index in -r (read_ranges); --level as sbh_bgzf_compress_level; --index-bai (idx_bai) writes OUT.bai
-  bool bam_out = false;
+  // view -b --sort, sort: the kept records in coordinate order (sbh_records_bam_scan_order), SO:coordinate
+  bool bam_out = false, sort = false;
   uint32_t flag_require = 0, flag_exclude = 0;
   int min_mapq = 0, level = SBH_LEVEL_HTSJDK;
 };
@@ -277,11 +279,13 @@ Args parse(int argc, char **argv) {
     throw Error(SBH_E_ARG,
                 "usage: spark-bam <command> [options] <bam>\n"
                 "  commands: compute-splits count-reads check-bam full-check index-blocks index-records index-bai\n"
-                "            check-blocks htsjdk-rewrite view\n"
+                "            check-blocks htsjdk-rewrite view sort\n"
                 "  view [-h|--header] [-o FILE] <bam>: the records as SAM text (-h: the header text first)\n"
-                "  view -b -o OUT [-f INT] [-F INT] [-q INT] [-r ROWS] [--level N] [--index-bai] <bam>: the records with\n"
+                "  view -b -o OUT [-f INT] [-F INT] [-q INT] [-r ROWS] [--level N] [--index-bai] [--sort] <bam>: the records with\n"
                 "       (flag & f) == f, (flag & F) == 0, mapq >= q and an index in ROWS (a-b,c-d: htsjdk-rewrite's -r)\n"
-                "       as a BAM at deflate level N (5: htsjdk's bytes; -1: the fast coder); --index-bai writes OUT.bai");
+                "       as a BAM at deflate level N (5: htsjdk's bytes; -1: the fast coder); --index-bai writes OUT.bai;\n"
+                "       --sort: in coordinate order (reference, position, strand; unplaced last), header SO:coordinate\n"
+                "  sort [-o OUT] [--level N] [--index-bai] <bam> [OUT]: every record, coordinate-sorted on the GPU");
   a.cmd = argv[1];
   const bool rewrite = a.cmd == "htsjdk-rewrite";
   std::vector<std::string> pos;
@@ -304,6 +308,10 @@ Args parse(int argc, char **argv) {
     else if (a.cmd == "view" && (t == "-r" || t == "--read-ranges")) { a.read_ranges = parse_ranges(next()); a.has_read_ranges = true; }
     else if (a.cmd == "view" && (t == "-l" || t == "--level")) a.level = (int)parse_int(next());
     else if (a.cmd == "view" && t == "--index-bai") a.idx_bai = true;
+    else if (a.cmd == "view" && t == "--sort") a.sort = true;
+    else if (a.cmd == "sort" && (t == "-o" || t == "--output")) a.out = next();
+    else if (a.cmd == "sort" && (t == "-l" || t == "--level")) a.level = (int)parse_int(next());
+    else if (a.cmd == "sort" && t == "--index-bai") a.idx_bai = true;
     else if (t == "-m" || t == "--max-split-size") { a.split = parse_bytes(next()); a.has_split = true; }
     else if (t == "-s" || t == "--spark-bam") a.s = true;
     else if (t == "-u" || t == "--upstream" || t == "--hadoop-bam") a.u = true;
@@ -320,6 +328,10 @@ Args parse(int argc, char **argv) {
   if (pos.empty()) throw Error(SBH_E_ARG, "missing BAM path");
   a.path = pos[0];
   if (pos.size() > 1) a.out = pos[1];
+  if (a.cmd == "sort") {
+    a.bam_out = a.sort = true;
+    if (a.out.empty()) throw Error(SBH_E_ARG, "usage: sort needs -o OUT (a BAM is not written to the terminal)");
+  }
   if (a.cmd == "view" && a.bam_out && a.out.empty())
     throw Error(SBH_E_ARG, "usage: view -b needs -o OUT (a BAM is not written to the terminal)");
   return a;
@@ -931,8 +943,8 @@ int view_bam(const Args &a);
 
 int view(const Args &a) {
   if (a.bam_out) return view_bam(a);
-  if (a.has_read_ranges || a.flag_require || a.flag_exclude || a.min_mapq || a.idx_bai)
-    throw Error(SBH_E_ARG, "view: -f / -F / -q / -r / --index-bai select records for BAM output: they need -b");
+  if (a.has_read_ranges || a.flag_require || a.flag_exclude || a.min_mapq || a.idx_bai || a.sort)
+    throw Error(SBH_E_ARG, "view: -f / -F / -q / -r / --index-bai / --sort select records for BAM output: they need -b");
   Loaded L(a.path);
   uint64_t seg_end = L.flat;
   for (const sbh_block &b : L.blocks)
@@ -986,6 +998,13 @@ int view_bam(const Args &a) {
       if (b.flags & SBH_BLOCK_EMPTY) { seg_end = b.ustart; break; }
     std::vector<uint8_t> head(L.hdr.end);
     if (L.hdr.end) chk(sbh_read_flat(L.sh, 0, L.hdr.end, head.data()), "read header");
+    if (a.sort) {
+      std::vector<uint8_t> so(head.size() + 64);
+      uint64_t so_n = 0;
+      chk(sbh_bam_header_set_so(head.data(), head.size(), "coordinate", so.data(), so.size(), &so_n), "header SO");
+      so.resize(so_n);
+      head.swap(so);
+    }
     sbh_records_sizes rs{};
     if (seg_end > L.hdr.end) {
       uint64_t n = 0;
@@ -1008,7 +1027,8 @@ int view_bam(const Args &a) {
     f.row_end = re.data();
     f.n_row_ranges = rb.size();
     sbh_bam_sizes bs{};
-    chk(sbh_records_bam_scan(L.sh, head.data(), head.size(), &f, &bs), "bam scan");
+    chk(sbh_records_bam_scan_order(L.sh, head.data(), head.size(), &f, a.sort ? SBH_ORDER_COORDINATE : SBH_ORDER_SCAN, &bs),
+        "bam scan");
     out.resize(sbh_bgzf_compress_bound(bs.bytes));
     chk(sbh_bgzf_compress_level(g_ctx, sbh_records_bam_device_ptr(L.sh), bs.bytes, 1, a.level, out.data(), out.size(), &size,
                                 &nb, nullptr),
@@ -1235,7 +1255,7 @@ int main(int argc, char **argv) {
     else if (a.cmd == "index-bai") rc = index_bai(a);
     else if (a.cmd == "check-blocks") rc = check_blocks(a);
     else if (a.cmd == "htsjdk-rewrite") rc = htsjdk_rewrite(a);
-    else if (a.cmd == "view") rc = view(a);
+    else if (a.cmd == "view" || a.cmd == "sort") rc = view(a);
     else throw Error(SBH_E_ARG, "unknown command " + a.cmd);
     sbh_ctx_destroy(g_ctx);
     return rc;

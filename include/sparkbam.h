@@ -671,6 +671,34 @@ int sbh_records_bam_fetch(sbh_shard *sh, uint8_t *stream /*[bytes]*/, uint64_t *
                           uint64_t *rows /*[n_kept]: the scan row each kept record came from*/);
 /* Bytes [offset, offset + n) of the stream (a window's unfinished tail, without the rest). */
 int sbh_records_bam_read(sbh_shard *sh, uint64_t offset, uint64_t n, uint8_t *out);
+/* The same stream with the kept rows in a chosen order.  SBH_ORDER_SCAN is sbh_records_bam_scan
+ * (which calls this).  SBH_ORDER_COORDINATE: the kept rows in ascending order of
+ *   key = (ref_id < 0 ? 0x7fffffff : ref_id) << 33 | (uint32)(pos + 1) << 1 | ((flag >> 4) & 1)
+ * -- reference, position, reverse strand: samtools' bam1_cmp_core, unplaced records last -- rows
+ * of equal key in scan order (a stable sort on the device; csrc/bam_sort_core.h holds the
+ * definition for device and host).  The filter's row ranges index scan rows, and
+ * sbh_records_bam_fetch's rows[k] is still the scan row the k-th record of the stream came from:
+ * in this order, the permutation.  State, invalidation and errors as sbh_records_bam_scan;
+ * SBH_E_ARG for any other order.  sbh_records_bam_sorted: after a coordinate-order scan,
+ * *already = 1 when the kept rows were in order as scanned (nothing was moved); SBH_E_STATE
+ * without such a scan. */
+#define SBH_ORDER_SCAN 0
+#define SBH_ORDER_COORDINATE 1
+int sbh_records_bam_scan_order(sbh_shard *sh, const uint8_t *head, uint64_t head_bytes,
+                               const sbh_record_filter *filter, int order, sbh_bam_sizes *out);
+int sbh_records_bam_sorted(sbh_shard *sh, int *already);
+/* HOST ONLY, no context, no GPU: perm[k] = the row of starts[] that comes k-th in that order.
+ * SBH_E_BAD_RECORD with *bad_row = the first invalid row (sbh_bam_gather_host's validation). */
+int sbh_bam_sort_host(const uint8_t *flat, uint64_t flat_size, const uint64_t *starts, uint64_t n,
+                      uint64_t *perm /*[n]*/, uint64_t *bad_row);
+/* HOST ONLY: the BAM header bytes head[0, n) (magic, l_text, text, n_ref, references) with the
+ * @HD line's SO: set to `so` -- an existing value replaced, "\tSO:<so>" appended to an @HD line
+ * without one, "@HD\tVN:1.6\tSO:<so>\n" put in front of a text without @HD.  l_text follows, a
+ * NUL-padded text keeps its padding behind the last line, everything else is untouched.  *out_n =
+ * the result's size, also when cap is too small (SBH_E_ARG then; out may be NULL with cap 0:
+ * at most n + 20 + strlen(so) bytes).  SBH_E_ARG too for bytes that are not a BAM header. */
+int sbh_bam_header_set_so(const uint8_t *head, uint64_t n, const char *so, uint8_t *out, uint64_t cap,
+                          uint64_t *out_n);
 /* HOST ONLY, no context, no GPU (like sbh_sam_render_host): the same stream for the records at
  * starts[] of a flat BAM stream.  rec_off (room for n + 1) and rows (room for n) may be NULL;
  * out == NULL: sizes only (*n_kept, rec_off).  SBH_E_BAD_RECORD with *bad_row = the first invalid

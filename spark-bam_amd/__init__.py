@@ -12,6 +12,7 @@ Import name: ``spark_bam_amd`` (the directory name contains a hyphen, so load it
   index:  build_bai / write_bai (the `.bai` samtools index writes, built on the GPU)
   text:   view (the records as SAM text, rendered on the GPU), sam_text_host
   subset: view_bam (filtered records as a BAM with its index, gathered on the GPU), bam_gather_host
+  sort:   sort_bam (the records coordinate-sorted on the GPU), bam_sort_host
 """
 from ._lib import (BLOCK_EMPTY, BLOCK_TRUNCATED, FULL_FLAGS_MASK, FULL_N_SHIFT,  # noqa: F401
                    FULL_SUCCESS, FULL_UNKNOWN, HeaderParseException, HeaderSearchFailedException,
@@ -19,8 +20,8 @@ from ._lib import (BLOCK_EMPTY, BLOCK_TRUNCATED, FULL_FLAGS_MASK, FULL_N_SHIFT, 
 from .device import Context, PinnedBuffer, Shard  # noqa: F401
 from .api import (FLAG_NAMES, htsjdk_rewrite, Header, Metadata, Pos, Split, bam_header, check_bam,  # noqa: F401
                   file_splits, full_check, load_bam_count, load_reads, load_splits_and_reads,
-                  parse_bam_header, view, view_bam)
-from .records import Reads, bam_gather_host, sam_text_host  # noqa: F401
+                  parse_bam_header, sort_bam, view, view_bam)
+from .records import Reads, bam_gather_host, bam_header_set_so, bam_sort_host, sam_text_host  # noqa: F401
 from .checkers import GpuWindow, WindowedEagerChecker, WindowedFullChecker  # noqa: F401
 from .intervals import (Chunk, Index, get_interval_chunks, load_bam_intervals,  # noqa: F401
                         parse_loci, read_bai)
@@ -35,4 +36,5 @@ __all__ = [
     "read_bai", "parse_loci", "get_interval_chunks", "load_bam_intervals",
     "GpuWindow", "WindowedEagerChecker", "WindowedFullChecker",
     "build_bai", "write_bai", "view", "sam_text_host", "view_bam", "bam_gather_host",
+    "sort_bam", "bam_sort_host", "bam_header_set_so",
 ]

@@ -47,7 +47,9 @@ EXPORTS = [
     "sbh_records_sam_scan", "sbh_records_sam_fetch", "sbh_sam_render_host",
     "sbh_records_bam_scan", "sbh_records_bam_device_ptr", "sbh_records_bam_fetch", "sbh_records_bam_read",
     "sbh_bam_gather_host",
+    "sbh_records_bam_scan_order", "sbh_records_bam_sorted", "sbh_bam_sort_host", "sbh_bam_header_set_so",
 ]
+ORDER_SCAN, ORDER_COORDINATE = 0, 1  # SBH_ORDER_*
 LEVEL_HTSJDK, LEVEL_FAST = 5, -1  # sbh_bgzf_compress_level: htsjdk's zlib level 5 / this library's own coder
 
 
@@ -265,6 +267,10 @@ def lib():
         "sbh_records_sam_fetch": [P, P, P],
         "sbh_sam_render_host": [P, U64, P, U64, P, P, I32, P, U64, P, PU64],
         "sbh_records_bam_scan": [P, P, U64, C.POINTER(SbhRecordFilter), C.POINTER(SbhBamSizes)],
+        "sbh_records_bam_scan_order": [P, P, U64, C.POINTER(SbhRecordFilter), C.c_int, C.POINTER(SbhBamSizes)],
+        "sbh_records_bam_sorted": [P, C.POINTER(C.c_int)],
+        "sbh_bam_sort_host": [P, U64, P, U64, P, PU64],
+        "sbh_bam_header_set_so": [P, U64, C.c_char_p, P, U64, PU64],
         "sbh_records_bam_fetch": [P, P, P, P],
         "sbh_records_bam_read": [P, U64, U64, P],
         "sbh_bam_gather_host": [P, U64, P, U64, P, U64, C.POINTER(SbhRecordFilter), P, U64, P, P, PU64, PU64],

@@ -10,7 +10,7 @@ from collections import namedtuple
 
 import numpy as np
 
-from ._lib import FULL_FLAGS_MASK, FULL_N_SHIFT, SBH_E_NEED_HALO, SBH_OK, SparkBamError, lib
+from ._lib import FULL_FLAGS_MASK, FULL_N_SHIFT, SBH_E_ARG, SBH_E_NEED_HALO, SBH_OK, SparkBamError, lib
 from .device import Context
 from .records import Reads
 
@@ -314,7 +314,8 @@ BGZF_EOF_BYTES = 28
 
 
 def view_bam(path_or_bytes, out=None, flag_require=0, flag_exclude=0, min_mapq=0, rows=None, intervals=None,
-             bai=None, level=5, window=None, index=False, ctx=None, reads_to_check=DEFAULT_READS_TO_CHECK):
+             bai=None, level=5, window=None, index=False, ctx=None, reads_to_check=DEFAULT_READS_TO_CHECK,
+             sort=None):
     """The file's records that pass the filters, as a BAM file: the header, then every record with
     (flag & flag_require) == flag_require, (flag & flag_exclude) == 0, mapq >= min_mapq and -- with
     `rows`, a range or a collection of ints -- a record index in it, byte for byte as stored, cut
@@ -331,14 +332,24 @@ def view_bam(path_or_bytes, out=None, flag_require=0, flag_exclude=0, min_mapq=0
     stream as its head; the last tail and the EOF member close the file.  The bytes do not depend
     on `window`.
 
+    sort="coordinate": the kept records in stable coordinate order (Shard.records_bam's
+    order="coordinate": reference, position, reverse strand, unplaced last), sorted on the GPU,
+    behind a header whose @HD line says SO:coordinate.  Filters and `rows` apply before the sort.
+    The whole file must then fit one window: a second window raises SparkBamError(SBH_E_ARG)
+    (merging sorted windows is not done here; pass a larger `window`), and so does `intervals`.
+
     Returns the file bytes; with `out` (a path or a binary file object) writes them and returns
     the byte count.  index=True: also the `.bai` of the result (bai.build_bai) -- returned as
     (bam, bai), written to out + ".bai" when out is a path, or returned as (count, bai) when out
     is a file object."""
+    if sort not in (None, "coordinate"):
+        raise ValueError("view_bam: sort is None or 'coordinate', not %r" % (sort,))
+    if sort and intervals is not None:
+        raise SparkBamError(SBH_E_ARG, "view_bam: sort needs the whole file in one window, not `intervals`")
     data = _file_array(path_or_bytes)
     own_ctx = ctx is None
     ctx = ctx or Context(0)
-    from .records import row_ranges
+    from .records import bam_header_set_so, row_ranges
     want = None if rows is None else row_ranges(rows)
     pieces = []
     state = {"tail": None, "row_base": 0}
@@ -350,7 +361,7 @@ def view_bam(path_or_bytes, out=None, flag_require=0, flag_exclude=0, min_mapq=0
         f = {"flag_require": flag_require, "flag_exclude": flag_exclude, "min_mapq": min_mapq}
         if want is not None:
             f["rows"] = [(max(a - base, 0), b - base) for a, b in want if b > base]
-        sh.records_bam(state["tail"], f, want_bytes=False)
+        sh.records_bam(state["tail"], f, want_bytes=False, order=sort or "scan")
         whole = sh.bam_size - sh.bam_size % BGZF_PAYLOAD
         comp = b""
         if whole:
@@ -365,11 +376,17 @@ def view_bam(path_or_bytes, out=None, flag_require=0, flag_exclude=0, min_mapq=0
 
     try:
         state["tail"] = _header_flat(ctx, data)
+        if sort:
+            state["tail"] = bam_header_set_so(state["tail"], sort)
         if intervals is None:
             def deliver(sh, f, E, names):
                 sh.records_scan(f, E)
                 return gather(sh)
             for got in _iter_windows(data, deliver, window, ctx=ctx, reads_to_check=reads_to_check):
+                if sort and pieces:
+                    raise SparkBamError(SBH_E_ARG, "view_bam: sort needs the file in one window; `window` (%d compressed "
+                                                   "bytes) is smaller than the file (%d)"
+                                        % (int(window or STREAM_WINDOW), int(data.size)))
                 commit(got)
         else:
             from .intervals import iter_interval_groups
@@ -401,6 +418,16 @@ def view_bam(path_or_bytes, out=None, flag_require=0, flag_exclude=0, min_mapq=0
         return len(result)
     out.write(result)
     return (len(result), bai_bytes) if index else len(result)
+
+
+def sort_bam(path_or_bytes, out=None, level=5, index=False, ctx=None, reads_to_check=DEFAULT_READS_TO_CHECK):
+    """The file coordinate-sorted (what `samtools sort` writes, up to the compressed bytes): every
+    record, in stable (reference, position, reverse strand) order with the unplaced ones last,
+    under a header that says SO:coordinate.  view_bam with sort="coordinate" and the whole file as
+    its one window; `out`, `level`, `index` and the return value as there."""
+    data = _file_array(path_or_bytes)
+    return view_bam(data, out=out, level=level, index=index, ctx=ctx, reads_to_check=reads_to_check,
+                    window=max(int(data.size), 1), sort="coordinate")
 
 
 def _header_flat(ctx, data):

@@ -147,6 +147,13 @@ hipError_t launch_bam_keep(const uint8_t *U, const uint64_t *pos, uint64_t n, ui
   return hipGetLastError();
 }
 
+// k_bam_heads alone, over rows whose len and keep flags (kh) are already there (the sorted rows)
+hipError_t launch_bam_heads(const uint64_t *pos, const uint64_t *len, uint64_t n, uint64_t *kh, hipStream_t st) {
+  if (!n) return hipSuccess;
+  hipLaunchKernelGGL(k_bam_heads, dim3(rows_grid(n)), dim3(256), 0, st, pos, len, n, kh);
+  return hipGetLastError();
+}
+
 // off, khpre: the exclusive scans of len and kh over n + 1 entries
 hipError_t launch_bam_index(const uint64_t *pos, const uint64_t *off, const uint64_t *kh, const uint64_t *khpre,
                             uint64_t n, uint64_t head_bytes, uint64_t *rec_off, uint64_t *rows, uint64_t *run_dst,

@@ -16,6 +16,7 @@
 
 #include "sam_core.h"
 #include "bam_gather_core.h"
+#include "bam_sort_core.h"
 #include "sbh_internal.h"
 
 namespace sbh {
@@ -290,8 +291,14 @@ struct sbh_shard {
   struct Bam {
     DBuf<uint64_t> len, off, kh, khpre, rec_off, rows, run_dst, run_src, ranges;
     DBuf<uint8_t> out;
+    // coordinate order (bam_sort.hip; sizes in bam_sort_core.h): the two (key, row) arrays the passes
+    // alternate between, the digit counts with their scan, the permuted starts and lengths
+    DBuf<uint64_t> skey[2], hist, pos2, len2;
+    DBuf<uint32_t> srow[2];
     sbh_bam_sizes sz{};
     uint64_t head_bytes = 0;
+    int order = SBH_ORDER_SCAN;
+    bool already = false;  // a coordinate-order scan found its kept rows in order (no pass ran)
     bool valid = false;
   } bam;
   std::vector<int32_t> h_ctg;  // host copy of the contig lengths (sbh_set_contigs)
@@ -3237,10 +3244,24 @@ static bool bam_filter_of(const sbh_record_filter *f, sbh_bam::Filter *F) {
 
 int sbh_records_bam_scan(sbh_shard *sh, const uint8_t *head, uint64_t head_bytes, const sbh_record_filter *filter,
                          sbh_bam_sizes *out) {
+  return sbh_records_bam_scan_order(sh, head, head_bytes, filter, SBH_ORDER_SCAN, out);
+}
+
+// SBH_ORDER_COORDINATE: the scan-order pipeline runs as it is up to k_bam_index, whose rows[] are the
+// kept rows; k_sort_keys follows it, and the one round trip brings its three counters as well.  No
+// descent: the scan order is the coordinate order and the call goes on exactly as in scan order.
+// Otherwise the passes whose digit differs somewhere (OR & ~AND) run, k_sort_apply lays out the
+// permuted starts and lengths, and k_bam_heads, the scans and k_bam_index run over those -- every
+// entry kept -- before a second round trip for the run count.
+int sbh_records_bam_scan_order(sbh_shard *sh, const uint8_t *head, uint64_t head_bytes, const sbh_record_filter *filter,
+                               int order, sbh_bam_sizes *out) {
   if (!sh || !out || (head_bytes && !head)) return SBH_E_ARG;
   sbh_ctx *ctx = sh->ctx;
   auto &R = sh->rec;
   auto &B = sh->bam;
+  if (order != SBH_ORDER_SCAN && order != SBH_ORDER_COORDINATE)
+    return fail(ctx, SBH_E_ARG, "records_bam_scan: order %d is neither SBH_ORDER_SCAN nor SBH_ORDER_COORDINATE", order);
+  const bool sorted = order == SBH_ORDER_COORDINATE;
   if (!R.valid) return fail(ctx, SBH_E_STATE, "records_bam_scan without a records scan");
   sbh_bam::Filter F;
   if (!bam_filter_of(filter, &F))
@@ -3254,6 +3275,15 @@ int sbh_records_bam_scan(sbh_shard *sh, const uint8_t *head, uint64_t head_bytes
   B.valid = false;
   uint64_t bytes = head_bytes, n_kept = 0, n_runs = 0;
   for (auto *b : {&B.len, &B.off, &B.kh, &B.khpre, &B.rec_off, &B.rows, &B.run_dst, &B.run_src}) HIPCHK(ctx, b->ensure(n + 1));
+  const uint64_t hist_words = 256 * sort_tiles(n) + 1;
+  if (sorted && n) {  // (sized for n: the kept count is not known here)
+    for (auto *b : {&B.skey[0], &B.skey[1]}) HIPCHK(ctx, b->ensure(n));
+    for (auto *b : {&B.srow[0], &B.srow[1]}) HIPCHK(ctx, b->ensure(n));
+    for (auto *b : {&B.pos2, &B.len2}) HIPCHK(ctx, b->ensure(n + 1));
+    HIPCHK(ctx, B.hist.ensure(2 * hist_words));
+    HIPCHK(ctx, sh->tmp.ensure(scan_tmp_words(hist_words)));
+  }
+  bool already = true;
   if (n) {
     HIPCHK(ctx, B.ranges.ensure(2 * nr));
     if (nr) {
@@ -3272,6 +3302,14 @@ int sbh_records_bam_scan(sbh_shard *sh, const uint8_t *head, uint64_t head_bytes
     HIPCHK(ctx, scan_exclusive_u64(B.kh.p, B.khpre.p, n + 1, sh->tmp.p, st));
     HIPCHK(ctx, launch_bam_index(R.pos.p, B.off.p, B.kh.p, B.khpre.p, n, head_bytes, B.rec_off.p, B.rows.p, B.run_dst.p,
                                  B.run_src.p, st));
+    unsigned long long *acc = sh->ctr.p + ctr::SORT_DESC;
+    static_assert(ctr::SORT_OR == ctr::SORT_DESC + 1 && ctr::SORT_AND == ctr::SORT_DESC + 2, "one copy");
+    if (sorted) {
+      HIPCHK(ctx, hipMemsetAsync(acc, 0, 16, st));
+      HIPCHK(ctx, hipMemsetAsync(acc + 2, 0xff, 8, st));
+      HIPCHK(ctx, launch_sort_keys(sh->U.p, R.pos.p, B.rows.p, B.khpre.p + n, n, B.skey[0].p, B.srow[0].p, acc, st));
+      HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::SORT_DESC, acc, 24, hipMemcpyDeviceToHost, st));
+    }
     HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::BAM_BAD, bad, 16, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::H_BAM_BYTES, B.off.p + n, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::H_BAM_KH, B.khpre.p + n, 8, hipMemcpyDeviceToHost, st));
@@ -3287,6 +3325,27 @@ int sbh_records_bam_scan(sbh_shard *sh, const uint8_t *head, uint64_t head_bytes
     bytes += sh->h_ctr[ctr::H_BAM_BYTES];
     n_kept = sh->h_ctr[ctr::H_BAM_KH] & 0xffffffffull;
     n_runs = sh->h_ctr[ctr::H_BAM_KH] >> 32;
+    if (sorted && sh->h_ctr[ctr::SORT_DESC]) {
+      already = false;
+      const uint64_t m = n_kept, differ = sh->h_ctr[ctr::SORT_OR] & ~sh->h_ctr[ctr::SORT_AND];
+      int cur = 0;
+      for (uint32_t shift = 0; shift < 64; shift += 8) {
+        if (!((differ >> shift) & 0xff)) continue;  // the same digit in every key: the pass would move nothing
+        HIPCHK(ctx, launch_sort_pass(B.skey[cur].p, B.srow[cur].p, m, shift, B.hist.p, sh->tmp.p, B.skey[cur ^ 1].p,
+                                     B.srow[cur ^ 1].p, st));
+        cur ^= 1;
+      }
+      HIPCHK(ctx, launch_sort_apply(R.pos.p, B.len.p, B.srow[cur].p, m, B.pos2.p, B.len2.p, B.kh.p, st));
+      HIPCHK(ctx, launch_bam_heads(B.pos2.p, B.len2.p, m, B.kh.p, st));
+      HIPCHK(ctx, scan_exclusive_u64(B.len2.p, B.off.p, m + 1, sh->tmp.p, st));
+      HIPCHK(ctx, scan_exclusive_u64(B.kh.p, B.khpre.p, m + 1, sh->tmp.p, st));
+      HIPCHK(ctx, launch_bam_index(B.pos2.p, B.off.p, B.kh.p, B.khpre.p, m, head_bytes, B.rec_off.p, B.rows.p,
+                                   B.run_dst.p, B.run_src.p, st));
+      HIPCHK(ctx, launch_sort_rows(B.srow[cur].p, m, B.rows.p, st));
+      HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::H_BAM_KH, B.khpre.p + m, 8, hipMemcpyDeviceToHost, st));
+      HIPCHK(ctx, hipStreamSynchronize(st));
+      n_runs = sh->h_ctr[ctr::H_BAM_KH] >> 32;
+    }
   } else {
     HIPCHK(ctx, hipMemcpyAsync(B.rec_off.p, &head_bytes, 8, hipMemcpyHostToDevice, st));
   }
@@ -3296,8 +3355,19 @@ int sbh_records_bam_scan(sbh_shard *sh, const uint8_t *head, uint64_t head_bytes
   HIPCHK(ctx, hipStreamSynchronize(st));
   B.sz = sbh_bam_sizes{n, n_kept, bytes};
   B.head_bytes = head_bytes;
+  B.order = order;
+  B.already = already;
   B.valid = true;
   *out = B.sz;
+  return SBH_OK;
+}
+
+int sbh_records_bam_sorted(sbh_shard *sh, int *already) {
+  if (!sh || !already) return SBH_E_ARG;
+  const auto &B = sh->bam;
+  if (!B.valid || B.order != SBH_ORDER_COORDINATE)
+    return fail(sh->ctx, SBH_E_STATE, "records_bam_sorted without a coordinate-order records_bam_scan");
+  *already = B.already ? 1 : 0;
   return SBH_OK;
 }
 
@@ -3342,6 +3412,20 @@ int sbh_bam_gather_host(const uint8_t *flat, uint64_t flat_size, const uint64_t 
                                       &bytes, &bad);
   if (bad_row) *bad_row = bad;
   return rc == 0 ? SBH_OK : rc == 1 ? SBH_E_BAD_RECORD : SBH_E_ARG;
+}
+
+int sbh_bam_sort_host(const uint8_t *flat, uint64_t flat_size, const uint64_t *starts, uint64_t n, uint64_t *perm,
+                      uint64_t *bad_row) {
+  if ((!flat && flat_size) || (!starts && n) || (!perm && n)) return SBH_E_ARG;
+  uint64_t bad = sbh_bam::NO_ROW;
+  const int rc = sbh_bam::sort_host(flat, flat_size, starts, n, perm, &bad);
+  if (bad_row) *bad_row = bad;
+  return rc == 0 ? SBH_OK : SBH_E_BAD_RECORD;
+}
+
+int sbh_bam_header_set_so(const uint8_t *head, uint64_t n, const char *so, uint8_t *out, uint64_t cap, uint64_t *out_n) {
+  if (!head || !so || !out_n) return SBH_E_ARG;
+  return sbh_bam::header_set_so(head, n, so, out, cap, out_n) == 0 ? SBH_OK : SBH_E_ARG;
 }
 
 // ---- BAI construction (bai.hip; htslib hts_idx_push over the record chain) ------------------

@@ -205,6 +205,20 @@ hipError_t launch_bam_index(const uint64_t *pos, const uint64_t *off, const uint
 // out[head_bytes, bytes) from the runs; reads U below (the last run's end) + 32
 hipError_t launch_bam_copy(const uint8_t *U, const uint64_t *run_dst, const uint64_t *run_src, uint64_t n_runs,
                            uint64_t head_bytes, uint64_t bytes, uint8_t *out, hipStream_t st);
+hipError_t launch_bam_heads(const uint64_t *pos, const uint64_t *len, uint64_t n, uint64_t *kh, hipStream_t st);
+// Coordinate order of the kept rows (bam_sort.hip; the key in bam_sort_core.h).  launch_sort_keys:
+// key / row of the first khpre[n] & 0xffffffff entries of rows (k_bam_index's), acc = ctr::SORT_DESC
+// (preset 0, 0, ~0).  launch_sort_pass: one stable 8-bit pass from (key, row) to (key_out, row_out);
+// hist: 2 (256 sort_tiles(m) + 1) words, tmp: scan_tmp_words(256 sort_tiles(m) + 1).
+// launch_sort_apply: pos2 / len2 / kh over m + 1 entries; launch_sort_rows: rows[k] = row[k].
+uint64_t sort_tiles(uint64_t m);
+hipError_t launch_sort_keys(const uint8_t *U, const uint64_t *pos, const uint64_t *rows, const uint64_t *kh_total,
+                            uint64_t n, uint64_t *key, uint32_t *row, unsigned long long *acc, hipStream_t st);
+hipError_t launch_sort_pass(const uint64_t *key, const uint32_t *row, uint64_t m, uint32_t shift, uint64_t *hist,
+                            uint64_t *tmp, uint64_t *key_out, uint32_t *row_out, hipStream_t st);
+hipError_t launch_sort_apply(const uint64_t *pos, const uint64_t *len, const uint32_t *row, uint64_t m, uint64_t *pos2,
+                             uint64_t *len2, uint64_t *kh, hipStream_t st);
+hipError_t launch_sort_rows(const uint32_t *row, uint64_t m, uint64_t *rows, hipStream_t st);
 // BGZF footer CRC32 of every inflated, non-truncated block (crc.hip).
 hipError_t launch_block_crc(const uint8_t *comp, DevBlocks bl, uint64_t nblocks, const uint8_t *U,
                             unsigned long long *n_bad, unsigned long long *first_bad, hipStream_t st);
@@ -310,6 +324,8 @@ constexpr uint32_t SAM_BAD = 48, H_SAM_NHOST = 49, H_SAM_TOTAL = 50;
 // BAM scan (sbh_records_bam_scan): first invalid row, first row that only runs past the stream's
 // end; h_ctr only: the kept records' bytes, kept rows | runs << 32
 constexpr uint32_t BAM_BAD = 51, BAM_PAST = 52, H_BAM_BYTES = 53, H_BAM_KH = 54;
+// coordinate order (k_sort_keys): descents key[k - 1] > key[k], the OR and the AND of all keys
+constexpr uint32_t SORT_DESC = 55, SORT_OR = 56, SORT_AND = 57, SORT_END = 58;
 // inflate status (launch_first_bad): the first block whose status is not INF_OK
 constexpr uint32_t FIRST_BAD = 100;
 // h_ctr only: that block's status (u32), fetched after the run's copy of [0, CTR_RUN_WORDS)

@@ -7,7 +7,7 @@ import numpy as np
 
 from .records import pack_ref_names, record_columns, record_filter
 
-from ._lib import (SBH_OK, SbhBaiSizes, SbhBamSizes, SbhBatchSplit, SbhBlock, SbhCheckOpts, SbhCheckResult, SbhRecordsOut,
+from ._lib import (ORDER_COORDINATE, SBH_OK, SbhBaiSizes, SbhBamSizes, SbhBatchSplit, SbhBlock, SbhCheckOpts, SbhCheckResult, SbhRecordsOut,
                    SbhRecordsSizes, SbhSamSizes, SbhShardResult, SbhSplitBatchResult, SbhSplitRecordsResult,
                    SbhStreamOpts, SbhStreamResult, SparkBamError, error_for, lib)
 
@@ -597,7 +597,7 @@ class Shard:
         self._c(lib().sbh_records_sam_fetch(self.h, _ptr(text) if text.size else None, _ptr(line_off)))
         return text, line_off
 
-    def records_bam(self, head=b"", filter=None, want_bytes=True):
+    def records_bam(self, head=b"", filter=None, want_bytes=True, order="scan"):
         """The rows of the last scan on this shard that `filter` keeps, as one uncompressed BAM
         stream built on the GPU (sbh_records_bam_scan + sbh_records_bam_fetch): `head` (the BAM
         header bytes, or an earlier window's unfinished tail), then the kept records' raw bytes
@@ -605,12 +605,22 @@ class Shard:
         min_mapq, rows).  Returns (stream uint8, rec_off uint64 [n_kept + 1], rows uint64
         [n_kept]: the scan row of each kept record).  want_bytes=False returns None and leaves the
         stream on the device: bam_ptr() / bam_size are what Context.bgzf_compress takes.
-        `self.bam_n` / `self.bam_n_kept`: rows scanned and kept."""
+        `self.bam_n` / `self.bam_n_kept`: rows scanned and kept.
+        order="coordinate" (sbh_records_bam_scan_order): the kept records in stable coordinate
+        order -- reference, position, reverse strand, unplaced last -- sorted on the GPU; `rows`
+        is then the permutation, and `self.bam_sorted` says whether they were in order already."""
+        if order not in ("scan", "coordinate"):
+            raise ValueError("records_bam: order is 'scan' or 'coordinate', not %r" % (order,))
         hd = np.frombuffer(bytes(head), dtype=np.uint8)
         f, keep = record_filter(filter)
         sz = SbhBamSizes()
-        self._c(lib().sbh_records_bam_scan(self.h, _ptr(hd) if hd.size else None, int(hd.size),
-                                           C.byref(f) if f is not None else None, C.byref(sz)))
+        if order == "scan":
+            self._c(lib().sbh_records_bam_scan(self.h, _ptr(hd) if hd.size else None, int(hd.size),
+                                               C.byref(f) if f is not None else None, C.byref(sz)))
+        else:
+            self._c(lib().sbh_records_bam_scan_order(self.h, _ptr(hd) if hd.size else None, int(hd.size),
+                                                     C.byref(f) if f is not None else None, ORDER_COORDINATE,
+                                                     C.byref(sz)))
         del keep
         self.bam_n, self.bam_n_kept, self.bam_size = int(sz.n), int(sz.n_kept), int(sz.bytes)
         if not want_bytes:
@@ -621,6 +631,14 @@ class Shard:
         self._c(lib().sbh_records_bam_fetch(self.h, _ptr(stream) if stream.size else None, _ptr(rec_off),
                                             _ptr(rows) if rows.size else None))
         return stream, rec_off, rows
+
+    @property
+    def bam_sorted(self):
+        """After records_bam(order="coordinate"): True when the kept rows were already in
+        coordinate order, so nothing was moved (sbh_records_bam_sorted; SBH_E_STATE otherwise)."""
+        already = C.c_int()
+        self._c(lib().sbh_records_bam_sorted(self.h, C.byref(already)))
+        return bool(already.value)
 
     def bam_ptr(self):
         """Device pointer of the last records_bam stream (sbh_records_bam_device_ptr; None when a

@@ -223,6 +223,43 @@ def bam_gather_host(flat, starts, head=b"", filter=None):
     return out, rec_off[:n_kept.value + 1].copy(), rows[:n_kept.value].copy()
 
 
+def bam_sort_host(flat, starts):
+    """The permutation Shard.records_bam(order="coordinate") applies on the GPU, computed on the
+    host by the library (sbh_bam_sort_host: no GPU, the key the device path shares): perm[k] = the
+    index into starts[] of the record that comes k-th in stable coordinate order (reference,
+    position, reverse strand; unplaced last; ties in starts[] order).  Raises
+    SparkBamError(SBH_E_BAD_RECORD) with `.fields = (row,)` for the first invalid record."""
+    import ctypes as C
+
+    from ._lib import SBH_OK, SparkBamError, lib
+    flat = np.ascontiguousarray(np.frombuffer(flat, dtype=np.uint8) if not isinstance(flat, np.ndarray) else flat)
+    st = np.ascontiguousarray(starts, dtype=np.uint64)
+    perm = np.zeros(st.size, dtype=np.uint64)
+    bad = C.c_uint64()
+    p = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None  # noqa: E731
+    rc = lib().sbh_bam_sort_host(p(flat), flat.size, p(st), st.size, p(perm), C.byref(bad))
+    if rc != SBH_OK:
+        raise SparkBamError(rc, "record %d is malformed" % bad.value if rc == 20 else "bam_sort_host", (bad.value,))
+    return perm
+
+
+def bam_header_set_so(head, so):
+    """The BAM header bytes (magic, l_text, text, references) with the @HD line's SO: set to `so`
+    (sbh_bam_header_set_so, host only)."""
+    import ctypes as C
+
+    from ._lib import SBH_OK, SparkBamError, lib
+    hd = np.frombuffer(bytes(head), dtype=np.uint8)
+    so = so.encode("ascii") if isinstance(so, str) else bytes(so)
+    out = np.empty(hd.size + 20 + len(so), dtype=np.uint8)
+    n = C.c_uint64()
+    rc = lib().sbh_bam_header_set_so(hd.ctypes.data_as(C.c_void_p) if hd.size else None, hd.size, so,
+                                     out.ctypes.data_as(C.c_void_p), out.size, C.byref(n))
+    if rc != SBH_OK:
+        raise SparkBamError(rc, "bam_header_set_so: not a BAM header, or not a sort-order value")
+    return out[:n.value].tobytes()
+
+
 class Reads:
     """A decoded batch: fixed fields as arrays, variable-length fields packed."""
 
