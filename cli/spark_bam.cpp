@@ -258,6 +258,9 @@ struct Args {
   bool bam_out = false, sort = false;
   uint32_t flag_require = 0, flag_exclude = 0;
   int min_mapq = 0, level = SBH_LEVEL_HTSJDK;
+  // depth: -a every position of the spans, -r REGION, -J D ops cover, --bedgraph; -F defaults to 1796
+  bool depth_all = false, count_del = false, bedgraph = false, has_exclude = false;
+  std::string region;
 };
 
 // decimal or 0x hex
@@ -279,13 +282,17 @@ Args parse(int argc, char **argv) {
     throw Error(SBH_E_ARG,
                 "usage: spark-bam <command> [options] <bam>\n"
                 "  commands: compute-splits count-reads check-bam full-check index-blocks index-records index-bai\n"
-                "            check-blocks htsjdk-rewrite view sort\n"
+                "            check-blocks htsjdk-rewrite view sort depth\n"
                 "  view [-h|--header] [-o FILE] <bam>: the records as SAM text (-h: the header text first)\n"
                 "  view -b -o OUT [-f INT] [-F INT] [-q INT] [-r ROWS] [--level N] [--index-bai] [--sort] <bam>: the records with\n"
                 "       (flag & f) == f, (flag & F) == 0, mapq >= q and an index in ROWS (a-b,c-d: htsjdk-rewrite's -r)\n"
                 "       as a BAM at deflate level N (5: htsjdk's bytes; -1: the fast coder); --index-bai writes OUT.bai;\n"
                 "       --sort: in coordinate order (reference, position, strand; unplaced last), header SO:coordinate\n"
-                "  sort [-o OUT] [--level N] [--index-bai] <bam> [OUT]: every record, coordinate-sorted on the GPU");
+                "  sort [-o OUT] [--level N] [--index-bai] <bam> [OUT]: every record, coordinate-sorted on the GPU\n"
+                "  depth [-a] [-r REGION] [-f INT] [-F INT] [-q INT] [-J] [--bedgraph] [-o FILE] <bam>: per-base depth as\n"
+                "       RNAME POS DEPTH lines (samtools depth; -a: zero-depth positions too) or, with --bedgraph, RNAME BEG END\n"
+                "       DEPTH runs (genomecov -bg); REGION is NAME or NAME:BEG-END (1-based, inclusive); -F defaults to 1796;\n"
+                "       -J: deletions count");
   a.cmd = argv[1];
   const bool rewrite = a.cmd == "htsjdk-rewrite";
   std::vector<std::string> pos;
@@ -309,6 +316,14 @@ Args parse(int argc, char **argv) {
     else if (a.cmd == "view" && (t == "-l" || t == "--level")) a.level = (int)parse_int(next());
     else if (a.cmd == "view" && t == "--index-bai") a.idx_bai = true;
     else if (a.cmd == "view" && t == "--sort") a.sort = true;
+    else if (a.cmd == "depth" && t == "-a") a.depth_all = true;
+    else if (a.cmd == "depth" && (t == "-r" || t == "--region")) a.region = next();
+    else if (a.cmd == "depth" && (t == "-f" || t == "--require-flags")) a.flag_require = (uint32_t)parse_int(next());
+    else if (a.cmd == "depth" && (t == "-F" || t == "--exclude-flags")) { a.flag_exclude = (uint32_t)parse_int(next()); a.has_exclude = true; }
+    else if (a.cmd == "depth" && (t == "-q" || t == "--min-mapq")) a.min_mapq = (int)parse_int(next());
+    else if (a.cmd == "depth" && t == "-J") a.count_del = true;
+    else if (a.cmd == "depth" && t == "--bedgraph") a.bedgraph = true;
+    else if (a.cmd == "depth" && (t == "-o" || t == "--output")) a.out = next();
     else if (a.cmd == "sort" && (t == "-o" || t == "--output")) a.out = next();
     else if (a.cmd == "sort" && (t == "-l" || t == "--level")) a.level = (int)parse_int(next());
     else if (a.cmd == "sort" && t == "--index-bai") a.idx_bai = true;
@@ -327,7 +342,8 @@ Args parse(int argc, char **argv) {
   }
   if (pos.empty()) throw Error(SBH_E_ARG, "missing BAM path");
   a.path = pos[0];
-  if (pos.size() > 1) a.out = pos[1];
+  if (pos.size() > 1 && a.cmd != "depth") a.out = pos[1];
+  if (a.cmd == "depth" && !a.has_exclude) a.flag_exclude = 1796;  // UNMAP, SECONDARY, QCFAIL, DUP: samtools depth's
   if (a.cmd == "sort") {
     a.bam_out = a.sort = true;
     if (a.out.empty()) throw Error(SBH_E_ARG, "usage: sort needs -o OUT (a BAM is not written to the terminal)");
@@ -1048,6 +1064,93 @@ int view_bam(const Args &a) {
   return 0;
 }
 
+// depth: per-base depth of the records that pass the filters, whole file resident as view holds
+// it.  The records are scanned, their CIGARs walked and the depth scanned into runs on the device
+// (sbh_records_depth_add, sbh_depth_finish); the runs come back and are printed here -- samtools
+// depth's lines (RNAME, 1-based POS, DEPTH; zero depth only with -a) or, with --bedgraph,
+// genomecov -bg's (RNAME, 0-based BEG, END, DEPTH; depth > 0 only).  REGION: a reference name, or
+// NAME:BEG-END with 1-based inclusive positions; none: every reference whole.
+int depth(const Args &a) {
+  Loaded L(a.path);
+  uint64_t seg_end = L.flat;
+  for (const sbh_block &b : L.blocks)
+    if (b.flags & SBH_BLOCK_EMPTY) { seg_end = b.ustart; break; }
+  const int32_t n_ref = (int32_t)L.hdr.lens.size();
+  std::vector<sbh_depth_span> spans;
+  if (a.region.empty()) {
+    for (int32_t k = 0; k < n_ref; ++k)
+      if (L.hdr.lens[k] > 0) spans.push_back(sbh_depth_span{k, 0, 0, L.hdr.lens[k]});
+  } else {
+    auto find = [&](const std::string &name) {
+      for (int32_t k = 0; k < n_ref; ++k)
+        if (L.hdr.names[k] == name) return k;
+      return (int32_t)-1;
+    };
+    int32_t k = find(a.region);
+    int64_t beg = 0, end = k >= 0 ? L.hdr.lens[k] : 0;
+    if (k < 0) {
+      const size_t c = a.region.rfind(':'), d = c == std::string::npos ? c : a.region.find('-', c);
+      auto digits = [](const std::string &t) { return !t.empty() && t.size() < 11 && t.find_first_not_of("0123456789") == std::string::npos; };
+      if (c == std::string::npos || d == std::string::npos || (k = find(a.region.substr(0, c))) < 0 ||
+          !digits(a.region.substr(c + 1, d - c - 1)) || !digits(a.region.substr(d + 1)))
+        throw Error(SBH_E_ARG, "depth: unknown reference in region " + a.region);
+      beg = std::stoll(a.region.substr(c + 1, d - c - 1)) - 1;
+      end = std::min<int64_t>(std::stoll(a.region.substr(d + 1)), L.hdr.lens[k]);
+    }
+    if (beg < 0 || beg >= end) throw Error(SBH_E_ARG, "depth: empty region " + a.region);
+    spans.push_back(sbh_depth_span{k, 0, beg, end});
+  }
+  struct Acc {
+    sbh_depth *d = nullptr;
+    ~Acc() { sbh_depth_destroy(d); }
+  } acc;
+  chk(sbh_depth_create(g_ctx, spans.data(), (uint32_t)spans.size(), n_ref, a.count_del ? SBH_DEPTH_DEL : 0u, &acc.d),
+      "depth create");
+  if (seg_end > L.hdr.end) {
+    uint64_t n = 0;
+    chk(sbh_check_eager(L.sh, L.hdr.end, seg_end, a.reads_to_check, nullptr, &n), "eager");
+    sbh_records_sizes rs{};
+    chk(sbh_records_scan(L.sh, L.hdr.end, seg_end, &rs), "records scan");
+    sbh_record_filter f{};
+    f.flag_require = a.flag_require;
+    f.flag_exclude = a.flag_exclude;
+    f.min_mapq = a.min_mapq;
+    sbh_depth_add_result ar{};
+    chk(sbh_records_depth_add(L.sh, acc.d, &f, &ar), "depth add");
+  }
+  sbh_depth_sizes sz{};
+  chk(sbh_depth_finish(acc.d, &sz), "depth finish");
+  std::vector<sbh_depth_run> runs(sz.n_runs);
+  chk(sbh_depth_runs_fetch(acc.d, 0, sz.n_runs, runs.data()), "depth runs");
+  FILE *f = a.out.empty() ? stdout : fopen(a.out.c_str(), "wb");
+  if (!f) throw Error(SBH_E_ARG, "cannot write " + a.out);
+  bool ok = true;
+  std::string text;
+  for (const sbh_depth_run &r : runs) {
+    if (!r.depth && !(a.depth_all && !a.bedgraph)) continue;
+    const std::string &name = L.hdr.names[r.ref_id];
+    if (a.bedgraph) {
+      text += name + "\t" + std::to_string(r.beg) + "\t" + std::to_string(r.end) + "\t" + std::to_string(r.depth) + "\n";
+    } else {
+      const std::string tail = "\t" + std::to_string(r.depth) + "\n";
+      for (int64_t p = r.beg + 1; p <= r.end; ++p) {
+        text += name;
+        text += '\t';
+        text += std::to_string(p);
+        text += tail;
+        if (text.size() >= (1u << 20)) {
+          ok = ok && fwrite(text.data(), 1, text.size(), f) == text.size();
+          text.clear();
+        }
+      }
+    }
+  }
+  ok = ok && fwrite(text.data(), 1, text.size(), f) == text.size() && fflush(f) == 0;
+  if (f != stdout) fclose(f);
+  if (!ok) throw Error(SBH_E_ARG, "short write to " + (a.out.empty() ? std::string("stdout") : a.out));
+  return 0;
+}
+
 // HTSJDKRewrite (cli/.../rewrite/HTSJDKRewrite.scala:40-92): the BAM's uncompressed stream --
 // header, then every record, or only the records whose index is in -r (:48-58) -- re-cut into
 // 65498-byte BGZF members on the GPU (sbh_bgzf_compress) plus the EOF member; -b / -i then
@@ -1256,6 +1359,7 @@ int main(int argc, char **argv) {
     else if (a.cmd == "check-blocks") rc = check_blocks(a);
     else if (a.cmd == "htsjdk-rewrite") rc = htsjdk_rewrite(a);
     else if (a.cmd == "view" || a.cmd == "sort") rc = view(a);
+    else if (a.cmd == "depth") rc = depth(a);
     else throw Error(SBH_E_ARG, "unknown command " + a.cmd);
     sbh_ctx_destroy(g_ctx);
     return rc;

@@ -708,6 +708,67 @@ int sbh_bam_gather_host(const uint8_t *flat, uint64_t flat_size, const uint64_t 
                         uint8_t *out, uint64_t out_cap, uint64_t *rec_off, uint64_t *rows,
                         uint64_t *n_kept, uint64_t *bad_row);
 
+/* ---- Per-base depth -----------------------------------------------------------------------
+ * How many kept records cover each reference position (samtools depth, bedtools genomecov -bg),
+ * computed on the device from the flat bytes and record starts of a scan and accumulated across
+ * shards in an sbh_depth, which belongs to a context and outlives the shards added to it
+ * (csrc/depth_core.h holds the definition for device and host).
+ * Spans: (ref_id, beg, end), 0-based half-open, 0 <= beg < end <= 2^31 - 1, ref_id in [0, n_ref)
+ * and strictly ascending.  Span k owns end - beg + 1 int32 slots of one array (the last takes the
+ * events that close at `end`); the accumulator costs 4 bytes per slot of HBM (SBH_E_NOMEM).
+ * A row is KEPT when the filter passes it (sbh_record_filter; NULL: every row).  A kept row with
+ * ref_id < 0 counts into n_unplaced; one whose reference has a span counts into n_counted and each
+ * of its CIGAR ops M, =, X -- and D with SBH_DEPTH_DEL -- covers [x, x + len) cut to the span, x
+ * starting at pos and advancing over M, D, N, =, X (64-bit arithmetic).  N never covers.  The
+ * stored CIGAR field counts: a long read's CIGAR in a CG:B,I tag is not followed.  cov_bases = the
+ * bases the add covered.
+ * sbh_records_depth_add uses the rows of the last valid scan on the shard, in their order, as
+ * sbh_records_bam_scan does (decode == 0 is enough; a row delivered twice counts twice), leaves the
+ * scan's rows, columns, SAM text and BAM stream as they are and synchronises the shard's stream
+ * before it returns.  Every row is validated as sbh_records_bam_scan validates it; a kept row with
+ * an op code above 8 or ref_id >= n_ref is bad too.  SBH_E_BAD_RECORD {row} for the first bad row,
+ * SBH_E_NEED_HALO instead when that row merely runs past an open shard end; a failed add leaves
+ * the accumulator exactly as it was.  One thread at a time per sbh_depth; a shard of another
+ * context gives SBH_E_ARG.
+ * sbh_depth_finish: depth[s] = the inclusive prefix sum of the slots, in place.  A run is a
+ * maximal stretch of equal depth inside one span (zero-depth runs included; the extra slot belongs
+ * to none).  covered = positions of depth >= 1, sum = depth over all positions = every add's
+ * cov_bases together.  After it an add or a second finish gives SBH_E_STATE until
+ * sbh_depth_reset (zero, open for adds again); before it the fetches give SBH_E_STATE and the
+ * device pointer is NULL.  sbh_depth_fetch: depth of positions beg + from .. beg + from + n of a
+ * span; sbh_depth_runs_fetch: runs [first, first + count) in span and position order.
+ * SBH_E_ARG for spans that are unsorted, share a reference, have beg >= end or a ref_id outside
+ * [0, n_ref), for n_spans == 0 and for unknown flag bits. */
+#define SBH_DEPTH_DEL 1u                      /* D ops cover (samtools depth -J) */
+typedef struct sbh_depth sbh_depth;           /* owned by a context; outlives shards */
+typedef struct { int32_t ref_id; int32_t pad; int64_t beg, end; } sbh_depth_span;
+typedef struct { uint64_t n, n_kept, n_counted, n_unplaced, cov_bases; } sbh_depth_add_result;
+typedef struct { uint64_t slots, n_runs, covered, sum; uint32_t max_depth, pad; } sbh_depth_sizes;
+typedef struct { int32_t ref_id; uint32_t depth; int64_t beg, end; } sbh_depth_run;
+
+int sbh_depth_create(sbh_ctx *ctx, const sbh_depth_span *spans, uint32_t n_spans, int32_t n_ref, uint32_t flags,
+                     sbh_depth **out);
+int sbh_depth_destroy(sbh_depth *d);
+int sbh_depth_reset(sbh_depth *d);
+int sbh_records_depth_add(sbh_shard *sh, sbh_depth *d, const sbh_record_filter *filter /* NULL: all */,
+                          sbh_depth_add_result *out);
+int sbh_depth_finish(sbh_depth *d, sbh_depth_sizes *out);
+int sbh_depth_fetch(sbh_depth *d, uint32_t span, uint64_t from, uint64_t n, uint32_t *depth);
+int sbh_depth_runs_fetch(sbh_depth *d, uint64_t first, uint64_t count, sbh_depth_run *runs);
+const void *sbh_depth_device_ptr(sbh_depth *d, uint32_t span);   /* u32 depth of the span, after finish */
+/* HOST ONLY, no context, no GPU.  sbh_depth_slots: the slots of the spans together, the sum of
+ * end - beg + 1 (0 for spans the other calls refuse).  sbh_depth_add_host adds into slots[] (the
+ * caller zeroes it first); SBH_E_BAD_RECORD with *bad_row = the first bad row, the slots untouched.
+ * sbh_depth_finish_host turns slots[] into depth in place (the same 32 bits, unsigned) and writes
+ * the first run_cap runs (runs may be NULL with run_cap 0); sizes->n_runs counts them all. */
+uint64_t sbh_depth_slots(const sbh_depth_span *spans, uint32_t n_spans);
+int sbh_depth_add_host(const uint8_t *flat, uint64_t flat_size, const uint64_t *starts, uint64_t n,
+                       const sbh_record_filter *filter, const sbh_depth_span *spans, uint32_t n_spans,
+                       int32_t n_ref, uint32_t flags, int32_t *slots, sbh_depth_add_result *out,
+                       uint64_t *bad_row);
+int sbh_depth_finish_host(int32_t *slots /* in place -> depth */, const sbh_depth_span *spans, uint32_t n_spans,
+                          sbh_depth_run *runs, uint64_t run_cap, sbh_depth_sizes *out);
+
 /* ---- BGZF writer -------------------------------------------------
  * The block compressor behind HTSJDKRewrite (cli/src/main/scala/org/hammerlab/bam/rewrite/
  * HTSJDKRewrite.scala:62-67: SAMFileWriterFactory.makeBAMWriter -> htsjdk

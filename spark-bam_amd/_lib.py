@@ -48,6 +48,9 @@ EXPORTS = [
     "sbh_records_bam_scan", "sbh_records_bam_device_ptr", "sbh_records_bam_fetch", "sbh_records_bam_read",
     "sbh_bam_gather_host",
     "sbh_records_bam_scan_order", "sbh_records_bam_sorted", "sbh_bam_sort_host", "sbh_bam_header_set_so",
+    "sbh_depth_create", "sbh_depth_destroy", "sbh_depth_reset", "sbh_records_depth_add", "sbh_depth_finish",
+    "sbh_depth_fetch", "sbh_depth_runs_fetch", "sbh_depth_device_ptr", "sbh_depth_slots", "sbh_depth_add_host",
+    "sbh_depth_finish_host",
 ]
 ORDER_SCAN, ORDER_COORDINATE = 0, 1  # SBH_ORDER_*
 LEVEL_HTSJDK, LEVEL_FAST = 5, -1  # sbh_bgzf_compress_level: htsjdk's zlib level 5 / this library's own coder
@@ -135,6 +138,16 @@ class SbhRecordFilter(C.Structure):
 
 class SbhBamSizes(C.Structure):
     _fields_ = [("n", C.c_uint64), ("n_kept", C.c_uint64), ("bytes", C.c_uint64)]
+
+
+class SbhDepthAddResult(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("n_kept", C.c_uint64), ("n_counted", C.c_uint64), ("n_unplaced", C.c_uint64),
+                ("cov_bases", C.c_uint64)]
+
+
+class SbhDepthSizes(C.Structure):
+    _fields_ = [("slots", C.c_uint64), ("n_runs", C.c_uint64), ("covered", C.c_uint64), ("sum", C.c_uint64),
+                ("max_depth", C.c_uint32), ("pad", C.c_uint32)]
 
 
 class SbhRecordsOut(C.Structure):  # host buffers (sbh_records_out); NULL = not copied
@@ -274,6 +287,16 @@ def lib():
         "sbh_records_bam_fetch": [P, P, P, P],
         "sbh_records_bam_read": [P, U64, U64, P],
         "sbh_bam_gather_host": [P, U64, P, U64, P, U64, C.POINTER(SbhRecordFilter), P, U64, P, P, PU64, PU64],
+        "sbh_depth_create": [P, P, U32, I32, U32, C.POINTER(P)],
+        "sbh_depth_destroy": [P],
+        "sbh_depth_reset": [P],
+        "sbh_records_depth_add": [P, P, C.POINTER(SbhRecordFilter), C.POINTER(SbhDepthAddResult)],
+        "sbh_depth_finish": [P, C.POINTER(SbhDepthSizes)],
+        "sbh_depth_fetch": [P, U32, U64, U64, P],
+        "sbh_depth_runs_fetch": [P, U64, U64, P],
+        "sbh_depth_add_host": [P, U64, P, U64, C.POINTER(SbhRecordFilter), P, U32, I32, U32, P,
+                               C.POINTER(SbhDepthAddResult), PU64],
+        "sbh_depth_finish_host": [P, P, U32, P, U64, C.POINTER(SbhDepthSizes)],
         "sbh_bgzf_compress": [P, P, U64, I32, P, U64, PU64, PU64, C.POINTER(C.c_float)],
         "sbh_bgzf_compress_level": [P, P, U64, I32, I32, P, U64, PU64, PU64, C.POINTER(C.c_float)],
     }
@@ -285,6 +308,10 @@ def lib():
     L.sbh_bgzf_compress_bound.restype = U64
     L.sbh_bai_bound.argtypes = [U64, U64, I32]
     L.sbh_bai_bound.restype = U64
+    L.sbh_depth_slots.argtypes = [P, U32]
+    L.sbh_depth_slots.restype = U64
+    L.sbh_depth_device_ptr.argtypes = [P, U32]
+    L.sbh_depth_device_ptr.restype = P
     L.sbh_stage_times.argtypes = [P, C.POINTER(C.c_double), I32]
     L.sbh_stage_times.restype = C.c_int
     L.sbh_last_error.argtypes = [P]

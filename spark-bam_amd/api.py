@@ -430,6 +430,71 @@ def sort_bam(path_or_bytes, out=None, level=5, index=False, ctx=None, reads_to_c
                     window=max(int(data.size), 1), sort="coordinate")
 
 
+def depth(path_or_bytes, region=None, flag_require=0, flag_exclude=0x704, min_mapq=0, count_del=False, window=None,
+          ctx=None, reads_to_check=DEFAULT_READS_TO_CHECK):
+    """Per-base depth of the file's records (what `samtools depth` and `bedtools genomecov -bg`
+    report), computed on the GPU: every window of iter_reads' walk is scanned and added into one
+    accumulator in HBM (Context.depth), which is then scanned into depth and runs of equal depth.
+
+    region: "NAME" (that reference whole), "NAME:BEG-END" (1-based, inclusive) or None -- every
+    reference whole, which costs 4 bytes of HBM per base of the genome.  A record counts when
+    (flag & flag_require) == flag_require, (flag & flag_exclude) == 0 (default 0x704: unmapped,
+    secondary, QC-fail, duplicate -- samtools depth's) and mapq >= min_mapq; its M, = and X ops
+    cover, D too with count_del (samtools depth -J), N never.  Base qualities and mate overlaps
+    are not looked at.  The whole file is read, whatever the region.
+
+    Returns a coverage.DepthResult: `.runs`, `.stats`, `.depth(name)`, `.text(all_positions=False)`
+    (samtools depth's lines) and `.bedgraph()` (genomecov -bg's)."""
+    from .coverage import DEPTH_RUN_DTYPE, DepthResult, region_spans
+    data = _file_array(path_or_bytes)
+    own_ctx = ctx is None
+    ctx = ctx or Context(0)
+    acc = None
+    try:
+        names, contig_len, _ = file_header(ctx, data)
+        try:
+            spans = region_spans(region, names, contig_len)
+        except ValueError as err:
+            raise SparkBamError(SBH_E_ARG, str(err))
+        acc = ctx.depth(spans, len(contig_len), count_del)
+        f = {"flag_require": flag_require, "flag_exclude": flag_exclude, "min_mapq": min_mapq}
+        totals = {}
+
+        def deliver(sh, first, E, _names):
+            # the walk looks at the chain's exit only after this returns, and runs the window again
+            # with a larger halo when the chain leaves the resident bytes: look first, add after
+            _, x = sh.chain_from(first, E)
+            blocks = sh.blocks()
+            seg = next((b[3] for b in blocks if b[5] & 1 and b[3] >= first), None)
+            last = seg is not None and E == seg or sh.file_offset + sh.n == sh.file_size and E == sh.flat_size
+            if not last and x >= sh.flat_size:
+                raise SparkBamError(SBH_E_NEED_HALO, "the chain leaves the halo")
+            sh.records_scan(first, E)
+            return [acc.add(sh, f)]
+
+        for (got,) in _iter_windows(data, deliver, window, ctx=ctx, reads_to_check=reads_to_check):
+            for k, v in got.items():
+                totals[k] = totals.get(k, 0) + v
+        stats = dict(acc.finish())
+        for k in ("n", "n_kept", "n_counted", "n_unplaced", "cov_bases"):
+            stats[k] = totals.get(k, 0)
+        runs = acc.runs() if stats["n_runs"] else np.zeros(0, dtype=DEPTH_RUN_DTYPE)
+        # the accumulator is closed below: a span's per-base depth is expanded from its runs on request
+        spans_l = list(spans)
+
+        def depths(k, runs=runs, spans=spans_l):
+            ref, b, e = spans[k]
+            r = runs[runs["ref_id"] == ref]
+            return np.repeat(r["depth"], (r["end"] - r["beg"]).astype(np.int64)).astype(np.uint32)
+
+        return DepthResult(runs, stats, spans_l, names, depths)
+    finally:
+        if acc is not None:
+            acc.close()
+        if own_ctx:
+            ctx.close()
+
+
 def _header_flat(ctx, data):
     """The BAM header's bytes (magic, text, reference dictionary: flat[0, header_end)), from the
     file's leading blocks inflated on the device."""

@@ -1,0 +1,492 @@
+// depth.hip -- per-base depth of a record scan's rows over the spans of an accumulator
+// (sbh_records_depth_add, sbh_depth_finish).  Events, validity and runs are defined in depth_core.h
+// for device and host.
+//
+//   k_depth_check      one row per lane: row_check, row_keep and, for kept rows, the reference range
+//                      and every op code; a keep bit per row (one ballot word per wave and pass), the
+//                      smallest bad row and the smallest row that only runs past the stream, n_kept,
+//                      n_unplaced (one atomic per workgroup and counter)
+//   k_depth_events     kept rows only, one row per lane: +1 / -1 into the slots by no-return integer
+//                      atomics.  A lane walks up to DEPTH_LANE_OPS ops itself; a row with more is
+//                      handed to its wave by ballot, and the wave takes such rows one at a time, 64
+//                      ops a round, each op's start from a 64-bit wave prefix sum of the advancing
+//                      lengths (two 32-bit scans: the low 16 bits and the rest).  n_counted, cov_bases.
+//   k_depth_tile_sums  per tile of DEPTH_TILE slots, their sum
+//   (scan)             tile sums -> tile bases
+//   k_depth_apply      the same tile cut: in-tile scan + base, depth written in place; per tile its
+//                      heads, max, covered, sum (k_depth_stats folds the last three: at most 64
+//                      workgroups' atomics meet in the three counters)
+//   (scan)             heads per tile -> the tile's first run
+//   k_depth_runs       the same tile cut over the finished depth: every head writes its run's
+//                      (ref_id, depth, beg) and closes the run before it when that lies in its span;
+//                      a span's extra slot closes the span's last run
+//
+// A finish is three launches and two small scans over the slots (histogram, scan, scatter in the
+// shape of DESIGN 15): no workgroup waits on another inside a kernel.
+//
+// Slot s of a tile belongs to (wave, round, lane, e) with s = tile * DEPTH_TILE + wave * 1024 +
+// round * 256 + lane * 4 + e: a lane reads 16 aligned bytes, a wave 1 KiB in a row, and the order
+// (wave, round, lane, e) ascends with s, so prefix sums nest: e within the lane, lanes by a DPP wave
+// scan, rounds by the wave's running total, waves through LDS.
+#include <algorithm>
+
+#define SBH_HD __host__ __device__
+#include "depth_core.h"
+#include "sbh_internal.h"
+
+namespace sbh {
+namespace {
+
+using sbh_dep::DEPTH_LANE_OPS;
+using sbh_dep::DEPTH_TILE;
+using sbh_dep::Span;
+constexpr uint32_t ROWS_GRID = 1024;  // the row kernels: 262144 rows a pass, as k_bam_keep
+constexpr uint32_t TILE_T = 256, TILE_ROUNDS = 4;
+static_assert(DEPTH_TILE == TILE_T * TILE_ROUNDS * 4, "a tile is 4 waves x 4 rounds x 64 lanes x 4 slots");
+
+__device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
+  for (int m = 1; m < 64; m <<= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, m);
+  return v;
+}
+
+// One value per workgroup into *dst: v summed over the 4 waves (every lane calls; s_red: 4 words).
+__device__ __forceinline__ void block_add(uint64_t v, uint64_t *s_red, unsigned long long *dst) {
+  v = wave_sum(v);
+  __syncthreads();  // (s_red may still be read from the call before)
+  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const uint64_t t = s_red[0] + s_red[1] + s_red[2] + s_red[3];
+    if (t) atomicAdd(dst, (unsigned long long)t);
+  }
+}
+
+// keep: one u64 per 64 rows, bit (i & 63) of word i >> 6; every word below ceil(n / 64) is written.
+// acc: bad, past (preset ~0), n_kept, n_unplaced (preset 0).
+__global__ __launch_bounds__(256) void k_depth_check(const uint8_t *__restrict__ U, const uint64_t *pos, uint64_t n,
+                                                     uint64_t total, sbh_bam::Filter F, int32_t n_ref, uint64_t *keep,
+                                                     unsigned long long *acc) {
+  __shared__ uint64_t s_red[4];
+  const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
+  uint64_t kept = 0, unplaced = 0, bad = ~0ull, past = ~0ull;
+  // (the loop is uniform in the workgroup: the ballot runs with every lane of the wave)
+  for (uint64_t base = (uint64_t)blockIdx.x * blockDim.x; base < n; base += step) {
+    const uint64_t i = base + threadIdx.x;
+    bool k = false;
+    if (i < n) {
+      const uint64_t p = pos[i];
+      uint64_t bytes = 0;
+      const int v = sbh_bam::row_check(U, total, p, &bytes);
+      if (v != sbh_bam::ROW_OK) {
+        bad = bad < i ? bad : i;
+        if (v == sbh_bam::ROW_PAST) past = past < i ? past : i;
+      } else if (sbh_bam::row_keep(U + p, i, F)) {
+        const uint8_t *r = U + p;
+        const int32_t ref_id = (int32_t)sbh_bam::ld32(r + 4);
+        if (ref_id >= n_ref || !sbh_dep::ops_ok(r)) {
+          bad = bad < i ? bad : i;
+        } else {
+          k = true;
+          ++kept;
+          if (ref_id < 0) ++unplaced;
+        }
+      }
+    }
+    const uint64_t word = __ballot(k);
+    if ((threadIdx.x & 63) == 0 && i < n) keep[i >> 6] = word;
+  }
+  if (bad != ~0ull) atomicMin(acc + 0, (unsigned long long)bad);
+  if (past != ~0ull) atomicMin(acc + 1, (unsigned long long)past);
+  block_add(kept, s_red, acc + 2);
+  block_add(unplaced, s_red, acc + 3);
+}
+
+// +1 at slot off + a - beg, -1 at slot off + b - beg for [x, x + len) cut to [beg, end).  Both
+// indices are re-tested against S whatever the record says.
+__device__ __forceinline__ uint64_t emit(int32_t *slots, uint64_t S, uint64_t off, int64_t beg, int64_t end, int64_t x,
+                                         int64_t len) {
+  int64_t a, b;
+  if (!sbh_dep::clip(x, len, beg, end, &a, &b)) return 0;
+  const uint64_t ia = off + (uint64_t)(a - beg), ib = off + (uint64_t)(b - beg);
+  if (ia < S) atomicAdd(slots + ia, 1);
+  if (ib < S) atomicAdd(slots + ib, -1);
+  return (uint64_t)(b - a);
+}
+
+// Runs only after k_depth_check found no bad row: every kept row is valid, its CIGAR words lie
+// inside its record and its ref_id is below n_ref.  acc: n_counted, cov_bases.
+__global__ __launch_bounds__(256) void k_depth_events(const uint8_t *__restrict__ U, const uint64_t *pos, uint64_t n,
+                                                      const uint64_t *keep, const Span *sp, const uint64_t *off,
+                                                      uint32_t n_spans, uint32_t flags, int32_t *slots, uint64_t S,
+                                                      unsigned long long *acc) {
+  __shared__ uint64_t s_red[4];
+  const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
+  const uint32_t lane = threadIdx.x & 63;
+  uint64_t counted = 0, cov = 0;
+  for (uint64_t base = (uint64_t)blockIdx.x * blockDim.x; base < n; base += step) {
+    const uint64_t i = base + threadIdx.x;
+    const uint8_t *r = U;
+    uint32_t nc = 0;
+    uint64_t o = 0;
+    int64_t beg = 0, end = 0, x = 0;
+    bool go = false;
+    if (i < n && ((keep[i >> 6] >> (i & 63)) & 1)) {
+      r = U + pos[i];
+      const int32_t ref_id = (int32_t)sbh_bam::ld32(r + 4);
+      const uint32_t k = ref_id < 0 ? n_spans : sbh_dep::span_of(sp, n_spans, ref_id);
+      if (k < n_spans) {
+        go = true;
+        ++counted;
+        nc = sbh_dep::n_cigar_of(r);
+        o = off[k], beg = sp[k].beg, end = sp[k].end;
+        x = (int32_t)sbh_bam::ld32(r + 8);
+      }
+    }
+    const bool is_long = go && nc > DEPTH_LANE_OPS;
+    if (go && !is_long) {
+      const uint8_t *c = sbh_dep::cigar_of(r);
+      for (uint32_t j = 0; j < nc; ++j) {
+        const uint32_t w = sbh_bam::ld32(c + 4 * j), op = w & 15u;
+        const int64_t l = w >> 4;
+        if (sbh_dep::op_covers(op, flags)) cov += emit(slots, S, o, beg, end, x, l);
+        if (sbh_dep::op_advances(op)) x += l;
+      }
+    }
+    // the wave's long rows, one at a time (the mask is the same in every lane: uniform loops)
+    for (uint64_t todo = __ballot(is_long); todo; todo &= todo - 1) {
+      const int src = __builtin_ctzll(todo);
+      const uint8_t *c = sbh_dep::cigar_of(U + (uint64_t)__shfl((unsigned long long)(r - U), src));
+      const uint32_t wnc = (uint32_t)__shfl((int)nc, src);
+      const uint64_t wo = (uint64_t)__shfl((unsigned long long)o, src);
+      const int64_t wbeg = (int64_t)__shfl((long long)beg, src), wend = (int64_t)__shfl((long long)end, src);
+      int64_t wx = (int64_t)__shfl((long long)x, src);
+      for (uint32_t b0 = 0; b0 < wnc; b0 += 64) {
+        const uint32_t j = b0 + lane;
+        const uint32_t w = j < wnc ? sbh_bam::ld32(c + 4 * (uint64_t)j) : 0u, op = w & 15u;
+        const uint32_t l = w >> 4, adv = sbh_dep::op_advances(op) ? l : 0u;
+        // 64 lengths below 2^28: the low 16 bits sum below 2^22, the high 12 below 2^18
+        const uint64_t incl = (uint64_t)wave_incl_scan(adv & 0xffffu) + ((uint64_t)wave_incl_scan(adv >> 16) << 16);
+        if (j < wnc && sbh_dep::op_covers(op, flags))
+          cov += emit(slots, S, wo, wbeg, wend, wx + (int64_t)(incl - adv), (int64_t)l);
+        wx += (int64_t)__shfl((unsigned long long)incl, 63);
+      }
+    }
+  }
+  block_add(counted, s_red, acc + 0);
+  block_add(cov, s_red, acc + 1);
+}
+
+// ---- the tile kernels ---------------------------------------------------------------------------
+// the first slot of (wave, round, lane) in its tile
+__device__ __forceinline__ uint32_t tile_slot(uint32_t wave, uint32_t round, uint32_t lane) {
+  return wave * (DEPTH_TILE / 4) + round * 256 + lane * 4;
+}
+// v[e] = slot first + e of the tile, 0 at and behind `count` (a slot is read only below the tile's count)
+__device__ __forceinline__ void load4(const int32_t *tile, uint32_t first, uint32_t count, uint32_t v[4]) {
+  if (first + 4 <= count) {
+    const int4 q = *reinterpret_cast<const int4 *>(tile + first);
+    v[0] = (uint32_t)q.x, v[1] = (uint32_t)q.y, v[2] = (uint32_t)q.z, v[3] = (uint32_t)q.w;
+  } else {
+#pragma unroll
+    for (uint32_t e = 0; e < 4; ++e) v[e] = first + e < count ? (uint32_t)tile[first + e] : 0u;
+  }
+}
+__device__ __forceinline__ uint32_t tile_count(uint64_t tile, uint64_t S) {
+  const uint64_t base = tile * DEPTH_TILE;
+  return (uint32_t)(S - base < DEPTH_TILE ? S - base : DEPTH_TILE);
+}
+
+// x[r]: this lane's total of round r.  Returns in x[r] the sum of everything before (wave, r, lane)
+// in the tile (32-bit wrapping), in *total the tile's.  Every lane of the workgroup calls.
+__device__ __forceinline__ void tile_excl_scan(uint32_t x[TILE_ROUNDS], uint32_t *s_wave, uint32_t *total) {
+  const uint32_t wave = threadIdx.x >> 6;
+  uint32_t run = 0;
+#pragma unroll
+  for (uint32_t r = 0; r < TILE_ROUNDS; ++r) {
+    const uint32_t incl = wave_incl_scan(x[r]);
+    const uint32_t excl = run + incl - x[r];
+    run += (uint32_t)__shfl((int)incl, 63);
+    x[r] = excl;
+  }
+  __syncthreads();  // (s_wave may still be read from the call before)
+  if ((threadIdx.x & 63) == 0) s_wave[wave] = run;
+  __syncthreads();
+  uint32_t before = 0, all = 0;
+  for (uint32_t w = 0; w < 4; ++w) {
+    if (w < wave) before += s_wave[w];
+    all += s_wave[w];
+  }
+#pragma unroll
+  for (uint32_t r = 0; r < TILE_ROUNDS; ++r) x[r] += before;
+  *total = all;
+}
+
+// grid = tiles.  sums[tile] = the tile's slots added up, sign-extended (the scan adds modulo 2^64).
+__global__ __launch_bounds__(TILE_T) void k_depth_tile_sums(const int32_t *slots, uint64_t S, uint64_t *sums) {
+  __shared__ uint64_t s_red[4];
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const uint32_t count = tile_count(blockIdx.x, S);
+  const int32_t *tile = slots + (uint64_t)blockIdx.x * DEPTH_TILE;
+  int64_t sum = 0;
+#pragma unroll
+  for (uint32_t r = 0; r < TILE_ROUNDS; ++r) {
+    uint32_t v[4];
+    load4(tile, tile_slot(wave, r, lane), count, v);
+    sum += (int64_t)(int32_t)v[0] + (int32_t)v[1] + (int32_t)v[2] + (int32_t)v[3];
+  }
+  const uint64_t w = wave_sum((uint64_t)sum);
+  if (lane == 0) s_red[wave] = w;
+  __syncthreads();
+  if (threadIdx.x == 0) sums[blockIdx.x] = s_red[0] + s_red[1] + s_red[2] + s_red[3];
+}
+
+// What a lane needs about the spans of its 4 slots: slot s is a span's first when s == off[k], its
+// extra slot when s + 1 == off[k + 1].  off has n_spans + 1 entries and s < S == off[n_spans], so
+// span_of_slot's k is below n_spans and off[k + 1] exists.
+struct SlotSpan {
+  uint32_t k;
+  uint64_t first, next;  // off[k], off[k + 1]
+};
+__device__ __forceinline__ SlotSpan slot_span(const uint64_t *off, uint32_t n_spans, uint64_t s) {
+  const uint32_t k = sbh_dep::span_of_slot(off, n_spans, s);
+  return SlotSpan{k, off[k], off[k + 1]};
+}
+// the span of slot s, from the span of a slot before it (spans may be 2 slots short: a loop)
+__device__ __forceinline__ void slot_span_to(SlotSpan &q, const uint64_t *off, uint32_t n_spans, uint64_t s) {
+  while (s >= q.next && q.k + 1 < n_spans) ++q.k, q.first = q.next, q.next = off[q.k + 1];
+}
+
+// base: the exclusive scan of the tile sums.  Depth in place; heads[tile]; tstat: 3 n_tiles words,
+// the tile's max depth, covered positions and sum of depth at [tile], [n_tiles + tile], [2 n_tiles +
+// tile] (k_depth_stats folds them: no workgroup of this kernel touches a word another one does).
+__global__ __launch_bounds__(TILE_T) void k_depth_apply(int32_t *slots, uint64_t S, const uint64_t *base,
+                                                        const uint64_t *off, uint32_t n_spans, uint64_t *heads,
+                                                        uint64_t *tstat) {
+  __shared__ uint32_t s_wave[4];
+  __shared__ uint64_t s_red[4][4];
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const uint32_t count = tile_count(blockIdx.x, S);
+  const uint64_t t0 = (uint64_t)blockIdx.x * DEPTH_TILE;
+  int32_t *tile = slots + t0;
+  uint32_t v[TILE_ROUNDS][4], x[TILE_ROUNDS];
+#pragma unroll
+  for (uint32_t r = 0; r < TILE_ROUNDS; ++r) {
+    load4(tile, tile_slot(wave, r, lane), count, v[r]);
+    x[r] = v[r][0] + v[r][1] + v[r][2] + v[r][3];
+  }
+  uint32_t total;
+  tile_excl_scan(x, s_wave, &total);
+  const uint32_t tb = (uint32_t)base[blockIdx.x];  // (depth is the prefix modulo 2^32)
+  uint32_t n_heads = 0, covered = 0, mx = 0;  // (at most 16 slots a lane)
+  uint64_t sum = 0;
+#pragma unroll
+  for (uint32_t r = 0; r < TILE_ROUNDS; ++r) {
+    const uint32_t first = tile_slot(wave, r, lane);
+    if (first >= count) continue;
+    const uint64_t s0 = t0 + first;
+    SlotSpan q = slot_span(off, n_spans, s0);
+    uint32_t d = tb + x[r], out[4];
+    if (first + 4 <= count && q.first < s0 && s0 + 4 < q.next) {
+      // the four slots lie inside one span, none of them its first or its extra slot
+#pragma unroll
+      for (uint32_t e = 0; e < 4; ++e) {
+        d += v[r][e];
+        out[e] = d;
+        n_heads += v[r][e] != 0;
+        mx = d > mx ? d : mx;
+        covered += d != 0;
+        sum += d;
+      }
+    } else {
+#pragma unroll
+      for (uint32_t e = 0; e < 4; ++e) {
+        const uint64_t s = s0 + e;
+        d += v[r][e];
+        out[e] = d;
+        if (first + e >= count) continue;
+        slot_span_to(q, off, n_spans, s);
+        if (s + 1 == q.next) continue;  // the extra slot
+        n_heads += s == q.first || v[r][e] != 0;
+        mx = d > mx ? d : mx;
+        covered += d != 0;
+        sum += d;
+      }
+    }
+    if (first + 4 <= count) {
+      *reinterpret_cast<int4 *>(tile + first) = make_int4((int)out[0], (int)out[1], (int)out[2], (int)out[3]);
+    } else {
+#pragma unroll
+      for (uint32_t e = 0; e < 4; ++e)
+        if (first + e < count) tile[first + e] = (int32_t)out[e];
+    }
+  }
+  for (int m = 1; m < 64; m <<= 1) {
+    const uint32_t o = (uint32_t)__shfl_xor((int)mx, m);
+    mx = o > mx ? o : mx;
+  }
+  const uint64_t wh = wave_sum(n_heads), wc = wave_sum(covered), ws = wave_sum(sum);
+  if (lane == 0) s_red[wave][0] = wh, s_red[wave][1] = wc, s_red[wave][2] = ws, s_red[wave][3] = mx;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint64_t h = 0, c = 0, t = 0, m = 0;
+    for (uint32_t w = 0; w < 4; ++w) h += s_red[w][0], c += s_red[w][1], t += s_red[w][2], m = s_red[w][3] > m ? s_red[w][3] : m;
+    heads[blockIdx.x] = h;
+    tstat[blockIdx.x] = m;
+    tstat[(uint64_t)gridDim.x + blockIdx.x] = c;
+    tstat[2 * (uint64_t)gridDim.x + blockIdx.x] = t;
+  }
+}
+
+// tstat: k_depth_apply's per-tile max, covered and sum (3 nt words) -> acc: max, covered, sum
+// (preset 0), one atomic per workgroup and counter.
+__global__ __launch_bounds__(256) void k_depth_stats(const uint64_t *tstat, uint64_t nt, unsigned long long *acc) {
+  __shared__ uint64_t s_red[4];
+  __shared__ uint64_t s_max[4];
+  uint64_t mx = 0, covered = 0, sum = 0;
+  for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < nt; t += (uint64_t)gridDim.x * blockDim.x) {
+    const uint64_t m = tstat[t];
+    mx = m > mx ? m : mx;
+    covered += tstat[nt + t];
+    sum += tstat[2 * nt + t];
+  }
+  for (int m = 1; m < 64; m <<= 1) {
+    const uint64_t o = (uint64_t)__shfl_xor((unsigned long long)mx, m);
+    mx = o > mx ? o : mx;
+  }
+  if ((threadIdx.x & 63) == 0) s_max[threadIdx.x >> 6] = mx;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (uint32_t w = 1; w < 4; ++w) mx = s_max[w] > mx ? s_max[w] : mx;
+    if (mx) atomicMax(acc + 0, (unsigned long long)mx);
+  }
+  block_add(covered, s_red, acc + 1);
+  block_add(sum, s_red, acc + 2);
+}
+
+// depth: the finished array; hbase: the exclusive scan of heads (the tile's first run); n_runs: its
+// total.  Every store index is hbase[tile] + (heads before the slot in the tile) [- 1], a rank below
+// n_runs by construction; the test against n_runs keeps a store inside runs[] whatever the scans hold.
+__global__ __launch_bounds__(TILE_T) void k_depth_runs(const int32_t *depth, uint64_t S, const uint64_t *hbase,
+                                                       const Span *sp, const uint64_t *off, uint32_t n_spans,
+                                                       uint64_t n_runs, sbh_depth_run *runs) {
+  __shared__ uint32_t s_wave[4];
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const uint32_t count = tile_count(blockIdx.x, S);
+  const uint64_t t0 = (uint64_t)blockIdx.x * DEPTH_TILE;
+  const int32_t *tile = depth + t0;
+  uint32_t v[TILE_ROUNDS][4], prev[TILE_ROUNDS], x[TILE_ROUNDS], hd[TILE_ROUNDS];
+#pragma unroll
+  for (uint32_t r = 0; r < TILE_ROUNDS; ++r) {
+    const uint32_t first = tile_slot(wave, r, lane);
+    load4(tile, first, count, v[r]);
+    // the depth before the lane's first slot: the lane below holds it, lane 0 reads it (slot t0 +
+    // first - 1 >= 0 is below S; the array is no longer written)
+    prev[r] = (uint32_t)__shfl_up((int)v[r][3], 1);
+    if (lane == 0) prev[r] = t0 + first && first < count ? (uint32_t)depth[t0 + first - 1] : 0u;
+    hd[r] = 0;
+    if (first < count) {
+      SlotSpan q = slot_span(off, n_spans, t0 + first);
+      uint32_t p = prev[r];
+      if (first + 4 <= count && q.first < t0 + first && t0 + first + 4 < q.next) {
+        // inside one span, none of the four its first or its extra slot: a head is a change of depth
+#pragma unroll
+        for (uint32_t e = 0; e < 4; ++e) {
+          if (v[r][e] != p) hd[r] |= 1u << e;
+          p = v[r][e];
+        }
+      } else {
+#pragma unroll
+        for (uint32_t e = 0; e < 4; ++e) {
+          const uint64_t s = t0 + first + e;
+          if (first + e < count) {
+            slot_span_to(q, off, n_spans, s);
+            if (s + 1 != q.next && (s == q.first || v[r][e] != p)) hd[r] |= 1u << e;
+          }
+          p = v[r][e];
+        }
+      }
+    }
+    x[r] = (uint32_t)__popc(hd[r]);
+  }
+  uint32_t total;
+  tile_excl_scan(x, s_wave, &total);
+  const uint64_t hb = hbase[blockIdx.x];
+#pragma unroll
+  for (uint32_t r = 0; r < TILE_ROUNDS; ++r) {
+    const uint32_t first = tile_slot(wave, r, lane);
+    if (first >= count) continue;
+    SlotSpan q = slot_span(off, n_spans, t0 + first);
+    uint64_t rank = hb + x[r];  // heads before the slot
+#pragma unroll
+    for (uint32_t e = 0; e < 4; ++e) {
+      const uint64_t s = t0 + first + e;
+      if (first + e >= count) continue;
+      slot_span_to(q, off, n_spans, s);
+      const int64_t at = sp[q.k].beg + (int64_t)(s - q.first);
+      if (s + 1 == q.next) {  // the extra slot: at == the span's end
+        if (rank && rank - 1 < n_runs) runs[rank - 1].end = at;
+      } else if ((hd[r] >> e) & 1u) {
+        if (s != q.first && rank && rank - 1 < n_runs) runs[rank - 1].end = at;
+        if (rank < n_runs) {
+          runs[rank].ref_id = sp[q.k].ref_id;
+          runs[rank].depth = v[r][e];
+          runs[rank].beg = at;
+        }
+        ++rank;
+      }
+    }
+  }
+}
+
+uint32_t rows_grid(uint64_t n) { return (uint32_t)std::min<uint64_t>((n + 255) / 256, ROWS_GRID); }
+
+}  // namespace
+
+uint64_t depth_tiles(uint64_t S) { return (S + DEPTH_TILE - 1) / DEPTH_TILE; }
+
+// keep: ceil(n / 64) words; acc: ctr::DEPTH_BAD .. DEPTH_UNPLACED (preset ~0, ~0, 0, 0)
+hipError_t launch_depth_check(const uint8_t *U, const uint64_t *pos, uint64_t n, uint64_t total, uint32_t flag_require,
+                              uint32_t flag_exclude, int32_t min_mapq, const uint64_t *row_begin, const uint64_t *row_end,
+                              uint64_t n_row_ranges, int32_t n_ref, uint64_t *keep, unsigned long long *acc,
+                              hipStream_t st) {
+  if (!n) return hipSuccess;
+  const sbh_bam::Filter F{flag_require, flag_exclude, min_mapq, row_begin, row_end, n_row_ranges};
+  hipLaunchKernelGGL(k_depth_check, dim3(rows_grid(n)), dim3(256), 0, st, U, pos, n, total, F, n_ref, keep, acc);
+  return hipGetLastError();
+}
+
+// acc: ctr::DEPTH_COUNTED, DEPTH_COV (preset 0)
+hipError_t launch_depth_events(const uint8_t *U, const uint64_t *pos, uint64_t n, const uint64_t *keep,
+                               const sbh_depth_span *spans, const uint64_t *off, uint32_t n_spans, uint32_t flags,
+                               int32_t *slots, uint64_t S, unsigned long long *acc, hipStream_t st) {
+  if (!n) return hipSuccess;
+  static_assert(sizeof(sbh_depth_span) == sizeof(Span), "one layout");
+  hipLaunchKernelGGL(k_depth_events, dim3(rows_grid(n)), dim3(256), 0, st, U, pos, n, keep,
+                     reinterpret_cast<const Span *>(spans), off, n_spans, flags, slots, S, acc);
+  return hipGetLastError();
+}
+
+hipError_t launch_depth_tile_sums(const int32_t *slots, uint64_t S, uint64_t *sums, hipStream_t st) {
+  hipLaunchKernelGGL(k_depth_tile_sums, dim3((uint32_t)depth_tiles(S)), dim3(TILE_T), 0, st, slots, S, sums);
+  return hipGetLastError();
+}
+
+// tstat: 3 depth_tiles(S) words, every one written; acc: max, covered, sum (preset 0)
+hipError_t launch_depth_apply(int32_t *slots, uint64_t S, const uint64_t *base, const uint64_t *off, uint32_t n_spans,
+                              uint64_t *heads, uint64_t *tstat, unsigned long long *acc, hipStream_t st) {
+  const uint64_t nt = depth_tiles(S);
+  hipLaunchKernelGGL(k_depth_apply, dim3((uint32_t)nt), dim3(TILE_T), 0, st, slots, S, base, off, n_spans, heads, tstat);
+  hipLaunchKernelGGL(k_depth_stats, dim3((uint32_t)std::min<uint64_t>((nt + 255) / 256, 64)), dim3(256), 0, st, tstat, nt,
+                     acc);
+  return hipGetLastError();
+}
+
+hipError_t launch_depth_runs(const int32_t *depth, uint64_t S, const uint64_t *hbase, const sbh_depth_span *spans,
+                             const uint64_t *off, uint32_t n_spans, uint64_t n_runs, sbh_depth_run *runs,
+                             hipStream_t st) {
+  hipLaunchKernelGGL(k_depth_runs, dim3((uint32_t)depth_tiles(S)), dim3(TILE_T), 0, st, depth, S, hbase,
+                     reinterpret_cast<const Span *>(spans), off, n_spans, n_runs, runs);
+  return hipGetLastError();
+}
+
+}  // namespace sbh

@@ -219,6 +219,27 @@ hipError_t launch_sort_pass(const uint64_t *key, const uint32_t *row, uint64_t m
 hipError_t launch_sort_apply(const uint64_t *pos, const uint64_t *len, const uint32_t *row, uint64_t m, uint64_t *pos2,
                              uint64_t *len2, uint64_t *kh, hipStream_t st);
 hipError_t launch_sort_rows(const uint32_t *row, uint64_t m, uint64_t *rows, hipStream_t st);
+// Per-base depth (depth.hip; events, validity and runs in depth_core.h).  launch_depth_check: keep =
+// ceil(n / 64) ballot words, acc = ctr::DEPTH_BAD .. DEPTH_UNPLACED (preset ~0, ~0, 0, 0).
+// launch_depth_events: acc = ctr::DEPTH_COUNTED, DEPTH_COV (preset 0); off: n_spans + 1 entries,
+// off[n_spans] == S.  The finish: tile sums (depth_tiles(S) words), their exclusive scan as base,
+// launch_depth_apply (heads: depth_tiles(S) + 1 words, the caller zeroes the last; tstat: 3
+// depth_tiles(S) words of per-tile max, covered, sum, folded into acc: max, covered, sum, preset 0),
+// the scan of heads as hbase, launch_depth_runs.
+uint64_t depth_tiles(uint64_t S);
+hipError_t launch_depth_check(const uint8_t *U, const uint64_t *pos, uint64_t n, uint64_t total, uint32_t flag_require,
+                              uint32_t flag_exclude, int32_t min_mapq, const uint64_t *row_begin, const uint64_t *row_end,
+                              uint64_t n_row_ranges, int32_t n_ref, uint64_t *keep, unsigned long long *acc,
+                              hipStream_t st);
+hipError_t launch_depth_events(const uint8_t *U, const uint64_t *pos, uint64_t n, const uint64_t *keep,
+                               const sbh_depth_span *spans, const uint64_t *off, uint32_t n_spans, uint32_t flags,
+                               int32_t *slots, uint64_t S, unsigned long long *acc, hipStream_t st);
+hipError_t launch_depth_tile_sums(const int32_t *slots, uint64_t S, uint64_t *sums, hipStream_t st);
+hipError_t launch_depth_apply(int32_t *slots, uint64_t S, const uint64_t *base, const uint64_t *off, uint32_t n_spans,
+                              uint64_t *heads, uint64_t *tstat, unsigned long long *acc, hipStream_t st);
+hipError_t launch_depth_runs(const int32_t *depth, uint64_t S, const uint64_t *hbase, const sbh_depth_span *spans,
+                             const uint64_t *off, uint32_t n_spans, uint64_t n_runs, sbh_depth_run *runs,
+                             hipStream_t st);
 // BGZF footer CRC32 of every inflated, non-truncated block (crc.hip).
 hipError_t launch_block_crc(const uint8_t *comp, DevBlocks bl, uint64_t nblocks, const uint8_t *U,
                             unsigned long long *n_bad, unsigned long long *first_bad, hipStream_t st);
@@ -326,6 +347,11 @@ constexpr uint32_t SAM_BAD = 48, H_SAM_NHOST = 49, H_SAM_TOTAL = 50;
 constexpr uint32_t BAM_BAD = 51, BAM_PAST = 52, H_BAM_BYTES = 53, H_BAM_KH = 54;
 // coordinate order (k_sort_keys): descents key[k - 1] > key[k], the OR and the AND of all keys
 constexpr uint32_t SORT_DESC = 55, SORT_OR = 56, SORT_AND = 57, SORT_END = 58;
+// depth add (k_depth_check): first bad row, first row that only runs past the stream's end, kept
+// rows, kept rows without a reference; (k_depth_events): rows walked, bases covered
+constexpr uint32_t DEPTH_BAD = SORT_END, DEPTH_PAST = DEPTH_BAD + 1, DEPTH_KEPT = DEPTH_BAD + 2;
+constexpr uint32_t DEPTH_UNPLACED = DEPTH_BAD + 3, DEPTH_COUNTED = DEPTH_BAD + 4, DEPTH_COV = DEPTH_BAD + 5;
+constexpr uint32_t DEPTH_END = DEPTH_BAD + 6;
 // inflate status (launch_first_bad): the first block whose status is not INF_OK
 constexpr uint32_t FIRST_BAD = 100;
 // h_ctr only: that block's status (u32), fetched after the run's copy of [0, CTR_RUN_WORDS)
@@ -341,6 +367,7 @@ constexpr uint32_t H_RUN_TPL = 1024;
 constexpr uint32_t CTR_CALL_END = 4 + ctr::FULL_NNZ * ctr::FULL_FLAGS + ctr::FULL_NNZ * ctr::FULL_RBE;
 static_assert(CTR_CALL_END <= CTR_TRUE_SPREAD && CTR_NEXT18 + 4 <= CTR_WORDS, "counter buffer layout");
 static_assert(ctr::FULL_END == CTR_CALL_END, "the full checker's counters end the per-call region");
+static_assert(ctr::DEPTH_END <= ctr::FIRST_BAD, "the depth counters end before the first bad block");
 // what the run template presets (the eager counters, FindRecordStart's best, the proof
 // counters, the first bad block) travels in the run's one copy each way ...
 static_assert(ctr::EAGER_END <= CTR_RUN_WORDS && ctr::FRS_BEST < CTR_RUN_WORDS &&

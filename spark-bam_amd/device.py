@@ -5,9 +5,11 @@ import weakref
 
 import numpy as np
 
+from .coverage import DEPTH_DEL, DEPTH_RUN_DTYPE, span_array
 from .records import pack_ref_names, record_columns, record_filter
 
-from ._lib import (ORDER_COORDINATE, SBH_OK, SbhBaiSizes, SbhBamSizes, SbhBatchSplit, SbhBlock, SbhCheckOpts, SbhCheckResult, SbhRecordsOut,
+from ._lib import (ORDER_COORDINATE, SBH_OK, SbhBaiSizes, SbhBamSizes, SbhBatchSplit, SbhBlock, SbhCheckOpts, SbhCheckResult, SbhDepthAddResult,
+                   SbhDepthSizes, SbhRecordsOut,
                    SbhRecordsSizes, SbhSamSizes, SbhShardResult, SbhSplitBatchResult, SbhSplitRecordsResult,
                    SbhStreamOpts, SbhStreamResult, SparkBamError, error_for, lib)
 
@@ -220,6 +222,86 @@ class Context:
 
     def shard(self, comp, file_offset=0, file_size=None, on_device=False, nbytes=None):
         return Shard(self, comp, file_offset, file_size, on_device, nbytes)
+
+    def depth(self, spans, n_ref, count_del=False):
+        """A per-base depth accumulator over spans [(ref_id, beg, end), ...] (0-based half-open,
+        one per reference, ascending) of a file with n_ref references (sbh_depth_create): 4 bytes of
+        HBM per position plus one per span.  count_del: D ops cover (samtools depth -J)."""
+        return Depth(self, spans, n_ref, count_del)
+
+
+class Depth:
+    """sbh_depth: scans of any number of this context's shards added into one array of slots
+    (`add`), then turned into per-base depth and runs of equal depth on the GPU (`finish`)."""
+
+    def __init__(self, ctx, spans, n_ref, count_del=False):
+        self.ctx = ctx
+        self.spans = [(int(r), int(b), int(e)) for r, b, e in spans]
+        sp = span_array(self.spans)
+        h = C.c_void_p()
+        _check(ctx.h, lib().sbh_depth_create(ctx.h, _ptr(sp) if sp.size else None, int(sp.size), int(n_ref),
+                                             DEPTH_DEL if count_del else 0, C.byref(h)))
+        self.h = h
+        self.sizes = None
+        ctx._shards.add(self)  # (closed with the context, before it)
+
+    def close(self):
+        if self.h:
+            if self.ctx.h:
+                lib().sbh_depth_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, shard, filter=None):
+        """The rows of the last scan on `shard` that `filter` keeps (records.record_filter's dict,
+        None: all), added (sbh_records_depth_add).  Returns the add's counts as a dict: n, n_kept,
+        n_counted, n_unplaced, cov_bases.  A failed add leaves the accumulator as it was."""
+        f, keep = record_filter(filter)
+        r = SbhDepthAddResult()
+        _check(self.ctx.h, lib().sbh_records_depth_add(shard.h, self.h, C.byref(f) if f is not None else None,
+                                                       C.byref(r)))
+        del keep
+        return {k: int(getattr(r, k)) for k, _ in SbhDepthAddResult._fields_}
+
+    def finish(self):
+        """Slots -> depth, runs and stats on the GPU (sbh_depth_finish): a dict slots, n_runs,
+        covered, sum, max_depth.  No add may follow until reset()."""
+        sz = SbhDepthSizes()
+        _check(self.ctx.h, lib().sbh_depth_finish(self.h, C.byref(sz)))
+        self.sizes = {k: int(getattr(sz, k)) for k, _ in SbhDepthSizes._fields_ if k != "pad"}
+        return self.sizes
+
+    def runs(self, first=0, count=None):
+        """Runs [first, first + count) (all by default) as a DEPTH_RUN_DTYPE array."""
+        if self.sizes is None:  # (the library says SBH_E_STATE)
+            _check(self.ctx.h, lib().sbh_depth_runs_fetch(self.h, 0, 0, None))
+        count = self.sizes["n_runs"] - first if count is None else count
+        out = np.zeros(max(int(count), 0), dtype=DEPTH_RUN_DTYPE)
+        _check(self.ctx.h, lib().sbh_depth_runs_fetch(self.h, int(first), int(count), _ptr(out) if out.size else None))
+        return out
+
+    def depth(self, span=0, start=0, n=None):
+        """Depth (uint32) of positions beg + start .. beg + start + n of span `span` (to its end by
+        default) -- sbh_depth_fetch."""
+        _, b, e = self.spans[span]
+        n = (e - b) - start if n is None else n
+        out = np.zeros(max(int(n), 0), dtype=np.uint32)
+        _check(self.ctx.h, lib().sbh_depth_fetch(self.h, int(span), int(start), int(n), _ptr(out) if out.size else None))
+        return out
+
+    def device_ptr(self, span=0):
+        """Device pointer of the span's uint32 depth after finish (None before)."""
+        return lib().sbh_depth_device_ptr(self.h, int(span))
+
+    def reset(self):
+        """Zero the slots and open the accumulator for adds again (sbh_depth_reset)."""
+        _check(self.ctx.h, lib().sbh_depth_reset(self.h))
+        self.sizes = None
 
 
 class Shard:
