@@ -22,7 +22,7 @@
 #include <map>
 #include <vector>
 
-#include "sbh_internal.h"
+#include "sbh_host.h"
 
 namespace sbh {
 namespace {
@@ -215,26 +215,29 @@ __global__ __launch_bounds__(BAI_T) void k_bai_runs(const uint64_t *ridx, uint64
 
 }  // namespace
 
-hipError_t launch_bai_keys(const uint8_t *U, const uint64_t *pos, uint64_t n, uint64_t total, const int32_t *ctg,
-                           int32_t nctg, DevBlocks bl, uint64_t nblocks, uint64_t file_off, uint64_t *key,
-                           uint64_t *win, uint64_t *vbeg, uint64_t *flg, uint64_t *aux, unsigned long long *err,
-                           hipStream_t st) {
+// key / win / vbeg: n u64 each, flg: n + 1 (the scan's input, head | unmapped << 32), aux: 3 words,
+// err: 3 (preset to ~0).
+static hipError_t launch_bai_keys(const uint8_t *U, const uint64_t *pos, uint64_t n, uint64_t total, const int32_t *ctg,
+                                  int32_t nctg, DevBlocks bl, uint64_t nblocks, uint64_t file_off, uint64_t *key,
+                                  uint64_t *win, uint64_t *vbeg, uint64_t *flg, uint64_t *aux, unsigned long long *err,
+                                  hipStream_t st) {
   if (!n) return hipSuccess;
   hipLaunchKernelGGL(k_bai_keys, dim3((uint32_t)((n + BAI_T - 1) / BAI_T)), dim3(BAI_T), 0, st, U, pos, n, total, ctg,
                      nctg, bl.ustart, bl.cstart, bl.csize, bl.usize, nblocks, file_off, key, win, vbeg, flg, aux, err);
   return hipGetLastError();
 }
 
-hipError_t launch_bai_heads(const uint64_t *key, const uint64_t *win, const uint64_t *vbeg, uint64_t n,
-                            const uint64_t *lin_off, uint64_t *flg, uint64_t *lin, hipStream_t st) {
+static hipError_t launch_bai_heads(const uint64_t *key, const uint64_t *win, const uint64_t *vbeg, uint64_t n,
+                                   const uint64_t *lin_off, uint64_t *flg, uint64_t *lin, hipStream_t st) {
   hipLaunchKernelGGL(k_bai_heads, dim3((uint32_t)((n + 1 + BAI_T - 1) / BAI_T)), dim3(BAI_T), 0, st, key, win, vbeg, n,
                      lin_off, flg, reinterpret_cast<unsigned long long *>(lin));
   return hipGetLastError();
 }
 
-hipError_t launch_bai_runs(const uint64_t *flg, const uint64_t *pre, uint64_t n, uint64_t nruns, const uint64_t *key,
-                           const uint64_t *vbeg, const uint64_t *aux, uint64_t *ridx, sbh_bai_run *runs,
-                           hipStream_t st) {
+// pre: the exclusive scan of flg[0..n]; ridx: nruns words; runs: nruns entries
+static hipError_t launch_bai_runs(const uint64_t *flg, const uint64_t *pre, uint64_t n, uint64_t nruns, const uint64_t *key,
+                                  const uint64_t *vbeg, const uint64_t *aux, uint64_t *ridx, sbh_bai_run *runs,
+                                  hipStream_t st) {
   if (!n || !nruns) return hipSuccess;
   hipLaunchKernelGGL(k_bai_ridx, dim3((uint32_t)((n + BAI_T - 1) / BAI_T)), dim3(BAI_T), 0, st, flg, pre, n, ridx);
   hipLaunchKernelGGL(k_bai_runs, dim3((uint32_t)((nruns + BAI_T - 1) / BAI_T)), dim3(BAI_T), 0, st, ridx, nruns, n, key,
@@ -243,6 +246,141 @@ hipError_t launch_bai_runs(const uint64_t *flg, const uint64_t *pre, uint64_t n,
 }
 
 }  // namespace sbh
+
+using namespace sbh;
+
+extern "C" {
+
+// ---- the C-ABI's scan calls (htslib hts_idx_push over the record chain) ----------------------
+int sbh_bai_scan(sbh_shard *sh, uint64_t first, uint64_t end_flat, sbh_bai_sizes *out) {
+  if (!sh || !out) return SBH_E_ARG;
+  sbh_ctx *ctx = sh->ctx;
+  if (!sh->inflated) return fail(ctx, SBH_E_STATE, "bai scan before inflate");
+  if (sh->nctg < 0) return fail(ctx, SBH_E_STATE, "contig lengths not set");
+  if (first > sh->utotal) return SBH_E_ARG;
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  hipStream_t st = sh->st;
+  auto &B = sh->bai;
+  B.valid = false;
+  const int32_t nref = sh->nctg;
+  if (!B.off_ok) {  // the linear index's layout: reference r owns (l_ref >> 14) + 2 slots
+    std::vector<uint64_t> off((size_t)nref + 1, 0);
+    for (int32_t r = 0; r < nref; ++r) {
+      if (sh->h_ctg[r] < 0) return fail(ctx, SBH_E_ARG, "contig %d has a negative length", r);
+      off[r + 1] = off[r] + ((uint64_t)sh->h_ctg[r] >> 14) + 2;
+    }
+    HIPCHK(ctx, B.lin_off.ensure((uint64_t)nref + 1));
+    HIPCHK(ctx, hipMemcpyAsync(B.lin_off.p, off.data(), 8 * ((uint64_t)nref + 1), hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    B.sz.lin_size = off[nref];
+    B.off_ok = true;
+  }
+  const uint64_t lin_size = B.sz.lin_size;
+  const uint64_t total = seg_end_of(sh, first);
+  const uint64_t E = std::min(std::min(end_flat, sh->utotal), total);
+  uint64_t n = 0;
+  int32_t anomalies = 0;
+  rc = count_records_impl(sh, first, E, &n, &anomalies);
+  if (rc) return rc;
+  if (n >= 0xffffffffull) return fail(ctx, SBH_E_ARG, "bai scan: %llu records in one scan (scan in windows)",
+                                      (unsigned long long)n);
+  HIPCHK(ctx, B.pos.ensure(n));
+  rc = records_positions(sh, first, E, total, n, anomalies, B.pos.p);
+  if (rc) return rc;
+  for (auto *b : {&B.key, &B.win, &B.vbeg}) HIPCHK(ctx, b->ensure(n));
+  HIPCHK(ctx, B.flg.ensure(n + 1));
+  HIPCHK(ctx, B.pre.ensure(n + 1));
+  HIPCHK(ctx, B.lin.ensure(lin_size));
+  HIPCHK(ctx, B.aux.ensure(8));
+  HIPCHK(ctx, sh->tmp.ensure(scan_tmp_words(n + 1)));
+  unsigned long long *err = sh->ctr.p + ctr::BAI_ERR;  // rows: does not fit, unsorted, off its reference
+  constexpr size_t err_bytes = (ctr::BAI_ERR_END - ctr::BAI_ERR) * 8;
+  HIPCHK(ctx, hipMemsetAsync(err, 0xff, err_bytes, st));
+  HIPCHK(ctx, hipMemsetAsync(B.aux.p, 0xff, 24, st));
+  if (lin_size) HIPCHK(ctx, hipMemsetAsync(B.lin.p, 0xff, 8 * lin_size, st));
+  uint64_t nruns = 0, no_coor = 0;
+  B.edges[0] = B.edges[2] = -1;
+  B.edges[1] = B.edges[3] = 0;
+  if (n) {
+    HIPCHK(ctx, launch_bai_keys(sh->U.p, B.pos.p, n, total, sh->ctg.p, nref, sh->dev_blocks(), sh->nblocks,
+                                sh->file_off, B.key.p, B.win.p, B.vbeg.p, B.flg.p, B.aux.p, err, st));
+    HIPCHK(ctx, launch_bai_heads(B.key.p, B.win.p, B.vbeg.p, n, B.lin_off.p, B.flg.p, B.lin.p, st));
+    HIPCHK(ctx, scan_exclusive_u64(B.flg.p, B.pre.p, n + 1, sh->tmp.p, st));
+    HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::BAI_ERR, err, err_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::H_BAI_NRUNS, B.pre.p + n, 8, hipMemcpyDeviceToHost, st));
+    // (aux's three words: the edges are the last two)
+    HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::H_BAI_AUX, B.aux.p, 3 * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    const uint64_t unfit = sh->h_ctr[ctr::BAI_UNFIT], uns = sh->h_ctr[ctr::BAI_UNSORTED],
+                   off_ref = sh->h_ctr[ctr::BAI_OFF_REF];
+    const uint64_t bad = std::min(unfit, off_ref);
+    if (bad != ~0ull || uns != ~0ull) {
+      const uint64_t row = std::min(bad, uns);
+      HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::H_BAI_BAD_VPOS, B.vbeg.p + row, 8, hipMemcpyDeviceToHost, st));
+      HIPCHK(ctx, hipStreamSynchronize(st));
+      const uint64_t v = sh->h_ctr[ctr::H_BAI_BAD_VPOS];
+      if (bad <= uns) {
+        // only a record that does not fit can be cured by more resident bytes
+        if (unfit < off_ref && !sh->at_eof)
+          return fail(ctx, SBH_E_NEED_HALO, "record %llu of the scan may run past the shard", (unsigned long long)row);
+        return fail(ctx, SBH_E_BAD_RECORD, "record %llu of the scan (%llu:%u) is malformed or off its reference",
+                    (unsigned long long)row, (unsigned long long)(v >> 16), (unsigned)(v & 0xffff));
+      }
+      return fail_with(ctx, SBH_E_UNSORTED, {(int64_t)v},
+                       "record %llu of the scan (%llu:%u) is out of coordinate order", (unsigned long long)row, (unsigned long long)(v >> 16), (unsigned)(v & 0xffff));
+    }
+    nruns = sh->h_ctr[ctr::H_BAI_NRUNS] & 0xffffffffull;
+    HIPCHK(ctx, B.ridx.ensure(nruns));
+    HIPCHK(ctx, B.runs.ensure(nruns));
+    HIPCHK(ctx, launch_bai_runs(B.flg.p, B.pre.p, n, nruns, B.key.p, B.vbeg.p, B.aux.p, B.ridx.p, B.runs.p, st));
+    sbh_bai_run last{};
+    HIPCHK(ctx, hipMemcpyAsync(&last, B.runs.p + (nruns - 1), sizeof last, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    if (last.ref_id < 0) {  // the trailing run of records without a reference
+      no_coor = last.n_mapped + last.n_unmapped;
+      --nruns;
+    }
+    B.edges[0] = (int32_t)(sh->h_ctr[ctr::H_BAI_FIRST_EDGE] >> 32);
+    B.edges[1] = (int32_t)(uint32_t)sh->h_ctr[ctr::H_BAI_FIRST_EDGE];
+    if (sh->h_ctr[ctr::H_BAI_LAST_EDGE] != ~0ull) {
+      B.edges[2] = (int32_t)(sh->h_ctr[ctr::H_BAI_LAST_EDGE] >> 32);
+      B.edges[3] = (int32_t)(uint32_t)sh->h_ctr[ctr::H_BAI_LAST_EDGE];
+    }
+  }
+  B.sz = sbh_bai_sizes{n, nruns, no_coor, lin_size};
+  B.valid = true;
+  *out = B.sz;
+  return SBH_OK;
+}
+
+int sbh_bai_fetch(sbh_shard *sh, sbh_bai_run *runs, uint64_t *lin) {
+  if (!sh) return SBH_E_ARG;
+  sbh_ctx *ctx = sh->ctx;
+  auto &B = sh->bai;
+  if (!B.valid) return fail(ctx, SBH_E_STATE, "bai_fetch without a bai_scan");
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  if (runs && B.sz.n_runs)
+    HIPCHK(ctx, hipMemcpyAsync(runs, B.runs.p, B.sz.n_runs * sizeof(sbh_bai_run), hipMemcpyDeviceToHost, sh->st));
+  if (lin && B.sz.lin_size)
+    HIPCHK(ctx, hipMemcpyAsync(lin, B.lin.p, 8 * B.sz.lin_size, hipMemcpyDeviceToHost, sh->st));
+  HIPCHK(ctx, hipStreamSynchronize(sh->st));
+  return SBH_OK;
+}
+
+int sbh_bai_edges(sbh_shard *sh, int32_t *first_ref, int32_t *first_pos, int32_t *last_ref, int32_t *last_pos) {
+  if (!sh) return SBH_E_ARG;
+  if (!sh->bai.valid) return fail(sh->ctx, SBH_E_STATE, "bai_edges without a bai_scan");
+  const int32_t *e = sh->bai.edges;
+  if (first_ref) *first_ref = e[0];
+  if (first_pos) *first_pos = e[1];
+  if (last_ref) *last_ref = e[2];
+  if (last_pos) *last_pos = e[3];
+  return SBH_OK;
+}
+
+}  // extern "C"
 
 // ---- host-only finisher (no context, no device) ---------------------------------------------
 namespace {

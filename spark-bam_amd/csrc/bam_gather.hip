@@ -8,10 +8,12 @@
 //   k_bam_index  rec_off / rows per kept row, (dst, src) per run, the closing entries
 //   k_bam_copy   one 16-byte-aligned granule of the OUTPUT per lane
 #include <algorithm>
+#include <cstring>
 
 #define SBH_HD __host__ __device__
 #include "bam_gather_core.h"
-#include "sbh_internal.h"
+#include "bam_sort_core.h"
+#include "sbh_host.h"
 
 namespace sbh {
 namespace {
@@ -135,11 +137,12 @@ uint32_t rows_grid(uint64_t n) { return (uint32_t)std::min<uint64_t>((n + 255) /
 
 }  // namespace
 
-// len, kh: n + 1 words (the caller zeroes entry n); bad, past preset to ~0
-hipError_t launch_bam_keep(const uint8_t *U, const uint64_t *pos, uint64_t n, uint64_t total, uint32_t flag_require,
-                           uint32_t flag_exclude, int32_t min_mapq, const uint64_t *row_begin, const uint64_t *row_end,
-                           uint64_t n_row_ranges, uint64_t *len, uint64_t *kh, unsigned long long *bad,
-                           unsigned long long *past, hipStream_t st) {
+// len, kh: n + 1 words (the caller zeroes entry n); bad, past preset to ~0: the first invalid row, the
+// first row invalid only because the stream ends too early
+static hipError_t launch_bam_keep(const uint8_t *U, const uint64_t *pos, uint64_t n, uint64_t total, uint32_t flag_require,
+                                  uint32_t flag_exclude, int32_t min_mapq, const uint64_t *row_begin, const uint64_t *row_end,
+                                  uint64_t n_row_ranges, uint64_t *len, uint64_t *kh, unsigned long long *bad,
+                                  unsigned long long *past, hipStream_t st) {
   if (!n) return hipSuccess;
   const sbh_bam::Filter F{flag_require, flag_exclude, min_mapq, row_begin, row_end, n_row_ranges};
   hipLaunchKernelGGL(k_bam_keep, dim3(rows_grid(n)), dim3(256), 0, st, U, pos, n, total, F, len, kh, bad, past);
@@ -148,23 +151,25 @@ hipError_t launch_bam_keep(const uint8_t *U, const uint64_t *pos, uint64_t n, ui
 }
 
 // k_bam_heads alone, over rows whose len and keep flags (kh) are already there (the sorted rows)
-hipError_t launch_bam_heads(const uint64_t *pos, const uint64_t *len, uint64_t n, uint64_t *kh, hipStream_t st) {
+static hipError_t launch_bam_heads(const uint64_t *pos, const uint64_t *len, uint64_t n, uint64_t *kh, hipStream_t st) {
   if (!n) return hipSuccess;
   hipLaunchKernelGGL(k_bam_heads, dim3(rows_grid(n)), dim3(256), 0, st, pos, len, n, kh);
   return hipGetLastError();
 }
 
-// off, khpre: the exclusive scans of len and kh over n + 1 entries
-hipError_t launch_bam_index(const uint64_t *pos, const uint64_t *off, const uint64_t *kh, const uint64_t *khpre,
-                            uint64_t n, uint64_t head_bytes, uint64_t *rec_off, uint64_t *rows, uint64_t *run_dst,
-                            uint64_t *run_src, hipStream_t st) {
+// off, khpre: the exclusive scans of len and kh over n + 1 entries (kh = keep | run head << 32, so
+// n < 2^32); rec_off, rows, run_dst, run_src: n + 1 words
+static hipError_t launch_bam_index(const uint64_t *pos, const uint64_t *off, const uint64_t *kh, const uint64_t *khpre,
+                                   uint64_t n, uint64_t head_bytes, uint64_t *rec_off, uint64_t *rows, uint64_t *run_dst,
+                                   uint64_t *run_src, hipStream_t st) {
   hipLaunchKernelGGL(k_bam_index, dim3(rows_grid(n + 1)), dim3(256), 0, st, pos, off, kh, khpre, n, head_bytes, rec_off,
                      rows, run_dst, run_src);
   return hipGetLastError();
 }
 
-hipError_t launch_bam_copy(const uint8_t *U, const uint64_t *run_dst, const uint64_t *run_src, uint64_t n_runs,
-                           uint64_t head_bytes, uint64_t bytes, uint8_t *out, hipStream_t st) {
+// out[head_bytes, bytes) from the runs; reads U below (the last run's end) + 32
+static hipError_t launch_bam_copy(const uint8_t *U, const uint64_t *run_dst, const uint64_t *run_src, uint64_t n_runs,
+                                  uint64_t head_bytes, uint64_t bytes, uint8_t *out, hipStream_t st) {
   if (!n_runs || bytes <= head_bytes) return hipSuccess;
   const uint64_t tiles = ((bytes + 15) / 16 - head_bytes / 16 + COPY_T - 1) / COPY_T;
   hipLaunchKernelGGL(k_bam_copy, dim3((uint32_t)std::min<uint64_t>(tiles, COPY_GRID)), dim3(COPY_T), 0, st, U, run_dst,
@@ -172,4 +177,206 @@ hipError_t launch_bam_copy(const uint8_t *U, const uint64_t *run_dst, const uint
   return hipGetLastError();
 }
 
+bool bam_filter_of(const sbh_record_filter *f, sbh_bam::Filter *F) {
+  *F = sbh_bam::Filter{0, 0, 0, nullptr, nullptr, 0};
+  if (f) *F = sbh_bam::Filter{f->flag_require, f->flag_exclude, f->min_mapq, f->row_begin, f->row_end, f->n_row_ranges};
+  return sbh_bam::filter_ok(*F);
+}
+
 }  // namespace sbh
+
+using namespace sbh;
+
+extern "C" {
+
+// ---- the C-ABI's BAM stream calls (validity and predicate in bam_gather_core.h) ---------------
+// Keep pass, two scans, index pass -- all launched before anything is read back, so one round trip
+// brings (first invalid row, first row past the end, kept bytes, kept rows | runs << 32); then the
+// stream is allocated, the head copied in and the runs copied behind it.
+int sbh_records_bam_scan(sbh_shard *sh, const uint8_t *head, uint64_t head_bytes, const sbh_record_filter *filter,
+                         sbh_bam_sizes *out) {
+  return sbh_records_bam_scan_order(sh, head, head_bytes, filter, SBH_ORDER_SCAN, out);
+}
+
+// SBH_ORDER_COORDINATE: the scan-order pipeline runs as it is up to k_bam_index, whose rows[] are the
+// kept rows; k_sort_keys follows it, and the one round trip brings its three counters as well.  No
+// descent: the scan order is the coordinate order and the call goes on exactly as in scan order.
+// Otherwise the passes whose digit differs somewhere (OR & ~AND) run, k_sort_apply lays out the
+// permuted starts and lengths, and k_bam_heads, the scans and k_bam_index run over those -- every
+// entry kept -- before a second round trip for the run count.
+int sbh_records_bam_scan_order(sbh_shard *sh, const uint8_t *head, uint64_t head_bytes, const sbh_record_filter *filter,
+                               int order, sbh_bam_sizes *out) {
+  if (!sh || !out || (head_bytes && !head)) return SBH_E_ARG;
+  sbh_ctx *ctx = sh->ctx;
+  auto &R = sh->rec;
+  auto &B = sh->bam;
+  if (order != SBH_ORDER_SCAN && order != SBH_ORDER_COORDINATE)
+    return fail(ctx, SBH_E_ARG, "records_bam_scan: order %d is neither SBH_ORDER_SCAN nor SBH_ORDER_COORDINATE", order);
+  const bool sorted = order == SBH_ORDER_COORDINATE;
+  if (!R.valid) return fail(ctx, SBH_E_STATE, "records_bam_scan without a records scan");
+  sbh_bam::Filter F;
+  if (!bam_filter_of(filter, &F))
+    return fail(ctx, SBH_E_ARG, "record filter: flags < 65536, 0 <= min_mapq <= 255, row ranges sorted, disjoint and non-empty");
+  const uint64_t n = R.sz.n, nr = F.n_row_ranges;
+  if (n >= 0xffffffffull)
+    return fail(ctx, SBH_E_ARG, "records_bam_scan: %llu rows in one scan (scan in windows)", (unsigned long long)n);
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  hipStream_t st = sh->st;
+  B.valid = false;
+  uint64_t bytes = head_bytes, n_kept = 0, n_runs = 0;
+  for (auto *b : {&B.len, &B.off, &B.kh, &B.khpre, &B.rec_off, &B.rows, &B.run_dst, &B.run_src}) HIPCHK(ctx, b->ensure(n + 1));
+  const uint64_t hist_words = 256 * sort_tiles(n) + 1;
+  if (sorted && n) {  // (sized for n: the kept count is not known here)
+    for (auto *b : {&B.skey[0], &B.skey[1]}) HIPCHK(ctx, b->ensure(n));
+    for (auto *b : {&B.srow[0], &B.srow[1]}) HIPCHK(ctx, b->ensure(n));
+    for (auto *b : {&B.pos2, &B.len2}) HIPCHK(ctx, b->ensure(n + 1));
+    HIPCHK(ctx, B.hist.ensure(2 * hist_words));
+    HIPCHK(ctx, sh->tmp.ensure(scan_tmp_words(hist_words)));
+  }
+  bool already = true;
+  if (n) {
+    HIPCHK(ctx, B.ranges.ensure(2 * nr));
+    if (nr) {
+      HIPCHK(ctx, hipMemcpyAsync(B.ranges.p, F.row_begin, 8 * nr, hipMemcpyHostToDevice, st));
+      HIPCHK(ctx, hipMemcpyAsync(B.ranges.p + nr, F.row_end, 8 * nr, hipMemcpyHostToDevice, st));
+    }
+    HIPCHK(ctx, sh->tmp.ensure(scan_tmp_words(n + 1)));
+    HIPCHK(ctx, hipMemsetAsync(B.len.p + n, 0, 8, st));
+    HIPCHK(ctx, hipMemsetAsync(B.kh.p + n, 0, 8, st));
+    unsigned long long *bad = sh->ctr.p + ctr::BAM_BAD;  // (BAM_PAST is the next word)
+    static_assert(ctr::BAM_PAST == ctr::BAM_BAD + 1, "one memset, one copy");
+    HIPCHK(ctx, hipMemsetAsync(bad, 0xff, 16, st));
+    HIPCHK(ctx, launch_bam_keep(sh->U.p, R.pos.p, n, sh->utotal, F.flag_require, F.flag_exclude, F.min_mapq, B.ranges.p,
+                                B.ranges.p + nr, nr, B.len.p, B.kh.p, bad, bad + 1, st));
+    HIPCHK(ctx, scan_exclusive_u64(B.len.p, B.off.p, n + 1, sh->tmp.p, st));
+    HIPCHK(ctx, scan_exclusive_u64(B.kh.p, B.khpre.p, n + 1, sh->tmp.p, st));
+    HIPCHK(ctx, launch_bam_index(R.pos.p, B.off.p, B.kh.p, B.khpre.p, n, head_bytes, B.rec_off.p, B.rows.p, B.run_dst.p,
+                                 B.run_src.p, st));
+    unsigned long long *acc = sh->ctr.p + ctr::SORT_DESC;
+    static_assert(ctr::SORT_OR == ctr::SORT_DESC + 1 && ctr::SORT_AND == ctr::SORT_DESC + 2, "one copy");
+    if (sorted) {
+      HIPCHK(ctx, hipMemsetAsync(acc, 0, 16, st));
+      HIPCHK(ctx, hipMemsetAsync(acc + 2, 0xff, 8, st));
+      HIPCHK(ctx, launch_sort_keys(sh->U.p, R.pos.p, B.rows.p, B.khpre.p + n, n, B.skey[0].p, B.srow[0].p, acc, st));
+      HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::SORT_DESC, acc, 24, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::BAM_BAD, bad, 16, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::H_BAM_BYTES, B.off.p + n, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::H_BAM_KH, B.khpre.p + n, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    const uint64_t row = sh->h_ctr[ctr::BAM_BAD];
+    if (row != ~0ull) {
+      // only a record that runs past the resident bytes can be cured by more of them
+      if (sh->h_ctr[ctr::BAM_PAST] == row && !sh->at_eof)
+        return fail(ctx, SBH_E_NEED_HALO, "record %llu of the scan may run past the shard", (unsigned long long)row);
+      return fail_with(ctx, SBH_E_BAD_RECORD, {(int64_t)row}, "record %llu of the scan does not fit its block or the stream",
+                       (unsigned long long)row);
+    }
+    bytes += sh->h_ctr[ctr::H_BAM_BYTES];
+    n_kept = sh->h_ctr[ctr::H_BAM_KH] & 0xffffffffull;
+    n_runs = sh->h_ctr[ctr::H_BAM_KH] >> 32;
+    if (sorted && sh->h_ctr[ctr::SORT_DESC]) {
+      already = false;
+      const uint64_t m = n_kept, differ = sh->h_ctr[ctr::SORT_OR] & ~sh->h_ctr[ctr::SORT_AND];
+      int cur = 0;
+      for (uint32_t shift = 0; shift < 64; shift += 8) {
+        if (!((differ >> shift) & 0xff)) continue;  // the same digit in every key: the pass would move nothing
+        HIPCHK(ctx, launch_sort_pass(B.skey[cur].p, B.srow[cur].p, m, shift, B.hist.p, sh->tmp.p, B.skey[cur ^ 1].p,
+                                     B.srow[cur ^ 1].p, st));
+        cur ^= 1;
+      }
+      HIPCHK(ctx, launch_sort_apply(R.pos.p, B.len.p, B.srow[cur].p, m, B.pos2.p, B.len2.p, B.kh.p, st));
+      HIPCHK(ctx, launch_bam_heads(B.pos2.p, B.len2.p, m, B.kh.p, st));
+      HIPCHK(ctx, scan_exclusive_u64(B.len2.p, B.off.p, m + 1, sh->tmp.p, st));
+      HIPCHK(ctx, scan_exclusive_u64(B.kh.p, B.khpre.p, m + 1, sh->tmp.p, st));
+      HIPCHK(ctx, launch_bam_index(B.pos2.p, B.off.p, B.kh.p, B.khpre.p, m, head_bytes, B.rec_off.p, B.rows.p,
+                                   B.run_dst.p, B.run_src.p, st));
+      HIPCHK(ctx, launch_sort_rows(B.srow[cur].p, m, B.rows.p, st));
+      HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::H_BAM_KH, B.khpre.p + m, 8, hipMemcpyDeviceToHost, st));
+      HIPCHK(ctx, hipStreamSynchronize(st));
+      n_runs = sh->h_ctr[ctr::H_BAM_KH] >> 32;
+    }
+  } else {
+    HIPCHK(ctx, hipMemcpyAsync(B.rec_off.p, &head_bytes, 8, hipMemcpyHostToDevice, st));
+  }
+  HIPCHK(ctx, B.out.ensure(bytes + 16));
+  if (head_bytes) HIPCHK(ctx, hipMemcpyAsync(B.out.p, head, head_bytes, hipMemcpyHostToDevice, st));
+  HIPCHK(ctx, launch_bam_copy(sh->U.p, B.run_dst.p, B.run_src.p, n_runs, head_bytes, bytes, B.out.p, st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
+  B.sz = sbh_bam_sizes{n, n_kept, bytes};
+  B.head_bytes = head_bytes;
+  B.order = order;
+  B.already = already;
+  B.valid = true;
+  *out = B.sz;
+  return SBH_OK;
+}
+
+int sbh_records_bam_sorted(sbh_shard *sh, int *already) {
+  if (!sh || !already) return SBH_E_ARG;
+  const auto &B = sh->bam;
+  if (!B.valid || B.order != SBH_ORDER_COORDINATE)
+    return fail(sh->ctx, SBH_E_STATE, "records_bam_sorted without a coordinate-order records_bam_scan");
+  *already = B.already ? 1 : 0;
+  return SBH_OK;
+}
+
+const void *sbh_records_bam_device_ptr(sbh_shard *sh) { return sh && sh->bam.valid ? sh->bam.out.p : nullptr; }
+
+int sbh_records_bam_fetch(sbh_shard *sh, uint8_t *stream, uint64_t *rec_off, uint64_t *rows) {
+  if (!sh) return SBH_E_ARG;
+  sbh_ctx *ctx = sh->ctx;
+  auto &B = sh->bam;
+  if (!B.valid) return fail(ctx, SBH_E_STATE, "records_bam_fetch without a records_bam_scan");
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  hipStream_t st = sh->st;
+  if (stream && B.sz.bytes) HIPCHK(ctx, hipMemcpyAsync(stream, B.out.p, B.sz.bytes, hipMemcpyDeviceToHost, st));
+  if (rec_off) HIPCHK(ctx, hipMemcpyAsync(rec_off, B.rec_off.p, 8 * (B.sz.n_kept + 1), hipMemcpyDeviceToHost, st));
+  if (rows && B.sz.n_kept) HIPCHK(ctx, hipMemcpyAsync(rows, B.rows.p, 8 * B.sz.n_kept, hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
+  return SBH_OK;
+}
+
+int sbh_records_bam_read(sbh_shard *sh, uint64_t offset, uint64_t n, uint8_t *out) {
+  if (!sh || (n && !out)) return SBH_E_ARG;
+  sbh_ctx *ctx = sh->ctx;
+  auto &B = sh->bam;
+  if (!B.valid) return fail(ctx, SBH_E_STATE, "records_bam_read without a records_bam_scan");
+  if (offset > B.sz.bytes || n > B.sz.bytes - offset) return fail(ctx, SBH_E_ARG, "records_bam_read past the stream");
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  if (n) HIPCHK(ctx, hipMemcpyAsync(out, B.out.p + offset, n, hipMemcpyDeviceToHost, sh->st));
+  HIPCHK(ctx, hipStreamSynchronize(sh->st));
+  return SBH_OK;
+}
+
+int sbh_bam_gather_host(const uint8_t *flat, uint64_t flat_size, const uint64_t *starts, uint64_t n, const uint8_t *head,
+                        uint64_t head_bytes, const sbh_record_filter *filter, uint8_t *out, uint64_t out_cap,
+                        uint64_t *rec_off, uint64_t *rows, uint64_t *n_kept, uint64_t *bad_row) {
+  if ((!flat && flat_size) || (!starts && n) || (!head && head_bytes) || !n_kept) return SBH_E_ARG;
+  sbh_bam::Filter F;
+  if (!bam_filter_of(filter, &F)) return SBH_E_ARG;
+  uint64_t bad = sbh_bam::NO_ROW, bytes = 0;
+  const int rc = sbh_bam::gather_host(flat, flat_size, starts, n, head, head_bytes, F, out, out_cap, rec_off, rows, n_kept,
+                                      &bytes, &bad);
+  if (bad_row) *bad_row = bad;
+  return rc == 0 ? SBH_OK : rc == 1 ? SBH_E_BAD_RECORD : SBH_E_ARG;
+}
+
+int sbh_bam_sort_host(const uint8_t *flat, uint64_t flat_size, const uint64_t *starts, uint64_t n, uint64_t *perm,
+                      uint64_t *bad_row) {
+  if ((!flat && flat_size) || (!starts && n) || (!perm && n)) return SBH_E_ARG;
+  uint64_t bad = sbh_bam::NO_ROW;
+  const int rc = sbh_bam::sort_host(flat, flat_size, starts, n, perm, &bad);
+  if (bad_row) *bad_row = bad;
+  return rc == 0 ? SBH_OK : SBH_E_BAD_RECORD;
+}
+
+int sbh_bam_header_set_so(const uint8_t *head, uint64_t n, const char *so, uint8_t *out, uint64_t cap, uint64_t *out_n) {
+  if (!head || !so || !out_n) return SBH_E_ARG;
+  return sbh_bam::header_set_so(head, n, so, out, cap, out_n) == 0 ? SBH_OK : SBH_E_ARG;
+}
+
+}  // extern "C"

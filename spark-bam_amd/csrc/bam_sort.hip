@@ -27,8 +27,6 @@
 #include "sbh_internal.h"
 
 namespace sbh {
-hipError_t scan_exclusive_u64(const uint64_t *in, uint64_t *out, uint64_t n, uint64_t *tmp, hipStream_t st);  // bgzf_index.hip
-
 namespace {
 
 using sbh_bam::SORT_ITEMS;

@@ -29,10 +29,11 @@
 // (wave, round, lane, e) ascends with s, so prefix sums nest: e within the lane, lanes by a DPP wave
 // scan, rounds by the wave's running total, waves through LDS.
 #include <algorithm>
+#include <vector>
 
 #define SBH_HD __host__ __device__
 #include "depth_core.h"
-#include "sbh_internal.h"
+#include "sbh_host.h"
 
 namespace sbh {
 namespace {
@@ -442,13 +443,17 @@ uint32_t rows_grid(uint64_t n) { return (uint32_t)std::min<uint64_t>((n + 255) /
 
 }  // namespace
 
-uint64_t depth_tiles(uint64_t S) { return (S + DEPTH_TILE - 1) / DEPTH_TILE; }
+// The launchers, in the order the entry points below use them.  launch_depth_events: off has
+// n_spans + 1 entries, off[n_spans] == S.  The finish: tile sums (depth_tiles(S) words), their
+// exclusive scan as base, launch_depth_apply (heads: depth_tiles(S) + 1 words, the caller zeroes
+// the last), the scan of heads as hbase, launch_depth_runs.
+static uint64_t depth_tiles(uint64_t S) { return (S + DEPTH_TILE - 1) / DEPTH_TILE; }
 
 // keep: ceil(n / 64) words; acc: ctr::DEPTH_BAD .. DEPTH_UNPLACED (preset ~0, ~0, 0, 0)
-hipError_t launch_depth_check(const uint8_t *U, const uint64_t *pos, uint64_t n, uint64_t total, uint32_t flag_require,
-                              uint32_t flag_exclude, int32_t min_mapq, const uint64_t *row_begin, const uint64_t *row_end,
-                              uint64_t n_row_ranges, int32_t n_ref, uint64_t *keep, unsigned long long *acc,
-                              hipStream_t st) {
+static hipError_t launch_depth_check(const uint8_t *U, const uint64_t *pos, uint64_t n, uint64_t total, uint32_t flag_require,
+                                     uint32_t flag_exclude, int32_t min_mapq, const uint64_t *row_begin, const uint64_t *row_end,
+                                     uint64_t n_row_ranges, int32_t n_ref, uint64_t *keep, unsigned long long *acc,
+                                     hipStream_t st) {
   if (!n) return hipSuccess;
   const sbh_bam::Filter F{flag_require, flag_exclude, min_mapq, row_begin, row_end, n_row_ranges};
   hipLaunchKernelGGL(k_depth_check, dim3(rows_grid(n)), dim3(256), 0, st, U, pos, n, total, F, n_ref, keep, acc);
@@ -456,9 +461,9 @@ hipError_t launch_depth_check(const uint8_t *U, const uint64_t *pos, uint64_t n,
 }
 
 // acc: ctr::DEPTH_COUNTED, DEPTH_COV (preset 0)
-hipError_t launch_depth_events(const uint8_t *U, const uint64_t *pos, uint64_t n, const uint64_t *keep,
-                               const sbh_depth_span *spans, const uint64_t *off, uint32_t n_spans, uint32_t flags,
-                               int32_t *slots, uint64_t S, unsigned long long *acc, hipStream_t st) {
+static hipError_t launch_depth_events(const uint8_t *U, const uint64_t *pos, uint64_t n, const uint64_t *keep,
+                                      const sbh_depth_span *spans, const uint64_t *off, uint32_t n_spans, uint32_t flags,
+                                      int32_t *slots, uint64_t S, unsigned long long *acc, hipStream_t st) {
   if (!n) return hipSuccess;
   static_assert(sizeof(sbh_depth_span) == sizeof(Span), "one layout");
   hipLaunchKernelGGL(k_depth_events, dim3(rows_grid(n)), dim3(256), 0, st, U, pos, n, keep,
@@ -466,14 +471,14 @@ hipError_t launch_depth_events(const uint8_t *U, const uint64_t *pos, uint64_t n
   return hipGetLastError();
 }
 
-hipError_t launch_depth_tile_sums(const int32_t *slots, uint64_t S, uint64_t *sums, hipStream_t st) {
+static hipError_t launch_depth_tile_sums(const int32_t *slots, uint64_t S, uint64_t *sums, hipStream_t st) {
   hipLaunchKernelGGL(k_depth_tile_sums, dim3((uint32_t)depth_tiles(S)), dim3(TILE_T), 0, st, slots, S, sums);
   return hipGetLastError();
 }
 
 // tstat: 3 depth_tiles(S) words, every one written; acc: max, covered, sum (preset 0)
-hipError_t launch_depth_apply(int32_t *slots, uint64_t S, const uint64_t *base, const uint64_t *off, uint32_t n_spans,
-                              uint64_t *heads, uint64_t *tstat, unsigned long long *acc, hipStream_t st) {
+static hipError_t launch_depth_apply(int32_t *slots, uint64_t S, const uint64_t *base, const uint64_t *off, uint32_t n_spans,
+                                     uint64_t *heads, uint64_t *tstat, unsigned long long *acc, hipStream_t st) {
   const uint64_t nt = depth_tiles(S);
   hipLaunchKernelGGL(k_depth_apply, dim3((uint32_t)nt), dim3(TILE_T), 0, st, slots, S, base, off, n_spans, heads, tstat);
   hipLaunchKernelGGL(k_depth_stats, dim3((uint32_t)std::min<uint64_t>((nt + 255) / 256, 64)), dim3(256), 0, st, tstat, nt,
@@ -481,12 +486,241 @@ hipError_t launch_depth_apply(int32_t *slots, uint64_t S, const uint64_t *base, 
   return hipGetLastError();
 }
 
-hipError_t launch_depth_runs(const int32_t *depth, uint64_t S, const uint64_t *hbase, const sbh_depth_span *spans,
-                             const uint64_t *off, uint32_t n_spans, uint64_t n_runs, sbh_depth_run *runs,
-                             hipStream_t st) {
+static hipError_t launch_depth_runs(const int32_t *depth, uint64_t S, const uint64_t *hbase, const sbh_depth_span *spans,
+                                    const uint64_t *off, uint32_t n_spans, uint64_t n_runs, sbh_depth_run *runs,
+                                    hipStream_t st) {
   hipLaunchKernelGGL(k_depth_runs, dim3((uint32_t)depth_tiles(S)), dim3(TILE_T), 0, st, depth, S, hbase,
                      reinterpret_cast<const Span *>(spans), off, n_spans, n_runs, runs);
   return hipGetLastError();
 }
 
 }  // namespace sbh
+
+using namespace sbh;
+
+extern "C" {
+
+// ---- the C-ABI's per-base depth calls (the definition in depth_core.h) ------------------------
+static const sbh_dep::Span *depth_spans(const sbh_depth_span *s) {
+  static_assert(sizeof(sbh_depth_span) == sizeof(sbh_dep::Span) && sizeof(sbh_depth_run) == sizeof(sbh_dep::Run) &&
+                    sizeof(sbh_depth_sizes) == sizeof(sbh_dep::Sizes) &&
+                    sizeof(sbh_depth_add_result) == sizeof(sbh_dep::AddResult),
+                "depth_core.h restates the header's layouts");
+  return reinterpret_cast<const sbh_dep::Span *>(s);
+}
+
+int sbh_depth_create(sbh_ctx *ctx, const sbh_depth_span *spans, uint32_t n_spans, int32_t n_ref, uint32_t flags,
+                     sbh_depth **out) {
+  if (!ctx || !out) return SBH_E_ARG;
+  *out = nullptr;
+  if (flags & ~SBH_DEPTH_DEL) return fail(ctx, SBH_E_ARG, "depth: unknown flag bits 0x%x", flags & ~SBH_DEPTH_DEL);
+  if (!sbh_dep::spans_ok(depth_spans(spans), n_spans, n_ref))
+    return fail(ctx, SBH_E_ARG,
+                "depth spans: at least one, ref_id in [0, n_ref) strictly ascending, 0 <= beg < end <= 2^31 - 1");
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  sbh_depth *d = new sbh_depth();
+  d->ctx = ctx;
+  d->n_ref = n_ref;
+  d->flags = flags;
+  d->spans.assign(spans, spans + n_spans);
+  d->off.assign(n_spans + 1, 0);
+  for (uint32_t k = 0; k < n_spans; ++k) d->off[k + 1] = d->off[k] + (uint64_t)(spans[k].end - spans[k].beg) + 1;
+  d->S = d->off[n_spans];
+  const uint64_t nt = depth_tiles(d->S);
+  hipError_t e = nt < 0x7fffffffull ? hipSuccess : hipErrorOutOfMemory;  // (one workgroup per tile)
+  if (e == hipSuccess) e = hipStreamCreateWithFlags(&d->st, hipStreamNonBlocking);
+  const bool have_stream = e == hipSuccess;
+  if (e == hipSuccess) e = d->slots.ensure(d->S);
+  if (e == hipSuccess) e = d->d_spans.ensure(n_spans);
+  if (e == hipSuccess) e = d->d_off.ensure(n_spans + 1);
+  for (auto *b : {&d->tsum, &d->tbase, &d->heads, &d->hbase})
+    if (e == hipSuccess) e = b->ensure(nt + 1);
+  if (e == hipSuccess) e = d->tstat.ensure(3 * nt);
+  if (e == hipSuccess) e = d->tmp.ensure(scan_tmp_words(nt + 1));
+  if (e == hipSuccess) e = d->acc.ensure(3);
+  if (e == hipSuccess) e = hipMemcpyAsync(d->d_spans.p, spans, n_spans * sizeof(sbh_depth_span), hipMemcpyHostToDevice, d->st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d->d_off.p, d->off.data(), 8 * (n_spans + 1), hipMemcpyHostToDevice, d->st);
+  if (e == hipSuccess) e = hipMemsetAsync(d->slots.p, 0, 4 * d->S, d->st);
+  if (e == hipSuccess) e = hipStreamSynchronize(d->st);  // (the copies' sources are the caller's and this frame's)
+  if (e != hipSuccess) {
+    const uint64_t S = d->S;
+    delete d;
+    if (e == hipErrorOutOfMemory || !have_stream) {
+      (void)hipGetLastError();
+      return fail(ctx, SBH_E_NOMEM, "depth: no memory for %llu slots (4 bytes each)", (unsigned long long)S);
+    }
+    return fail(ctx, SBH_E_HIP, "depth create: %s", hipGetErrorString(e));
+  }
+  *out = d;
+  return SBH_OK;
+}
+
+int sbh_depth_destroy(sbh_depth *d) {
+  delete d;  // (~sbh_depth; a null accumulator is fine)
+  return SBH_OK;
+}
+
+int sbh_depth_reset(sbh_depth *d) {
+  if (!d) return SBH_E_ARG;
+  sbh_ctx *ctx = d->ctx;
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  HIPCHK(ctx, hipMemsetAsync(d->slots.p, 0, 4 * d->S, d->st));
+  HIPCHK(ctx, hipStreamSynchronize(d->st));
+  d->finished = false;
+  d->sz = sbh_depth_sizes{};
+  return SBH_OK;
+}
+
+// k_depth_check, one round trip (bad row, past row, kept, unplaced), then k_depth_events only when
+// no row is bad: a failed add has written nothing into the slots.
+int sbh_records_depth_add(sbh_shard *sh, sbh_depth *d, const sbh_record_filter *filter, sbh_depth_add_result *out) {
+  if (!sh || !d || !out) return SBH_E_ARG;
+  sbh_ctx *ctx = sh->ctx;
+  if (d->ctx != ctx) return fail(ctx, SBH_E_ARG, "records_depth_add: the shard and the accumulator belong to different contexts");
+  auto &R = sh->rec;
+  if (!R.valid) return fail(ctx, SBH_E_STATE, "records_depth_add without a records scan");
+  if (d->finished) return fail(ctx, SBH_E_STATE, "records_depth_add after sbh_depth_finish (sbh_depth_reset reopens)");
+  sbh_bam::Filter F;
+  if (!bam_filter_of(filter, &F))
+    return fail(ctx, SBH_E_ARG, "record filter: flags < 65536, 0 <= min_mapq <= 255, row ranges sorted, disjoint and non-empty");
+  const uint64_t n = R.sz.n, nr = F.n_row_ranges;
+  *out = sbh_depth_add_result{n, 0, 0, 0, 0};
+  if (!n) return SBH_OK;
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  hipStream_t st = sh->st;
+  auto &D = sh->dep;
+  HIPCHK(ctx, D.keep.ensure((n + 63) / 64));
+  HIPCHK(ctx, D.ranges.ensure(2 * nr));
+  if (nr) {
+    HIPCHK(ctx, hipMemcpyAsync(D.ranges.p, F.row_begin, 8 * nr, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(D.ranges.p + nr, F.row_end, 8 * nr, hipMemcpyHostToDevice, st));
+  }
+  unsigned long long *acc = sh->ctr.p + ctr::DEPTH_BAD;
+  static_assert(ctr::DEPTH_PAST == ctr::DEPTH_BAD + 1 && ctr::DEPTH_KEPT == ctr::DEPTH_BAD + 2 &&
+                    ctr::DEPTH_UNPLACED == ctr::DEPTH_BAD + 3 && ctr::DEPTH_COUNTED == ctr::DEPTH_BAD + 4 &&
+                    ctr::DEPTH_COV == ctr::DEPTH_BAD + 5,
+                "two memsets, one copy each way");
+  HIPCHK(ctx, hipMemsetAsync(acc, 0xff, 16, st));
+  HIPCHK(ctx, hipMemsetAsync(acc + 2, 0, 32, st));
+  HIPCHK(ctx, launch_depth_check(sh->U.p, R.pos.p, n, sh->utotal, F.flag_require, F.flag_exclude, F.min_mapq, D.ranges.p,
+                                 D.ranges.p + nr, nr, d->n_ref, D.keep.p, acc, st));
+  HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::DEPTH_BAD, acc, 32, hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
+  const uint64_t row = sh->h_ctr[ctr::DEPTH_BAD];
+  if (row != ~0ull) {
+    // only a record that runs past the resident bytes can be cured by more of them
+    if (sh->h_ctr[ctr::DEPTH_PAST] == row && !sh->at_eof)
+      return fail(ctx, SBH_E_NEED_HALO, "record %llu of the scan may run past the shard", (unsigned long long)row);
+    return fail_with(ctx, SBH_E_BAD_RECORD, {(int64_t)row},
+                     "record %llu of the scan does not fit its block or the stream, or its CIGAR or reference is out of range",
+                     (unsigned long long)row);
+  }
+  out->n_kept = sh->h_ctr[ctr::DEPTH_KEPT];
+  out->n_unplaced = sh->h_ctr[ctr::DEPTH_UNPLACED];
+  if (out->n_kept > out->n_unplaced) {
+    HIPCHK(ctx, launch_depth_events(sh->U.p, R.pos.p, n, D.keep.p, d->d_spans.p, d->d_off.p, (uint32_t)d->spans.size(),
+                                    d->flags, d->slots.p, d->S, acc + 4, st));
+    HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::DEPTH_COUNTED, acc + 4, 16, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    out->n_counted = sh->h_ctr[ctr::DEPTH_COUNTED];
+    out->cov_bases = sh->h_ctr[ctr::DEPTH_COV];
+  }
+  return SBH_OK;
+}
+
+int sbh_depth_finish(sbh_depth *d, sbh_depth_sizes *out) {
+  if (!d || !out) return SBH_E_ARG;
+  sbh_ctx *ctx = d->ctx;
+  if (d->finished) return fail(ctx, SBH_E_STATE, "sbh_depth_finish twice (sbh_depth_reset reopens)");
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  hipStream_t st = d->st;
+  const uint64_t S = d->S, nt = depth_tiles(S);
+  const uint32_t ns = (uint32_t)d->spans.size();
+  unsigned long long h[4] = {0, 0, 0, 0};
+  HIPCHK(ctx, hipMemsetAsync(d->acc.p, 0, 24, st));
+  HIPCHK(ctx, hipMemsetAsync(d->heads.p + nt, 0, 8, st));
+  HIPCHK(ctx, launch_depth_tile_sums(d->slots.p, S, d->tsum.p, st));
+  HIPCHK(ctx, scan_exclusive_u64(d->tsum.p, d->tbase.p, nt, d->tmp.p, st));
+  HIPCHK(ctx, launch_depth_apply(d->slots.p, S, d->tbase.p, d->d_off.p, ns, d->heads.p, d->tstat.p, d->acc.p, st));
+  HIPCHK(ctx, scan_exclusive_u64(d->heads.p, d->hbase.p, nt + 1, d->tmp.p, st));
+  HIPCHK(ctx, hipMemcpyAsync(h, d->acc.p, 24, hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipMemcpyAsync(h + 3, d->hbase.p + nt, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
+  // from here on the slots hold depth: whatever fails below, no add may follow without a reset
+  d->finished = true;
+  d->sz = sbh_depth_sizes{S, h[3], h[1], h[2], (uint32_t)h[0], 0};
+  const hipError_t e = d->runs.ensure(d->sz.n_runs);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    d->sz.n_runs = 0;
+    return fail(ctx, SBH_E_NOMEM, "depth finish: no memory for %llu runs", (unsigned long long)h[3]);
+  }
+  HIPCHK(ctx, launch_depth_runs(d->slots.p, S, d->hbase.p, d->d_spans.p, d->d_off.p, ns, d->sz.n_runs, d->runs.p, st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
+  *out = d->sz;
+  return SBH_OK;
+}
+
+int sbh_depth_fetch(sbh_depth *d, uint32_t span, uint64_t from, uint64_t n, uint32_t *depth) {
+  if (!d || (n && !depth)) return SBH_E_ARG;
+  sbh_ctx *ctx = d->ctx;
+  if (!d->finished) return fail(ctx, SBH_E_STATE, "sbh_depth_fetch before sbh_depth_finish");
+  if (span >= d->spans.size()) return fail(ctx, SBH_E_ARG, "sbh_depth_fetch: span %u of %zu", span, d->spans.size());
+  const uint64_t len = (uint64_t)(d->spans[span].end - d->spans[span].beg);
+  if (from > len || n > len - from) return fail(ctx, SBH_E_ARG, "sbh_depth_fetch past the span");
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  if (n) HIPCHK(ctx, hipMemcpyAsync(depth, d->slots.p + d->off[span] + from, 4 * n, hipMemcpyDeviceToHost, d->st));
+  HIPCHK(ctx, hipStreamSynchronize(d->st));
+  return SBH_OK;
+}
+
+int sbh_depth_runs_fetch(sbh_depth *d, uint64_t first, uint64_t count, sbh_depth_run *runs) {
+  if (!d || (count && !runs)) return SBH_E_ARG;
+  sbh_ctx *ctx = d->ctx;
+  if (!d->finished) return fail(ctx, SBH_E_STATE, "sbh_depth_runs_fetch before sbh_depth_finish");
+  if (first > d->sz.n_runs || count > d->sz.n_runs - first) return fail(ctx, SBH_E_ARG, "sbh_depth_runs_fetch past the runs");
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  if (count)
+    HIPCHK(ctx, hipMemcpyAsync(runs, d->runs.p + first, count * sizeof(sbh_depth_run), hipMemcpyDeviceToHost, d->st));
+  HIPCHK(ctx, hipStreamSynchronize(d->st));
+  return SBH_OK;
+}
+
+const void *sbh_depth_device_ptr(sbh_depth *d, uint32_t span) {
+  return d && d->finished && span < d->spans.size() ? d->slots.p + d->off[span] : nullptr;
+}
+
+uint64_t sbh_depth_slots(const sbh_depth_span *spans, uint32_t n_spans) {
+  if (!sbh_dep::spans_ok(depth_spans(spans), n_spans, 0x7fffffff)) return 0;
+  return sbh_dep::slots_of(depth_spans(spans), n_spans);
+}
+
+int sbh_depth_add_host(const uint8_t *flat, uint64_t flat_size, const uint64_t *starts, uint64_t n,
+                       const sbh_record_filter *filter, const sbh_depth_span *spans, uint32_t n_spans, int32_t n_ref,
+                       uint32_t flags, int32_t *slots, sbh_depth_add_result *out, uint64_t *bad_row) {
+  if ((!flat && flat_size) || (!starts && n) || !slots || !out || (flags & ~SBH_DEPTH_DEL)) return SBH_E_ARG;
+  sbh_bam::Filter F;
+  if (!bam_filter_of(filter, &F) || !sbh_dep::spans_ok(depth_spans(spans), n_spans, n_ref)) return SBH_E_ARG;
+  uint64_t bad = sbh_bam::NO_ROW;
+  const int rc = sbh_dep::add_host(flat, flat_size, starts, n, F, depth_spans(spans), n_spans, n_ref, flags, slots,
+                                     reinterpret_cast<sbh_dep::AddResult *>(out), &bad);
+  if (bad_row) *bad_row = bad;
+  return rc == 0 ? SBH_OK : SBH_E_BAD_RECORD;
+}
+
+int sbh_depth_finish_host(int32_t *slots, const sbh_depth_span *spans, uint32_t n_spans, sbh_depth_run *runs,
+                          uint64_t run_cap, sbh_depth_sizes *out) {
+  if (!slots || !out || (run_cap && !runs)) return SBH_E_ARG;
+  if (!sbh_dep::spans_ok(depth_spans(spans), n_spans, 0x7fffffff)) return SBH_E_ARG;
+  sbh_dep::finish_host(slots, depth_spans(spans), n_spans, reinterpret_cast<sbh_dep::Run *>(runs), run_cap,
+                         reinterpret_cast<sbh_dep::Sizes *>(out));
+  return SBH_OK;
+}
+
+}  // extern "C"

@@ -344,8 +344,6 @@ __global__ __launch_bounds__(256) void k_rec_fields(const uint8_t *__restrict__ 
 
 }  // namespace
 
-hipError_t scan_exclusive_u64(const uint64_t *in, uint64_t *out, uint64_t n, uint64_t *tmp, hipStream_t st);
-
 // cnt: 2 u64 per WP_CHUNK words (chunk sums and their prefix); wpre: one u64 per WPRE_GROUP
 // words of [first, E); tmp: scan_tmp_words(words)
 hipError_t launch_rec_positions_bits(const uint32_t *bits, uint64_t begin, uint64_t first, uint64_t E, uint64_t *cnt,

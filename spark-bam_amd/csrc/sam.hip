@@ -31,10 +31,12 @@
 //    Host rows (len 0 in the size pass, their lengths scattered in before the scan) are skipped.
 //  * Reference names are read inside [off[k], off[k + 1]) for 0 <= k < n_ref only.
 #include <algorithm>
+#include <cstring>
+#include <vector>
 
 #define SBH_HD __host__ __device__
 #include "sam_core.h"
-#include "sbh_internal.h"
+#include "sbh_host.h"
 
 namespace sbh {
 namespace {
@@ -377,46 +379,201 @@ uint32_t wave_grid(uint64_t n) { return (uint32_t)std::min<uint64_t>((n + 3) / 4
 
 }  // namespace
 
-hipError_t launch_sam_sizes(const uint8_t *U, const uint64_t *pos, uint64_t n, const uint64_t *nm_off,
-                            const uint64_t *cg_off, const uint64_t *sq_off, const uint64_t *ax_off, const char *names,
-                            const uint64_t *name_off, int32_t n_ref, uint64_t *len, uint64_t *hostf,
-                            unsigned long long *bad, hipStream_t st) {
+// len / hostf: n + 1 words (the caller zeroes entry n); names / name_off: the packed reference names
+// on the device.
+static hipError_t launch_sam_sizes(const uint8_t *U, const uint64_t *pos, uint64_t n, const uint64_t *nm_off,
+                                   const uint64_t *cg_off, const uint64_t *sq_off, const uint64_t *ax_off, const char *names,
+                                   const uint64_t *name_off, int32_t n_ref, uint64_t *len, uint64_t *hostf,
+                                   unsigned long long *bad, hipStream_t st) {
   if (!n) return hipSuccess;
   hipLaunchKernelGGL(k_sam_sizes, dim3(wave_grid(n)), dim3(256), 0, st, U, pos, n, nm_off, cg_off, sq_off, ax_off,
                      Refs{names, name_off, n_ref}, len, hostf, bad);
   return hipGetLastError();
 }
 
-hipError_t launch_sam_emit(const uint8_t *U, const uint64_t *pos, uint64_t n, const uint64_t *nm_off,
-                           const uint64_t *cg_off, const uint64_t *sq_off, const uint64_t *ax_off, const char *names,
-                           const uint64_t *name_off, int32_t n_ref, const uint64_t *line_off, const uint64_t *hostf,
-                           char *text, hipStream_t st) {
+static hipError_t launch_sam_emit(const uint8_t *U, const uint64_t *pos, uint64_t n, const uint64_t *nm_off,
+                                  const uint64_t *cg_off, const uint64_t *sq_off, const uint64_t *ax_off, const char *names,
+                                  const uint64_t *name_off, int32_t n_ref, const uint64_t *line_off, const uint64_t *hostf,
+                                  char *text, hipStream_t st) {
   if (!n) return hipSuccess;
   hipLaunchKernelGGL(k_sam_emit, dim3(wave_grid(n)), dim3(256), 0, st, U, pos, n, nm_off, cg_off, sq_off, ax_off,
                      Refs{names, name_off, n_ref}, line_off, hostf, text);
   return hipGetLastError();
 }
 
-hipError_t launch_sam_host_rows(const uint8_t *U, const uint64_t *pos, const uint64_t *hostf, const uint64_t *hpre,
-                                uint64_t n, uint64_t *rows, uint64_t *rec_bytes, hipStream_t st) {
+// the rows with hostf set (hpre: its exclusive scan), compacted: their indices and record sizes
+static hipError_t launch_sam_host_rows(const uint8_t *U, const uint64_t *pos, const uint64_t *hostf, const uint64_t *hpre,
+                                       uint64_t n, uint64_t *rows, uint64_t *rec_bytes, hipStream_t st) {
   if (!n) return hipSuccess;
   hipLaunchKernelGGL(k_sam_host_rows, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, U, pos, hostf, hpre, n, rows,
                      rec_bytes);
   return hipGetLastError();
 }
 
-hipError_t launch_sam_gather(const uint8_t *U, const uint64_t *pos, const uint64_t *rows, const uint64_t *goff,
-                             uint64_t m, uint8_t *out, hipStream_t st) {
+// those m rows' record bytes packed at goff
+static hipError_t launch_sam_gather(const uint8_t *U, const uint64_t *pos, const uint64_t *rows, const uint64_t *goff,
+                                    uint64_t m, uint8_t *out, hipStream_t st) {
   if (!m) return hipSuccess;
   hipLaunchKernelGGL(k_sam_gather, dim3(wave_grid(m)), dim3(256), 0, st, U, pos, rows, goff, m, out);
   return hipGetLastError();
 }
 
-hipError_t launch_sam_scatter(const uint64_t *rows, const uint64_t *vals, uint64_t m, uint64_t n, uint64_t *len,
-                              hipStream_t st) {
+// their lines' lengths (vals) back into len
+static hipError_t launch_sam_scatter(const uint64_t *rows, const uint64_t *vals, uint64_t m, uint64_t n, uint64_t *len,
+                                     hipStream_t st) {
   if (!m) return hipSuccess;
   hipLaunchKernelGGL(k_sam_scatter, dim3((uint32_t)((m + 255) / 256)), dim3(256), 0, st, rows, vals, m, n, len);
   return hipGetLastError();
 }
 
 }  // namespace sbh
+
+using namespace sbh;
+
+extern "C" {
+
+// ---- the C-ABI's SAM text calls (the line is defined in sam_core.h) --------------------------
+// Size pass, scan, emit pass over the rows of the last decoded scan.  Both scans (line lengths,
+// host-row flags) are launched before anything is read back, so the common case -- no row with
+// a float tag -- costs one round trip for (bad row, n_host, total) before the text is allocated
+// and written.  With host rows: their indices and record bytes come to the host, sam_core.h's
+// renderer writes their lines, the lengths go back into len[] and the scan runs again; the lines
+// themselves are put into their holes by sbh_records_sam_fetch.
+int sbh_records_sam_scan(sbh_shard *sh, const char *ref_names, const uint64_t *ref_name_off, int32_t n_ref,
+                         sbh_sam_sizes *out) {
+  if (!sh || !out || n_ref < 0 || (n_ref && (!ref_names || !ref_name_off))) return SBH_E_ARG;
+  sbh_ctx *ctx = sh->ctx;
+  auto &R = sh->rec;
+  auto &S = sh->sam;
+  if (!R.valid || !R.decoded) return fail(ctx, SBH_E_STATE, "records_sam_scan without a decoded records scan");
+  for (int32_t k = 0; k < n_ref; ++k)
+    if (ref_name_off[k + 1] < ref_name_off[k]) return fail(ctx, SBH_E_ARG, "reference name offsets must not decrease");
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  hipStream_t st = sh->st;
+  S.valid = false;
+  S.h_rows.clear();
+  S.h_off.assign(1, 0);
+  S.h_text.clear();
+  const uint64_t n = R.sz.n;
+  if (!n) {
+    S.sz = sbh_sam_sizes{0, 0, 0};
+    S.valid = true;
+    *out = S.sz;
+    return SBH_OK;
+  }
+  const uint64_t name_bytes = n_ref ? ref_name_off[n_ref] - ref_name_off[0] : 0;
+  std::vector<uint64_t> roff((size_t)n_ref + 1, 0);  // rebased to the first name
+  for (int32_t k = 0; k <= n_ref && n_ref; ++k) roff[k] = ref_name_off[k] - ref_name_off[0];
+  HIPCHK(ctx, S.refs.ensure(name_bytes + 1));
+  HIPCHK(ctx, S.ref_off.ensure((uint64_t)n_ref + 1));
+  if (name_bytes)
+    HIPCHK(ctx, hipMemcpyAsync(S.refs.p, ref_names + ref_name_off[0], name_bytes, hipMemcpyHostToDevice, st));
+  HIPCHK(ctx, hipMemcpyAsync(S.ref_off.p, roff.data(), 8 * ((uint64_t)n_ref + 1), hipMemcpyHostToDevice, st));
+  for (auto *b : {&S.len, &S.off, &S.hostf, &S.hpre}) HIPCHK(ctx, b->ensure(n + 1));
+  HIPCHK(ctx, sh->tmp.ensure(scan_tmp_words(n + 1)));
+  HIPCHK(ctx, hipMemsetAsync(S.len.p + n, 0, 8, st));
+  HIPCHK(ctx, hipMemsetAsync(S.hostf.p + n, 0, 8, st));
+  unsigned long long *bad = sh->ctr.p + ctr::SAM_BAD;  // first malformed row
+  HIPCHK(ctx, hipMemsetAsync(bad, 0xff, 8, st));
+  HIPCHK(ctx, launch_sam_sizes(sh->U.p, R.pos.p, n, R.nmo.p, R.cgo.p, R.sqo.p, R.axo.p, S.refs.p, S.ref_off.p, n_ref,
+                               S.len.p, S.hostf.p, bad, st));
+  HIPCHK(ctx, scan_exclusive_u64(S.hostf.p, S.hpre.p, n + 1, sh->tmp.p, st));
+  HIPCHK(ctx, scan_exclusive_u64(S.len.p, S.off.p, n + 1, sh->tmp.p, st));  // (speculative: right when n_host == 0)
+  HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::SAM_BAD, bad, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::H_SAM_NHOST, S.hpre.p + n, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::H_SAM_TOTAL, S.off.p + n, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
+  if (sh->h_ctr[ctr::SAM_BAD] != ~0ull)
+    return fail_with(ctx, SBH_E_BAD_RECORD, {(int64_t)sh->h_ctr[ctr::SAM_BAD]},
+                     "record %llu of the scan has a malformed CIGAR or tag area",
+                     (unsigned long long)sh->h_ctr[ctr::SAM_BAD]);
+  const uint64_t n_host = sh->h_ctr[ctr::H_SAM_NHOST];
+  uint64_t total = sh->h_ctr[ctr::H_SAM_TOTAL];
+  if (n_host) {
+    for (auto *b : {&S.rows, &S.rbytes}) HIPCHK(ctx, b->ensure(n_host));
+    HIPCHK(ctx, S.goff.ensure(n_host + 1));
+    HIPCHK(ctx, launch_sam_host_rows(sh->U.p, R.pos.p, S.hostf.p, S.hpre.p, n, S.rows.p, S.rbytes.p, st));
+    S.h_rows.resize(n_host);
+    std::vector<uint64_t> goff(n_host + 1, 0), hlen(n_host);
+    HIPCHK(ctx, hipMemcpyAsync(S.h_rows.data(), S.rows.p, 8 * n_host, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(hlen.data(), S.rbytes.p, 8 * n_host, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    for (uint64_t j = 0; j < n_host; ++j) goff[j + 1] = goff[j] + hlen[j];
+    std::vector<uint8_t> recs(goff[n_host]);
+    HIPCHK(ctx, S.gbuf.ensure(goff[n_host]));
+    HIPCHK(ctx, hipMemcpyAsync(S.goff.p, goff.data(), 8 * (n_host + 1), hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, launch_sam_gather(sh->U.p, R.pos.p, S.rows.p, S.goff.p, n_host, S.gbuf.p, st));
+    HIPCHK(ctx, hipMemcpyAsync(recs.data(), S.gbuf.p, goff[n_host], hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    const sbh_sam::Refs refs{ref_names + ref_name_off[0], roff.data(), n_ref};
+    S.h_off.assign(n_host + 1, 0);
+    uint64_t bad_row = 0;
+    int hr = sbh_sam::render_host(recs.data(), recs.size(), goff.data(), n_host, refs, nullptr, 0, S.h_off.data(), &bad_row);
+    if (!hr) {
+      S.h_text.resize(S.h_off[n_host]);
+      hr = sbh_sam::render_host(recs.data(), recs.size(), goff.data(), n_host, refs, S.h_text.data(), S.h_text.size(),
+                                S.h_off.data(), &bad_row);
+    }
+    if (hr)
+      return fail_with(ctx, SBH_E_BAD_RECORD, {(int64_t)S.h_rows[bad_row]}, "record %llu of the scan has a malformed CIGAR or tag area",
+                       (unsigned long long)S.h_rows[bad_row]);
+    for (uint64_t j = 0; j < n_host; ++j) hlen[j] = S.h_off[j + 1] - S.h_off[j];
+    HIPCHK(ctx, hipMemcpyAsync(S.rbytes.p, hlen.data(), 8 * n_host, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, launch_sam_scatter(S.rows.p, S.rbytes.p, n_host, n, S.len.p, st));
+    HIPCHK(ctx, scan_exclusive_u64(S.len.p, S.off.p, n + 1, sh->tmp.p, st));
+    HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::H_SAM_TOTAL, S.off.p + n, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    total = sh->h_ctr[ctr::H_SAM_TOTAL];
+  }
+  HIPCHK(ctx, S.text.ensure(total));
+  HIPCHK(ctx, launch_sam_emit(sh->U.p, R.pos.p, n, R.nmo.p, R.cgo.p, R.sqo.p, R.axo.p, S.refs.p, S.ref_off.p, n_ref,
+                              S.off.p, S.hostf.p, S.text.p, st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
+  S.sz = sbh_sam_sizes{n, total, n_host};
+  S.valid = true;
+  *out = S.sz;
+  return SBH_OK;
+}
+
+int sbh_records_sam_fetch(sbh_shard *sh, char *text, uint64_t *line_off) {
+  if (!sh) return SBH_E_ARG;
+  sbh_ctx *ctx = sh->ctx;
+  auto &S = sh->sam;
+  if (!S.valid) return fail(ctx, SBH_E_STATE, "records_sam_fetch without a records_sam_scan");
+  const uint64_t n = S.sz.n;
+  if (!n) {
+    if (line_off) line_off[0] = 0;
+    return SBH_OK;
+  }
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  std::vector<uint64_t> own;  // the holes' offsets when the caller does not want line_off
+  if (!line_off && text && S.sz.n_host) {
+    own.resize(n + 1);
+    line_off = own.data();
+  }
+  if (text && S.sz.text_bytes) HIPCHK(ctx, hipMemcpyAsync(text, S.text.p, S.sz.text_bytes, hipMemcpyDeviceToHost, sh->st));
+  if (line_off) HIPCHK(ctx, hipMemcpyAsync(line_off, S.off.p, 8 * (n + 1), hipMemcpyDeviceToHost, sh->st));
+  HIPCHK(ctx, hipStreamSynchronize(sh->st));
+  if (text)
+    for (uint64_t j = 0; j < S.sz.n_host; ++j)
+      std::memcpy(text + line_off[S.h_rows[j]], S.h_text.data() + S.h_off[j], S.h_off[j + 1] - S.h_off[j]);
+  return SBH_OK;
+}
+
+int sbh_sam_render_host(const uint8_t *flat, uint64_t flat_size, const uint64_t *starts, uint64_t n,
+                        const char *ref_names, const uint64_t *ref_name_off, int32_t n_ref, char *text,
+                        uint64_t text_cap, uint64_t *line_off, uint64_t *bad_row) {
+  if ((!flat && flat_size) || (!starts && n) || !line_off || n_ref < 0 || (n_ref && (!ref_names || !ref_name_off)))
+    return SBH_E_ARG;
+  for (int32_t k = 0; k < n_ref; ++k)
+    if (ref_name_off[k + 1] < ref_name_off[k]) return SBH_E_ARG;
+  uint64_t bad = sbh_sam::NO_ROW;
+  const int rc = sbh_sam::render_host(flat, flat_size, starts, n, sbh_sam::Refs{ref_names, ref_name_off, n_ref}, text,
+                                      text_cap, line_off, &bad);
+  if (bad_row) *bad_row = bad;
+  return rc == 0 ? SBH_OK : rc == 1 ? SBH_E_BAD_RECORD : SBH_E_ARG;
+}
+
+}  // extern "C"

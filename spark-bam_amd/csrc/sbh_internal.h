@@ -91,7 +91,31 @@ constexpr uint64_t EAGER_REACH = SBH_ETILE + 4096 + 512 + 64;
 // popcounts of the group's earlier words (one 64-byte read).
 constexpr uint32_t WPRE_GROUP = 16;
 
-// Launchers (defined in the .hip files, called from sbh_api.hip).
+// Launchers that one .hip file defines and another calls: this header is the only place such a
+// function is declared.  (A launcher whose callers all sit in its own file is static there; the
+// host side's structs and helpers are in sbh_host.h.)
+
+// Exclusive scan of n u64 (bgzf_index.hip; out != in); tmp holds scan_tmp_words(n) words.
+uint64_t scan_tmp_words(uint64_t n);
+hipError_t scan_exclusive_u64(const uint64_t *in, uint64_t *out, uint64_t n, uint64_t *tmp, hipStream_t st);
+// Block index (bgzf_index.hip): FindBlockStart's best, the header candidates per scan chunk
+// (cand_chunks(n) of them: counts, then the scan, then the write), the chain over the
+// candidates (build_chain, described there) and the table packed as sbh_block records.
+hipError_t launch_find_block_start(const uint8_t *comp, uint64_t n, uint64_t start, int32_t k, int at_eof,
+                                   unsigned long long *best, hipStream_t st);
+uint64_t cand_chunks(uint64_t n);
+hipError_t launch_cand_count(const uint8_t *comp, uint64_t n, uint64_t from, uint64_t *counts, uint32_t *first,
+                             uint64_t nchunks, hipStream_t st);
+hipError_t launch_cand_write(const uint8_t *comp, uint64_t n, uint64_t from, const uint64_t *counts,
+                             const uint32_t *first, const uint64_t *offs, uint64_t *cand, uint64_t nchunks,
+                             hipStream_t st);
+hipError_t launch_pack_blocks(DevBlocks bl, uint64_t n, uint64_t file_off, uint64_t *out, hipStream_t st,
+                              const uint64_t *rank = nullptr, const uint64_t *v = nullptr,
+                              const uint64_t *next18 = nullptr);
+hipError_t build_chain(const uint8_t *comp, uint64_t n, const uint64_t *cand, uint64_t nc, uint64_t start_rel,
+                       int64_t *J0, int64_t *J1, uint8_t *on, uint64_t *v, uint64_t *rank, uint64_t *tmp,
+                       DevBlocks bl, uint64_t *usz, uint8_t *next18, uint64_t *sidx, bool linear, hipStream_t st);
+
 // Inflate = k_huff (Huffman decode -> LZ77 tokens, block status) then k_lz (tokens ->
 // flat bytes; a block that is one stored deflate block is copied from comp).  tok_buf: >= 4 B
 // of token scratch per flat byte of the launched blocks, tok_buf[0] standing for flat offset
@@ -113,6 +137,38 @@ hipError_t launch_lz(const uint8_t *comp, DevBlocks blocks, uint64_t nblocks, co
 // (init: set *first to ~0 first; false when the caller already did)
 hipError_t launch_first_bad(const uint32_t *status, uint64_t n, unsigned long long *first, hipStream_t stream,
                             bool init = true);
+
+// Checkers and the record chain (check.hip; each launcher's buffers are described at its
+// definition).  counters: the shard's counter buffer, slots in namespace ctr below.
+hipError_t launch_eager(const uint8_t *U, uint64_t u_pad, uint64_t begin, uint64_t end, const uint64_t *seg_end,
+                        uint32_t nseg, uint32_t open_last, const int32_t *ctg, int32_t nctg, int32_t rtc,
+                        uint32_t *bits, unsigned long long *counters, hipStream_t st, uint64_t front,
+                        uint64_t *defer_pos, uint64_t defer_cap, uint64_t *xq_pos, uint64_t xq_cap,
+                        const uint32_t *sieve = nullptr);
+hipError_t launch_eager_xq(const uint8_t *U, uint64_t begin, const uint64_t *seg_end, uint32_t nseg,
+                           uint32_t open_last, const int32_t *ctg, int32_t nctg, int32_t rtc, uint32_t *bits,
+                           unsigned long long *counters, uint64_t *xq_pos, uint64_t cap, hipStream_t st);
+hipError_t launch_eager_defer(const uint8_t *U, uint64_t begin, const uint64_t *seg_end, uint32_t nseg,
+                              uint32_t open_last, const int32_t *ctg, int32_t nctg, int32_t rtc, uint32_t *bits,
+                              unsigned long long *counters, const uint64_t *defer_pos, uint64_t cap,
+                              hipStream_t st);
+hipError_t launch_full(const uint8_t *U, uint64_t u_pad, uint64_t begin, uint64_t end, const uint64_t *seg_end,
+                       uint32_t nseg, uint32_t open_last, const int32_t *ctg, int32_t nctg, int32_t rtc,
+                       uint32_t *words, unsigned long long *counters, uint64_t *close_pos, uint32_t *close_word,
+                       uint64_t close_cap, uint32_t *op_words, uint64_t op_cap_words, hipStream_t st);
+hipError_t launch_first_set(const uint32_t *bits, uint64_t begin, uint64_t from, uint64_t to,
+                            unsigned long long *best, hipStream_t st);
+hipError_t launch_verify_chain_count(const uint8_t *U, const uint32_t *bits, uint64_t begin, uint64_t bits_end,
+                                     uint64_t from, uint64_t E, uint64_t total, unsigned long long *n_anom,
+                                     unsigned long long *first_anom, unsigned long long *exit_pos,
+                                     unsigned long long *n_set, hipStream_t st,
+                                     const unsigned long long *from_dev = nullptr, uint32_t *chunk_cnt = nullptr);
+hipError_t launch_chain_walk(const uint8_t *U, uint64_t first, uint64_t E, uint64_t total,
+                             unsigned long long *count, unsigned long long *last, hipStream_t st);
+hipError_t launch_chain_mark(const uint8_t *U, const uint32_t *bits, uint64_t begin, uint64_t from, uint64_t E,
+                             uint64_t total, const uint64_t *pos, const uint64_t *wpre, uint64_t n, uint32_t *J,
+                             uint32_t *J2, uint32_t *J0, uint64_t *mark, unsigned long long *exit_pos,
+                             uint32_t *final_code, hipStream_t st);
 
 // Record field extraction (records.hip): device columns of a decoded batch (the host
 // view is sbh_records_out in sparkbam.h).
@@ -161,51 +217,6 @@ hipError_t launch_split_count_cc(const uint32_t *bits, uint64_t begin, const uin
 // record starts (flat) -> htsjdk virtual positions over the device block table
 hipError_t launch_rec_vpos(const uint64_t *pos, uint64_t n, DevBlocks bl, uint64_t nblocks, uint64_t file_off,
                            uint64_t *vpos, hipStream_t st);
-// BAI construction (bai.hip; the passes are described there).  key / win / vbeg: n u64 each,
-// flg: n + 1 (the scan's input, head | unmapped << 32), aux: 3 words, err: 3 (preset to ~0).
-hipError_t launch_bai_keys(const uint8_t *U, const uint64_t *pos, uint64_t n, uint64_t total, const int32_t *ctg,
-                           int32_t nctg, DevBlocks bl, uint64_t nblocks, uint64_t file_off, uint64_t *key,
-                           uint64_t *win, uint64_t *vbeg, uint64_t *flg, uint64_t *aux, unsigned long long *err,
-                           hipStream_t st);
-hipError_t launch_bai_heads(const uint64_t *key, const uint64_t *win, const uint64_t *vbeg, uint64_t n,
-                            const uint64_t *lin_off, uint64_t *flg, uint64_t *lin, hipStream_t st);
-// pre: the exclusive scan of flg[0..n]; ridx: nruns words; runs: nruns entries
-hipError_t launch_bai_runs(const uint64_t *flg, const uint64_t *pre, uint64_t n, uint64_t nruns, const uint64_t *key,
-                           const uint64_t *vbeg, const uint64_t *aux, uint64_t *ridx, sbh_bai_run *runs,
-                           hipStream_t st);
-// SAM text of the decoded records (sam.hip; the line is defined in sam_core.h).  len / hostf: n + 1
-// words (the caller zeroes entry n); names / name_off: the packed reference names on the device.
-hipError_t launch_sam_sizes(const uint8_t *U, const uint64_t *pos, uint64_t n, const uint64_t *nm_off,
-                            const uint64_t *cg_off, const uint64_t *sq_off, const uint64_t *ax_off, const char *names,
-                            const uint64_t *name_off, int32_t n_ref, uint64_t *len, uint64_t *hostf,
-                            unsigned long long *bad, hipStream_t st);
-hipError_t launch_sam_emit(const uint8_t *U, const uint64_t *pos, uint64_t n, const uint64_t *nm_off,
-                           const uint64_t *cg_off, const uint64_t *sq_off, const uint64_t *ax_off, const char *names,
-                           const uint64_t *name_off, int32_t n_ref, const uint64_t *line_off, const uint64_t *hostf,
-                           char *text, hipStream_t st);
-// the rows with hostf set (hpre: its exclusive scan), compacted: their indices and record sizes;
-// their bytes packed at goff; their lines' lengths back into len
-hipError_t launch_sam_host_rows(const uint8_t *U, const uint64_t *pos, const uint64_t *hostf, const uint64_t *hpre,
-                                uint64_t n, uint64_t *rows, uint64_t *rec_bytes, hipStream_t st);
-hipError_t launch_sam_gather(const uint8_t *U, const uint64_t *pos, const uint64_t *rows, const uint64_t *goff,
-                             uint64_t m, uint8_t *out, hipStream_t st);
-hipError_t launch_sam_scatter(const uint64_t *rows, const uint64_t *vals, uint64_t m, uint64_t n, uint64_t *len,
-                              hipStream_t st);
-// BAM stream of selected rows (bam_gather.hip; validity and predicate in bam_gather_core.h).  len / kh:
-// n + 1 words (the caller zeroes entry n); bad / past preset to ~0: the first invalid row, the first
-// row invalid only because the stream ends too early.  off / khpre: the exclusive scans of len / kh
-// (kh = keep | run head << 32, so n < 2^32).  rec_off, rows, run_dst, run_src: n + 1 words.
-hipError_t launch_bam_keep(const uint8_t *U, const uint64_t *pos, uint64_t n, uint64_t total, uint32_t flag_require,
-                           uint32_t flag_exclude, int32_t min_mapq, const uint64_t *row_begin, const uint64_t *row_end,
-                           uint64_t n_row_ranges, uint64_t *len, uint64_t *kh, unsigned long long *bad,
-                           unsigned long long *past, hipStream_t st);
-hipError_t launch_bam_index(const uint64_t *pos, const uint64_t *off, const uint64_t *kh, const uint64_t *khpre,
-                            uint64_t n, uint64_t head_bytes, uint64_t *rec_off, uint64_t *rows, uint64_t *run_dst,
-                            uint64_t *run_src, hipStream_t st);
-// out[head_bytes, bytes) from the runs; reads U below (the last run's end) + 32
-hipError_t launch_bam_copy(const uint8_t *U, const uint64_t *run_dst, const uint64_t *run_src, uint64_t n_runs,
-                           uint64_t head_bytes, uint64_t bytes, uint8_t *out, hipStream_t st);
-hipError_t launch_bam_heads(const uint64_t *pos, const uint64_t *len, uint64_t n, uint64_t *kh, hipStream_t st);
 // Coordinate order of the kept rows (bam_sort.hip; the key in bam_sort_core.h).  launch_sort_keys:
 // key / row of the first khpre[n] & 0xffffffff entries of rows (k_bam_index's), acc = ctr::SORT_DESC
 // (preset 0, 0, ~0).  launch_sort_pass: one stable 8-bit pass from (key, row) to (key_out, row_out);
@@ -219,27 +230,6 @@ hipError_t launch_sort_pass(const uint64_t *key, const uint32_t *row, uint64_t m
 hipError_t launch_sort_apply(const uint64_t *pos, const uint64_t *len, const uint32_t *row, uint64_t m, uint64_t *pos2,
                              uint64_t *len2, uint64_t *kh, hipStream_t st);
 hipError_t launch_sort_rows(const uint32_t *row, uint64_t m, uint64_t *rows, hipStream_t st);
-// Per-base depth (depth.hip; events, validity and runs in depth_core.h).  launch_depth_check: keep =
-// ceil(n / 64) ballot words, acc = ctr::DEPTH_BAD .. DEPTH_UNPLACED (preset ~0, ~0, 0, 0).
-// launch_depth_events: acc = ctr::DEPTH_COUNTED, DEPTH_COV (preset 0); off: n_spans + 1 entries,
-// off[n_spans] == S.  The finish: tile sums (depth_tiles(S) words), their exclusive scan as base,
-// launch_depth_apply (heads: depth_tiles(S) + 1 words, the caller zeroes the last; tstat: 3
-// depth_tiles(S) words of per-tile max, covered, sum, folded into acc: max, covered, sum, preset 0),
-// the scan of heads as hbase, launch_depth_runs.
-uint64_t depth_tiles(uint64_t S);
-hipError_t launch_depth_check(const uint8_t *U, const uint64_t *pos, uint64_t n, uint64_t total, uint32_t flag_require,
-                              uint32_t flag_exclude, int32_t min_mapq, const uint64_t *row_begin, const uint64_t *row_end,
-                              uint64_t n_row_ranges, int32_t n_ref, uint64_t *keep, unsigned long long *acc,
-                              hipStream_t st);
-hipError_t launch_depth_events(const uint8_t *U, const uint64_t *pos, uint64_t n, const uint64_t *keep,
-                               const sbh_depth_span *spans, const uint64_t *off, uint32_t n_spans, uint32_t flags,
-                               int32_t *slots, uint64_t S, unsigned long long *acc, hipStream_t st);
-hipError_t launch_depth_tile_sums(const int32_t *slots, uint64_t S, uint64_t *sums, hipStream_t st);
-hipError_t launch_depth_apply(int32_t *slots, uint64_t S, const uint64_t *base, const uint64_t *off, uint32_t n_spans,
-                              uint64_t *heads, uint64_t *tstat, unsigned long long *acc, hipStream_t st);
-hipError_t launch_depth_runs(const int32_t *depth, uint64_t S, const uint64_t *hbase, const sbh_depth_span *spans,
-                             const uint64_t *off, uint32_t n_spans, uint64_t n_runs, sbh_depth_run *runs,
-                             hipStream_t st);
 // BGZF footer CRC32 of every inflated, non-truncated block (crc.hip).
 hipError_t launch_block_crc(const uint8_t *comp, DevBlocks bl, uint64_t nblocks, const uint8_t *U,
                             unsigned long long *n_bad, unsigned long long *first_bad, hipStream_t st);
@@ -270,9 +260,6 @@ constexpr uint64_t ZDEFLATE_TOK_ENTRIES = 65536;
 constexpr uint64_t ZDEFLATE_REC_BYTES = 16384;
 constexpr uint32_t ZDEFLATE_HDR_BYTES = 640;  // a dynamic block header (<= ~4500 bits)
 constexpr uint64_t ZDEFLATE_SLOT = 65536 + 64;  // 18 + (< 65518) + 8 bytes, a multiple of 16
-hipError_t launch_zdeflate(const uint8_t *src, uint64_t n, uint64_t b0, uint32_t nbatch, int level, uint16_t *prev,
-                           uint64_t *info, uint32_t *toks, uint8_t *recs, uint8_t *slots, uint32_t *sizes,
-                           hipStream_t st);
 hipError_t launch_member_footer(const uint8_t *src, uint64_t n, uint64_t b0, uint64_t nblocks, uint32_t nbatch,
                                 uint8_t *slots, uint64_t stride, const uint32_t *sizes, hipStream_t st);
 

@@ -41,8 +41,12 @@
 //   3. This notice may not be removed or altered from any source distribution.
 //
 //   Jean-loup Gailly jloup@gzip.org, Mark Adler madler@alumni.caltech.edu
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
 #define SBH_HD __host__ __device__
-#include "sbh_internal.h"
+#include "sbh_host.h"
 #include "zdeflate_core.h"
 
 namespace sbh {
@@ -511,9 +515,9 @@ __global__ __launch_bounds__(ZE_T) void k_zemit(const uint8_t *__restrict__ src,
 
 }  // namespace
 
-hipError_t launch_zdeflate(const uint8_t *src, uint64_t n, uint64_t b0, uint32_t nbatch, int level, uint16_t *prev,
-                           uint64_t *info, uint32_t *toks, uint8_t *recs, uint8_t *slots, uint32_t *sizes,
-                           hipStream_t st) {
+static hipError_t launch_zdeflate(const uint8_t *src, uint64_t n, uint64_t b0, uint32_t nbatch, int level, uint16_t *prev,
+                                  uint64_t *info, uint32_t *toks, uint8_t *recs, uint8_t *slots, uint32_t *sizes,
+                                  hipStream_t st) {
   const uint64_t nb = (n + ZPAY - 1) / ZPAY;
   if (!nbatch || b0 >= nb) return hipSuccess;
   if (nbatch > ZDEFLATE_BATCH || b0 + nbatch > nb || level < 0 || (level > 0 && level < 4) || level > 9)
@@ -533,3 +537,127 @@ hipError_t launch_zdeflate(const uint8_t *src, uint64_t n, uint64_t b0, uint32_t
 }
 
 }  // namespace sbh
+
+using namespace sbh;
+
+extern "C" {
+
+// ---- the C-ABI's BGZF writer calls (the fast level's kernels: deflate.hip; HTSJDKRewrite.scala:62-67)
+uint64_t sbh_bgzf_compress_bound(uint64_t n) { return deflate_nblocks(n) * ZDEFLATE_SLOT + 28; }
+
+int sbh_bgzf_compress(sbh_ctx *ctx, const void *src, uint64_t n, int src_on_device, uint8_t *out,
+                      uint64_t out_cap, uint64_t *out_size, uint64_t *n_blocks, float *deflate_ms) {
+  return sbh_bgzf_compress_level(ctx, src, n, src_on_device, SBH_LEVEL_HTSJDK, out, out_cap, out_size, n_blocks,
+                                 deflate_ms);
+}
+
+int sbh_bgzf_compress_level(sbh_ctx *ctx, const void *src, uint64_t n, int src_on_device, int level, uint8_t *out,
+                            uint64_t out_cap, uint64_t *out_size, uint64_t *n_blocks, float *deflate_ms) {
+  if (!ctx || !out_size || (!src && n) || !out) return SBH_E_ARG;
+  const bool fast = level == SBH_LEVEL_FAST;
+  if (!fast && (level < 0 || (level > 0 && level < 4) || level > 9))
+    return fail(ctx, SBH_E_ARG, "bgzf_compress: level %d (0, 4..9 or SBH_LEVEL_FAST)", level);
+  const uint64_t nb = deflate_nblocks(n);
+  if (out_cap < sbh_bgzf_compress_bound(n)) return fail(ctx, SBH_E_ARG, "bgzf_compress: out_cap < bound");
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  struct Bufs {  // per-call scratch (and stream), freed on every return path
+    DBuf<uint8_t> in, slots, packed, recs;
+    DBuf<uint16_t> prev;
+    DBuf<uint32_t> toks, sizes;
+    DBuf<uint64_t> offs, info;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hipStream_t own = nullptr;
+    ~Bufs() {  // (the buffers free themselves after this, the call's own stream drained)
+      if (own) (void)hipStreamSynchronize(own);
+      if (e0) (void)hipEventDestroy(e0);
+      if (e1) (void)hipEventDestroy(e1);
+      if (own) (void)hipStreamDestroy(own);
+    }
+  } B;
+  // a stream of the call's own unless the caller gave the context one: concurrent callers of one
+  // context (include/sparkbam.h, threading) neither wait for nor time each other's kernels
+  if (ctx->own_stream) HIPCHK(ctx, hipStreamCreateWithFlags(&B.own, hipStreamNonBlocking));
+  hipStream_t st = B.own ? B.own : ctx->stream;
+  const uint8_t *d_src = static_cast<const uint8_t *>(src);
+  if (!src_on_device && n) {
+    HIPCHK(ctx, B.in.ensure(n));
+    HIPCHK(ctx, hipMemcpyAsync(B.in.p, src, n, hipMemcpyHostToDevice, st));
+    d_src = B.in.p;
+  }
+  uint64_t total = 0;
+  float kms = 0.f;
+  if (nb) {
+    // members in batches: scratch bounded by the batch, not the input
+    uint64_t bmax = fast ? DEFLATE_BATCH : ZDEFLATE_BATCH;
+    if (const char *e = std::getenv("SBH_ZDEFLATE_BATCH"))
+      if (!fast && std::strtoull(e, nullptr, 10) > 0) bmax = std::strtoull(e, nullptr, 10);
+    const uint64_t stride = fast ? 65536ull : ZDEFLATE_SLOT;
+    // scratch per member; the batch shrinks to half of the free HBM (a resident shard may hold
+    // the rest), never below 256 members
+    const uint64_t per_member =
+        2 * stride + (fast ? DEFLATE_PREV_BYTES + DEFLATE_TOK_BYTES + DEFLATE_REC_BYTES
+                           : level > 0 ? ZDEFLATE_PREV_ENTRIES * 2 + ZDEFLATE_INFO_ENTRIES * 8 +
+                                             ZDEFLATE_TOK_ENTRIES * 4 + ZDEFLATE_REC_BYTES
+                                       : 0) + 16;
+    size_t hbm_free = 0, hbm_total = 0;
+    if (hipMemGetInfo(&hbm_free, &hbm_total) == hipSuccess && hbm_free / 2 / per_member < bmax)
+      bmax = std::max<uint64_t>(256, hbm_free / 2 / per_member);
+    const uint64_t cap = nb < bmax ? nb : bmax;
+    HIPCHK(ctx, B.slots.ensure(cap * stride));
+    HIPCHK(ctx, B.packed.ensure(cap * stride));
+    if (fast) {
+      HIPCHK(ctx, B.prev.ensure(cap * (DEFLATE_PREV_BYTES / 2)));
+      HIPCHK(ctx, B.toks.ensure(cap * (DEFLATE_TOK_BYTES / 4)));
+      HIPCHK(ctx, B.recs.ensure(cap * DEFLATE_REC_BYTES));
+    } else if (level > 0) {
+      HIPCHK(ctx, B.prev.ensure(cap * ZDEFLATE_PREV_ENTRIES));
+      HIPCHK(ctx, B.info.ensure(cap * ZDEFLATE_INFO_ENTRIES));
+      HIPCHK(ctx, B.toks.ensure(cap * ZDEFLATE_TOK_ENTRIES));
+      HIPCHK(ctx, B.recs.ensure(cap * ZDEFLATE_REC_BYTES));
+    }
+    HIPCHK(ctx, B.sizes.ensure(cap));
+    HIPCHK(ctx, B.offs.ensure(cap));
+    HIPCHK(ctx, hipEventCreate(&B.e0));
+    HIPCHK(ctx, hipEventCreate(&B.e1));
+    std::vector<uint32_t> hs(cap);
+    std::vector<uint64_t> ho(cap);
+    for (uint64_t b0 = 0; b0 < nb; b0 += cap) {
+      const uint32_t k = (uint32_t)(nb - b0 < cap ? nb - b0 : cap);
+      HIPCHK(ctx, hipEventRecord(B.e0, st));
+      if (fast)
+        HIPCHK(ctx, launch_deflate(d_src, n, b0, k, B.prev.p, B.toks.p, B.recs.p, B.slots.p, B.sizes.p, st));
+      else
+        HIPCHK(ctx, launch_zdeflate(d_src, n, b0, k, level, B.prev.p, B.info.p, B.toks.p, B.recs.p, B.slots.p,
+                                    B.sizes.p, st));
+      HIPCHK(ctx, hipEventRecord(B.e1, st));
+      HIPCHK(ctx, hipMemcpyAsync(hs.data(), B.sizes.p, 4ull * k, hipMemcpyDeviceToHost, st));
+      HIPCHK(ctx, hipStreamSynchronize(st));
+      float ms = 0.f;
+      HIPCHK(ctx, hipEventElapsedTime(&ms, B.e0, B.e1));
+      kms += ms;
+      uint64_t bt = 0;
+      for (uint32_t j = 0; j < k; ++j) {
+        if (hs[j] < 26 || hs[j] > stride)
+          return fail(ctx, SBH_E_HIP, "bgzf_compress: block %llu size %u", (unsigned long long)(b0 + j), hs[j]);
+        ho[j] = bt;
+        bt += hs[j];
+      }
+      if (total + bt + 28 > out_cap) return fail(ctx, SBH_E_ARG, "bgzf_compress: out_cap exceeded");
+      HIPCHK(ctx, hipMemcpyAsync(B.offs.p, ho.data(), 8ull * k, hipMemcpyHostToDevice, st));
+      HIPCHK(ctx, launch_deflate_gather(B.slots.p, stride, B.sizes.p, B.offs.p, k, B.packed.p, st));
+      HIPCHK(ctx, hipMemcpyAsync(out + total, B.packed.p, bt, hipMemcpyDeviceToHost, st));
+      HIPCHK(ctx, hipStreamSynchronize(st));
+      total += bt;
+    }
+  }
+  if (deflate_ms) *deflate_ms = kms;
+  static const uint8_t eof[28] = {31, 139, 8, 4, 0, 0, 0, 0, 0, 255, 6, 0, 66, 67, 2, 0,
+                                  27, 0,   3, 0, 0, 0, 0, 0, 0, 0,   0, 0};
+  memcpy(out + total, eof, 28);
+  *out_size = total + 28;
+  if (n_blocks) *n_blocks = nb;
+  return SBH_OK;
+}
+
+}  // extern "C"
