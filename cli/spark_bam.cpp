@@ -37,6 +37,7 @@
 #include <unistd.h>
 
 #include "../include/sparkbam.h"
+#include "../spark-bam_amd/csrc/tally_core.h"  // flagstat's and idxstats' text (host functions only)
 
 namespace {
 
@@ -261,6 +262,7 @@ struct Args {
   // depth: -a every position of the spans, -r REGION, -J D ops cover, --bedgraph; -F defaults to 1796
   bool depth_all = false, count_del = false, bedgraph = false, has_exclude = false;
   std::string region;
+  bool count_only = false;  // view -c: the number of records that pass -f / -F / -q, nothing else
 };
 
 // decimal or 0x hex
@@ -282,7 +284,7 @@ Args parse(int argc, char **argv) {
     throw Error(SBH_E_ARG,
                 "usage: spark-bam <command> [options] <bam>\n"
                 "  commands: compute-splits count-reads check-bam full-check index-blocks index-records index-bai\n"
-                "            check-blocks htsjdk-rewrite view sort depth\n"
+                "            check-blocks htsjdk-rewrite view sort depth flagstat idxstats\n"
                 "  view [-h|--header] [-o FILE] <bam>: the records as SAM text (-h: the header text first)\n"
                 "  view -b -o OUT [-f INT] [-F INT] [-q INT] [-r ROWS] [--level N] [--index-bai] [--sort] <bam>: the records with\n"
                 "       (flag & f) == f, (flag & F) == 0, mapq >= q and an index in ROWS (a-b,c-d: htsjdk-rewrite's -r)\n"
@@ -292,9 +294,13 @@ Args parse(int argc, char **argv) {
                 "  depth [-a] [-r REGION] [-f INT] [-F INT] [-q INT] [-J] [--bedgraph] [-o FILE] <bam>: per-base depth as\n"
                 "       RNAME POS DEPTH lines (samtools depth; -a: zero-depth positions too) or, with --bedgraph, RNAME BEG END\n"
                 "       DEPTH runs (genomecov -bg); REGION is NAME or NAME:BEG-END (1-based, inclusive); -F defaults to 1796;\n"
-                "       -J: deletions count");
+                "       -J: deletions count\n"
+                "  flagstat [-f INT] [-F INT] [-q INT] [-o FILE] <bam>: samtools flagstat's sixteen lines of the records that pass\n"
+                "  idxstats [-f INT] [-F INT] [-q INT] [-o FILE] <bam>: NAME LENGTH MAPPED UNMAPPED per reference, then the `*` line\n"
+                "       (samtools idxstats), counted from the records: no index is read, any order will do\n"
+                "  view -c [-f INT] [-F INT] [-q INT] <bam>: how many records pass (samtools view -c)");
   a.cmd = argv[1];
-  const bool rewrite = a.cmd == "htsjdk-rewrite";
+  const bool rewrite = a.cmd == "htsjdk-rewrite", tally = a.cmd == "flagstat" || a.cmd == "idxstats";
   std::vector<std::string> pos;
   for (int i = 2; i < argc; ++i) {
     std::string t = argv[i];
@@ -316,6 +322,12 @@ Args parse(int argc, char **argv) {
     else if (a.cmd == "view" && (t == "-l" || t == "--level")) a.level = (int)parse_int(next());
     else if (a.cmd == "view" && t == "--index-bai") a.idx_bai = true;
     else if (a.cmd == "view" && t == "--sort") a.sort = true;
+    else if (a.cmd == "view" && (t == "-c" || t == "--count")) a.count_only = true;
+    else if (tally && (t == "-f" || t == "--require-flags")) a.flag_require = (uint32_t)parse_int(next());
+    else if (tally && (t == "-F" || t == "--exclude-flags")) a.flag_exclude = (uint32_t)parse_int(next());
+    else if (tally && (t == "-q" || t == "--min-mapq")) a.min_mapq = (int)parse_int(next());
+    else if (tally && (t == "-o" || t == "--output")) a.out = next();
+    else if (tally && t.size() > 1 && t[0] == '-') throw Error(SBH_E_ARG, "usage: " + a.cmd + " [-f INT] [-F INT] [-q INT] [-o FILE] <bam> (unknown option " + t + ")");
     else if (a.cmd == "depth" && t == "-a") a.depth_all = true;
     else if (a.cmd == "depth" && (t == "-r" || t == "--region")) a.region = next();
     else if (a.cmd == "depth" && (t == "-f" || t == "--require-flags")) a.flag_require = (uint32_t)parse_int(next());
@@ -342,7 +354,12 @@ Args parse(int argc, char **argv) {
   }
   if (pos.empty()) throw Error(SBH_E_ARG, "missing BAM path");
   a.path = pos[0];
-  if (pos.size() > 1 && a.cmd != "depth") a.out = pos[1];
+  if (a.count_only) {
+    if (a.bam_out || a.sam_header || a.has_read_ranges || a.idx_bai || a.sort || !a.out.empty() || pos.size() != 1 ||
+        (pos[0].size() > 1 && pos[0][0] == '-'))
+      throw Error(SBH_E_ARG, "usage: view -c [-f INT] [-F INT] [-q INT] <bam>");
+  }
+  if (pos.size() > 1 && a.cmd != "depth" && !tally) a.out = pos[1];
   if (a.cmd == "depth" && !a.has_exclude) a.flag_exclude = 1796;  // UNMAP, SECONDARY, QCFAIL, DUP: samtools depth's
   if (a.cmd == "sort") {
     a.bam_out = a.sort = true;
@@ -957,7 +974,10 @@ int index_bai(const Args &a) {
 // text back.  -h: the BAM header text (the l_text bytes after the magic) first, verbatim.
 int view_bam(const Args &a);
 
+int tally(const Args &a);
+
 int view(const Args &a) {
+  if (a.count_only) return tally(a);
   if (a.bam_out) return view_bam(a);
   if (a.has_read_ranges || a.flag_require || a.flag_exclude || a.min_mapq || a.idx_bai || a.sort)
     throw Error(SBH_E_ARG, "view: -f / -F / -q / -r / --index-bai / --sort select records for BAM output: they need -b");
@@ -1146,6 +1166,47 @@ int depth(const Args &a) {
     }
   }
   ok = ok && fwrite(text.data(), 1, text.size(), f) == text.size() && fflush(f) == 0;
+  if (f != stdout) fclose(f);
+  if (!ok) throw Error(SBH_E_ARG, "short write to " + (a.out.empty() ? std::string("stdout") : a.out));
+  return 0;
+}
+
+// flagstat, idxstats, view -c: one pass over the records that pass -f / -F / -q, whole file resident as
+// depth holds it, counted on the device (sbh_records_tally_add); the counts come back and are printed
+// here by tally_core.h's renderers -- samtools flagstat's sixteen lines, samtools idxstats' line per
+// reference and its `*` line, or (view -c) the number of records kept.
+int tally(const Args &a) {
+  Loaded L(a.path);
+  uint64_t seg_end = L.flat;
+  for (const sbh_block &b : L.blocks)
+    if (b.flags & SBH_BLOCK_EMPTY) { seg_end = b.ustart; break; }
+  const int32_t n_ref = (int32_t)L.hdr.lens.size();
+  struct Acc {
+    sbh_tally *t = nullptr;
+    ~Acc() { sbh_tally_destroy(t); }
+  } acc;
+  chk(sbh_tally_create(g_ctx, n_ref, &acc.t), "tally create");
+  sbh_tally_add_result ar{};
+  if (seg_end > L.hdr.end) {
+    uint64_t n = 0;
+    chk(sbh_check_eager(L.sh, L.hdr.end, seg_end, a.reads_to_check, nullptr, &n), "eager");
+    sbh_records_sizes rs{};
+    chk(sbh_records_scan(L.sh, L.hdr.end, seg_end, &rs), "records scan");
+    sbh_record_filter f{};
+    f.flag_require = a.flag_require;
+    f.flag_exclude = a.flag_exclude;
+    f.min_mapq = a.min_mapq;
+    chk(sbh_records_tally_add(L.sh, acc.t, &f, &ar), "tally add");
+  }
+  std::vector<uint64_t> flag(2 * SBH_TALLY_ROWS), ref(2 * ((size_t)n_ref + 1));
+  chk(sbh_tally_fetch(acc.t, flag.data(), 0, (uint64_t)n_ref + 1, ref.data()), "tally fetch");
+  std::string text;
+  if (a.count_only) text = std::to_string(ar.n_kept) + "\n";
+  else if (a.cmd == "flagstat") text = sbh_tal::flagstat_text(flag.data());
+  else text = sbh_tal::idxstats_text(ref.data(), L.hdr.names.data(), L.hdr.lens.data(), n_ref);
+  FILE *f = a.out.empty() ? stdout : fopen(a.out.c_str(), "wb");
+  if (!f) throw Error(SBH_E_ARG, "cannot write " + a.out);
+  const bool ok = fwrite(text.data(), 1, text.size(), f) == text.size() && fflush(f) == 0;
   if (f != stdout) fclose(f);
   if (!ok) throw Error(SBH_E_ARG, "short write to " + (a.out.empty() ? std::string("stdout") : a.out));
   return 0;
@@ -1360,6 +1421,7 @@ int main(int argc, char **argv) {
     else if (a.cmd == "htsjdk-rewrite") rc = htsjdk_rewrite(a);
     else if (a.cmd == "view" || a.cmd == "sort") rc = view(a);
     else if (a.cmd == "depth") rc = depth(a);
+    else if (a.cmd == "flagstat" || a.cmd == "idxstats") rc = tally(a);
     else throw Error(SBH_E_ARG, "unknown command " + a.cmd);
     sbh_ctx_destroy(g_ctx);
     return rc;

@@ -769,6 +769,46 @@ int sbh_depth_add_host(const uint8_t *flat, uint64_t flat_size, const uint64_t *
 int sbh_depth_finish_host(int32_t *slots /* in place -> depth */, const sbh_depth_span *spans, uint32_t n_spans,
                           sbh_depth_run *runs, uint64_t run_cap, sbh_depth_sizes *out);
 
+/* ---- Flag counts and per-reference read counts ---------------------------------------------
+ * What samtools flagstat and samtools idxstats report, counted on the device in one pass over the
+ * fixed fields of a record scan's rows and summed over any number of scans and shards in an
+ * sbh_tally, which belongs to a context and outlives the shards added to it (csrc/tally_core.h
+ * holds the definition for device and host).
+ *
+ * A row the filter keeps (NULL: every row) counts; a kept row whose reference id is >= n_ref is a
+ * bad row, the mate's reference id is not validated, and every row, kept or not, must be a valid
+ * record.  flag[SBH_TALLY_ROWS][2]: column 0 the QC-passed rows, column 1 the QC-failed ones
+ * (0x200); the rows are total, primary, secondary, supplementary, duplicates, primary duplicates,
+ * mapped, primary mapped, paired, read1, read2, properly paired, itself and mate mapped,
+ * singletons, mate on a different reference, the same with mapq >= 5 -- flagstat's lines in its
+ * order.  ref[n_ref + 1][2]: per reference id the rows with 0x4 clear (column 0) and set (column
+ * 1); bin n_ref takes every row without a reference (idxstats' `*` line).
+ *
+ * sbh_records_tally_add uses the rows of the last valid scan on the shard, in their order, as
+ * sbh_records_bam_scan does (a row delivered twice counts twice; decode == 0 is enough), and
+ * leaves the scan's rows, columns, text and BAM stream alone.  It synchronises the shard's stream
+ * before it returns: the shard may be destroyed right after.  A failed add -- SBH_E_BAD_RECORD
+ * {row}, or SBH_E_NEED_HALO when the first bad row merely runs past an open shard end -- leaves
+ * the accumulator exactly as it was.  There is no finish: sbh_tally_fetch may be called between
+ * adds, and copies flag (32 words, or NULL) and bins [first_bin, first_bin + n_bins) of ref (2
+ * n_bins words, or NULL); first_bin + n_bins > n_ref + 1 is SBH_E_ARG, and so are a negative n_ref
+ * and a shard of another context.  One thread at a time per sbh_tally. */
+typedef struct sbh_tally sbh_tally;           /* owned by a context; outlives shards */
+typedef struct { uint64_t n, n_kept; } sbh_tally_add_result;
+#define SBH_TALLY_ROWS 16
+int sbh_tally_create(sbh_ctx *ctx, int32_t n_ref /* >= 0 */, sbh_tally **out);
+int sbh_tally_destroy(sbh_tally *t);
+int sbh_tally_reset(sbh_tally *t);
+int sbh_records_tally_add(sbh_shard *sh, sbh_tally *t, const sbh_record_filter *filter /* NULL: all */,
+                          sbh_tally_add_result *out);
+int sbh_tally_fetch(sbh_tally *t, uint64_t *flag /* [16][2] or NULL */, uint64_t first_bin, uint64_t n_bins,
+                    uint64_t *ref /* [n_bins][2] or NULL */);
+/* HOST ONLY, no context, no GPU: adds into flag[16][2] and ref[n_ref + 1][2] (the caller zeroes
+ * them first); SBH_E_BAD_RECORD with *bad_row = the first bad row, the arrays untouched. */
+int sbh_tally_add_host(const uint8_t *flat, uint64_t flat_size, const uint64_t *starts, uint64_t n,
+                       const sbh_record_filter *filter, int32_t n_ref, uint64_t *flag, uint64_t *ref,
+                       sbh_tally_add_result *out, uint64_t *bad_row);
+
 /* ---- BGZF writer -------------------------------------------------
  * The block compressor behind HTSJDKRewrite (cli/src/main/scala/org/hammerlab/bam/rewrite/
  * HTSJDKRewrite.scala:62-67: SAMFileWriterFactory.makeBAMWriter -> htsjdk

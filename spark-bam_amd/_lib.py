@@ -51,6 +51,8 @@ EXPORTS = [
     "sbh_depth_create", "sbh_depth_destroy", "sbh_depth_reset", "sbh_records_depth_add", "sbh_depth_finish",
     "sbh_depth_fetch", "sbh_depth_runs_fetch", "sbh_depth_device_ptr", "sbh_depth_slots", "sbh_depth_add_host",
     "sbh_depth_finish_host",
+    "sbh_tally_create", "sbh_tally_destroy", "sbh_tally_reset", "sbh_records_tally_add", "sbh_tally_fetch",
+    "sbh_tally_add_host",
 ]
 ORDER_SCAN, ORDER_COORDINATE = 0, 1  # SBH_ORDER_*
 LEVEL_HTSJDK, LEVEL_FAST = 5, -1  # sbh_bgzf_compress_level: htsjdk's zlib level 5 / this library's own coder
@@ -148,6 +150,10 @@ class SbhDepthAddResult(C.Structure):
 class SbhDepthSizes(C.Structure):
     _fields_ = [("slots", C.c_uint64), ("n_runs", C.c_uint64), ("covered", C.c_uint64), ("sum", C.c_uint64),
                 ("max_depth", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class SbhTallyAddResult(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("n_kept", C.c_uint64)]
 
 
 class SbhRecordsOut(C.Structure):  # host buffers (sbh_records_out); NULL = not copied
@@ -297,6 +303,12 @@ def lib():
         "sbh_depth_add_host": [P, U64, P, U64, C.POINTER(SbhRecordFilter), P, U32, I32, U32, P,
                                C.POINTER(SbhDepthAddResult), PU64],
         "sbh_depth_finish_host": [P, P, U32, P, U64, C.POINTER(SbhDepthSizes)],
+        "sbh_tally_create": [P, I32, C.POINTER(P)],
+        "sbh_tally_destroy": [P],
+        "sbh_tally_reset": [P],
+        "sbh_records_tally_add": [P, P, C.POINTER(SbhRecordFilter), C.POINTER(SbhTallyAddResult)],
+        "sbh_tally_fetch": [P, P, U64, U64, P],
+        "sbh_tally_add_host": [P, U64, P, U64, C.POINTER(SbhRecordFilter), I32, P, P, C.POINTER(SbhTallyAddResult), PU64],
         "sbh_bgzf_compress": [P, P, U64, I32, P, U64, PU64, PU64, C.POINTER(C.c_float)],
         "sbh_bgzf_compress_level": [P, P, U64, I32, I32, P, U64, PU64, PU64, C.POINTER(C.c_float)],
     }

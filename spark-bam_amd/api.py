@@ -495,6 +495,67 @@ def depth(path_or_bytes, region=None, flag_require=0, flag_exclude=0x704, min_ma
             ctx.close()
 
 
+def _tally(path_or_bytes, flag_require, flag_exclude, min_mapq, window, ctx, reads_to_check):
+    """flagstat's and idxstats' one pass: every window of iter_reads' walk scanned
+    and counted into one accumulator in HBM (Context.tally)."""
+    from .tally import TallyResult
+    data = _file_array(path_or_bytes)
+    own_ctx = ctx is None
+    ctx = ctx or Context(0)
+    acc = None
+    try:
+        names, contig_len, _ = file_header(ctx, data)
+        acc = ctx.tally(len(contig_len))
+        f = {"flag_require": flag_require, "flag_exclude": flag_exclude, "min_mapq": min_mapq}
+        n = n_kept = 0
+
+        def deliver(sh, first, E, _names):
+            # the walk looks at the chain's exit only after this returns, and runs the window again
+            # with a larger halo when the chain leaves the resident bytes: look first, add after
+            # (api.depth's delivery), or a window that runs again would count twice
+            _, x = sh.chain_from(first, E)
+            blocks = sh.blocks()
+            seg = next((b[3] for b in blocks if b[5] & 1 and b[3] >= first), None)
+            last = seg is not None and E == seg or sh.file_offset + sh.n == sh.file_size and E == sh.flat_size
+            if not last and x >= sh.flat_size:
+                raise SparkBamError(SBH_E_NEED_HALO, "the chain leaves the halo")
+            sh.records_scan(first, E)
+            return [acc.add(sh, f)]
+
+        for (got,) in _iter_windows(data, deliver, window, ctx=ctx, reads_to_check=reads_to_check):
+            n, n_kept = n + got["n"], n_kept + got["n_kept"]
+        flag, ref = acc.counts()
+        return TallyResult(flag, ref, names, contig_len, n, n_kept)
+    finally:
+        if acc is not None:
+            acc.close()
+        if own_ctx:
+            ctx.close()
+
+
+def flagstat(path_or_bytes, flag_require=0, flag_exclude=0, min_mapq=0, window=None, ctx=None,
+             reads_to_check=DEFAULT_READS_TO_CHECK):
+    """What `samtools flagstat` reports, counted on the GPU: of the file's records with
+    (flag & flag_require) == flag_require, (flag & flag_exclude) == 0 and mapq >= min_mapq (default:
+    every record), how many are primary, secondary, supplementary, duplicate, mapped, paired, read1,
+    read2, properly paired, mapped with their mate, singletons, or have their mate on another
+    reference -- each split into QC-passed and QC-failed.  The file is walked `window` compressed
+    bytes at a time (iter_reads' walk); the counts do not depend on `window`.
+
+    Returns a tally.TallyResult: `.flag`, `.ref`, `.names`, `.lengths`, `.n_kept`,
+    `.flagstat_text()` (samtools flagstat's lines) and `.idxstats_text()` (samtools idxstats')."""
+    return _tally(path_or_bytes, flag_require, flag_exclude, min_mapq, window, ctx, reads_to_check)
+
+
+def idxstats(path_or_bytes, flag_require=0, flag_exclude=0, min_mapq=0, window=None, ctx=None,
+             reads_to_check=DEFAULT_READS_TO_CHECK):
+    """What `samtools idxstats` reports, counted on the GPU from the records themselves (no index
+    is read, and the file need not be sorted): per reference the records with flag 0x4 clear and
+    set, and in a last bin those without a reference.  The same pass, arguments and result as
+    flagstat."""
+    return _tally(path_or_bytes, flag_require, flag_exclude, min_mapq, window, ctx, reads_to_check)
+
+
 def _header_flat(ctx, data):
     """The BAM header's bytes (magic, text, reference dictionary: flat[0, header_end)), from the
     file's leading blocks inflated on the device."""

@@ -1,7 +1,7 @@
 // sbh_host.h -- the host side's private header: the context, the shard and the other structs
 // behind the opaque handles of include/sparkbam.h, the error helpers, and the host helpers that
 // one file's entry points (sbh_api.hip, api_check.hip, api_records.hip, and the output stages' calls
-// behind the kernels of bai.hip, sam.hip, bam_gather.hip, depth.hip, zdeflate.hip) borrow from another's.  Launchers are
+// behind the kernels of bai.hip, sam.hip, bam_gather.hip, depth.hip, tally.hip, zdeflate.hip) borrow from another's.  Launchers are
 // declared in sbh_internal.h; nothing here is seen by device code.
 #pragma once
 #include <algorithm>
@@ -318,6 +318,27 @@ struct sbh_depth {
   sbh_depth_sizes sz{};
   bool finished = false;
   ~sbh_depth() {
+    if (ctx) (void)hipSetDevice(ctx->device);
+    if (st) {
+      (void)hipStreamSynchronize(st);
+      (void)hipStreamDestroy(st);
+    }
+  }
+};
+
+// A tally accumulator (sbh_tally_create): flag counts and per-reference counts, owned by a context,
+// fed by any number of its shards.  Streams as sbh_depth's: the adds run on the adding shard's
+// stream and synchronise it before they return; reset and fetch run on the accumulator's own.
+struct sbh_tally {
+  sbh_ctx *ctx = nullptr;
+  hipStream_t st = nullptr;
+  int32_t n_ref = 0;
+  uint64_t words = 0;  // 2 SBH_TALLY_ROWS flag counters, then 2 (n_ref + 1) per-reference counters
+  // stage: bad row, past row, then `words` counters of the add under way (k_tally_rows); totals:
+  // `words` counters of every add that succeeded (k_tally_commit)
+  sbh::DBuf<unsigned long long> stage, totals;
+  sbh::DBuf<uint64_t> ranges;  // the device copy of the last add's row ranges
+  ~sbh_tally() {
     if (ctx) (void)hipSetDevice(ctx->device);
     if (st) {
       (void)hipStreamSynchronize(st);

@@ -339,6 +339,10 @@ constexpr uint32_t SORT_DESC = 55, SORT_OR = 56, SORT_AND = 57, SORT_END = 58;
 constexpr uint32_t DEPTH_BAD = SORT_END, DEPTH_PAST = DEPTH_BAD + 1, DEPTH_KEPT = DEPTH_BAD + 2;
 constexpr uint32_t DEPTH_UNPLACED = DEPTH_BAD + 3, DEPTH_COUNTED = DEPTH_BAD + 4, DEPTH_COV = DEPTH_BAD + 5;
 constexpr uint32_t DEPTH_END = DEPTH_BAD + 6;
+// tally add (sbh_records_tally_add), h_ctr only -- the device words are the accumulator's staging
+// words: first bad row, first row that only runs past the stream's end, kept rows (QC-pass, QC-fail)
+constexpr uint32_t H_TALLY_BAD = DEPTH_END, H_TALLY_PAST = H_TALLY_BAD + 1, H_TALLY_KEPT = H_TALLY_BAD + 2;
+constexpr uint32_t TALLY_END = H_TALLY_BAD + 4;
 // inflate status (launch_first_bad): the first block whose status is not INF_OK
 constexpr uint32_t FIRST_BAD = 100;
 // h_ctr only: that block's status (u32), fetched after the run's copy of [0, CTR_RUN_WORDS)
@@ -355,6 +359,7 @@ constexpr uint32_t CTR_CALL_END = 4 + ctr::FULL_NNZ * ctr::FULL_FLAGS + ctr::FUL
 static_assert(CTR_CALL_END <= CTR_TRUE_SPREAD && CTR_NEXT18 + 4 <= CTR_WORDS, "counter buffer layout");
 static_assert(ctr::FULL_END == CTR_CALL_END, "the full checker's counters end the per-call region");
 static_assert(ctr::DEPTH_END <= ctr::FIRST_BAD, "the depth counters end before the first bad block");
+static_assert(ctr::TALLY_END <= ctr::FIRST_BAD, "the tally add's mirror words end before the first bad block");
 // what the run template presets (the eager counters, FindRecordStart's best, the proof
 // counters, the first bad block) travels in the run's one copy each way ...
 static_assert(ctr::EAGER_END <= CTR_RUN_WORDS && ctr::FRS_BEST < CTR_RUN_WORDS &&

@@ -11,7 +11,7 @@ from .records import pack_ref_names, record_columns, record_filter
 from ._lib import (ORDER_COORDINATE, SBH_OK, SbhBaiSizes, SbhBamSizes, SbhBatchSplit, SbhBlock, SbhCheckOpts, SbhCheckResult, SbhDepthAddResult,
                    SbhDepthSizes, SbhRecordsOut,
                    SbhRecordsSizes, SbhSamSizes, SbhShardResult, SbhSplitBatchResult, SbhSplitRecordsResult,
-                   SbhStreamOpts, SbhStreamResult, SparkBamError, error_for, lib)
+                   SbhStreamOpts, SbhStreamResult, SbhTallyAddResult, SparkBamError, error_for, lib)
 
 
 # sbh_bai_run (include/sparkbam.h)
@@ -228,6 +228,57 @@ class Context:
         one per reference, ascending) of a file with n_ref references (sbh_depth_create): 4 bytes of
         HBM per position plus one per span.  count_del: D ops cover (samtools depth -J)."""
         return Depth(self, spans, n_ref, count_del)
+
+    def tally(self, n_ref):
+        """A flag-count and per-reference-count accumulator for a file with n_ref references
+        (sbh_tally_create): what samtools flagstat and idxstats report, counted on the GPU."""
+        return Tally(self, n_ref)
+
+
+class Tally:
+    """sbh_tally: scans of any number of this context's shards counted into one set of totals
+    (`add`); `counts` may be read between adds."""
+
+    def __init__(self, ctx, n_ref):
+        self.ctx = ctx
+        self.n_ref = int(n_ref)
+        h = C.c_void_p()
+        _check(ctx.h, lib().sbh_tally_create(ctx.h, self.n_ref, C.byref(h)))
+        self.h = h
+        ctx._shards.add(self)  # (closed with the context, before it)
+
+    def close(self):
+        if self.h:
+            if self.ctx.h:
+                lib().sbh_tally_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, shard, filter=None):
+        """The rows of the last scan on `shard` that `filter` keeps (records.record_filter's dict,
+        None: all), counted (sbh_records_tally_add).  Returns {"n": rows, "n_kept": kept rows}.  A
+        failed add leaves the accumulator as it was."""
+        f, keep = record_filter(filter)
+        r = SbhTallyAddResult()
+        _check(self.ctx.h, lib().sbh_records_tally_add(shard.h, self.h, C.byref(f) if f is not None else None,
+                                                       C.byref(r)))
+        del keep
+        return {"n": int(r.n), "n_kept": int(r.n_kept)}
+
+    def counts(self):
+        """(flag uint64[16, 2], ref uint64[n_ref + 1, 2]) of every add so far (sbh_tally_fetch)."""
+        flag, ref = np.zeros((16, 2), np.uint64), np.zeros((self.n_ref + 1, 2), np.uint64)
+        _check(self.ctx.h, lib().sbh_tally_fetch(self.h, _ptr(flag), 0, self.n_ref + 1, _ptr(ref)))
+        return flag, ref
+
+    def reset(self):
+        """Zero the totals (sbh_tally_reset)."""
+        _check(self.ctx.h, lib().sbh_tally_reset(self.h))
 
 
 class Depth:
