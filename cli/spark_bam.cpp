@@ -38,6 +38,7 @@
 
 #include "../include/sparkbam.h"
 #include "../spark-bam_amd/csrc/tally_core.h"  // flagstat's and idxstats' text (host functions only)
+#include "../spark-bam_amd/csrc/fastq_core.h"  // fastq's mode bits, the quality bound and the parts' order
 
 namespace {
 
@@ -263,6 +264,12 @@ struct Args {
   bool depth_all = false, count_del = false, bedgraph = false, has_exclude = false;
   std::string region;
   bool count_only = false;  // view -c: the number of records that pass -f / -F / -q, nothing else
+  // fastq, fasta: -1 / -2 / -0 the sinks of read 1, read 2 and the others (any of them: the output is split),
+  // -n no /1 /2 suffixes, -N always, -v the quality of a record without qualities; -F defaults to 0x900;
+  // --level, or a sink ending in .gz: BGZF members compressed from device memory
+  std::string out_part[3];
+  bool suffix_never = false, suffix_always = false, has_level = false;
+  int def_qual = 1;
 };
 
 // decimal or 0x hex
@@ -284,7 +291,7 @@ Args parse(int argc, char **argv) {
     throw Error(SBH_E_ARG,
                 "usage: spark-bam <command> [options] <bam>\n"
                 "  commands: compute-splits count-reads check-bam full-check index-blocks index-records index-bai\n"
-                "            check-blocks htsjdk-rewrite view sort depth flagstat idxstats\n"
+                "            check-blocks htsjdk-rewrite view sort depth flagstat idxstats fastq fasta\n"
                 "  view [-h|--header] [-o FILE] <bam>: the records as SAM text (-h: the header text first)\n"
                 "  view -b -o OUT [-f INT] [-F INT] [-q INT] [-r ROWS] [--level N] [--index-bai] [--sort] <bam>: the records with\n"
                 "       (flag & f) == f, (flag & F) == 0, mapq >= q and an index in ROWS (a-b,c-d: htsjdk-rewrite's -r)\n"
@@ -298,9 +305,16 @@ Args parse(int argc, char **argv) {
                 "  flagstat [-f INT] [-F INT] [-q INT] [-o FILE] <bam>: samtools flagstat's sixteen lines of the records that pass\n"
                 "  idxstats [-f INT] [-F INT] [-q INT] [-o FILE] <bam>: NAME LENGTH MAPPED UNMAPPED per reference, then the `*` line\n"
                 "       (samtools idxstats), counted from the records: no index is read, any order will do\n"
-                "  view -c [-f INT] [-F INT] [-q INT] <bam>: how many records pass (samtools view -c)");
+                "  view -c [-f INT] [-F INT] [-q INT] <bam>: how many records pass (samtools view -c)\n"
+                "  fastq [-o FILE] [-1 FILE] [-2 FILE] [-0 FILE] [-n|-N] [-f INT] [-F INT] [-q INT] [-v INT] [--level N] <bam>:\n"
+                "       the records as FASTQ (samtools fastq): @NAME[/1|/2], bases, +, qualities; reverse-strand reads\n"
+                "       reverse-complemented; -1 / -2 / -0: read 1, read 2 and the others to their own files (a class without\n"
+                "       one goes to -o, or nowhere); -n: no /1 /2 suffixes, -N: always; -v: the quality of reads without\n"
+                "       qualities (1); -F defaults to 0x900; --level N, or a FILE ending in .gz: BGZF-compressed on the GPU\n"
+                "  fasta: the same flags, >NAME and the bases only (samtools fasta)");
   a.cmd = argv[1];
   const bool rewrite = a.cmd == "htsjdk-rewrite", tally = a.cmd == "flagstat" || a.cmd == "idxstats";
+  const bool fq = a.cmd == "fastq" || a.cmd == "fasta";
   std::vector<std::string> pos;
   for (int i = 2; i < argc; ++i) {
     std::string t = argv[i];
@@ -328,6 +342,20 @@ Args parse(int argc, char **argv) {
     else if (tally && (t == "-q" || t == "--min-mapq")) a.min_mapq = (int)parse_int(next());
     else if (tally && (t == "-o" || t == "--output")) a.out = next();
     else if (tally && t.size() > 1 && t[0] == '-') throw Error(SBH_E_ARG, "usage: " + a.cmd + " [-f INT] [-F INT] [-q INT] [-o FILE] <bam> (unknown option " + t + ")");
+    else if (fq && (t == "-o" || t == "--output")) a.out = next();
+    else if (fq && t == "-1") a.out_part[0] = next();
+    else if (fq && t == "-2") a.out_part[1] = next();
+    else if (fq && t == "-0") a.out_part[2] = next();
+    else if (fq && t == "-n") a.suffix_never = true;
+    else if (fq && t == "-N") a.suffix_always = true;
+    else if (fq && (t == "-f" || t == "--require-flags")) a.flag_require = (uint32_t)parse_int(next());
+    else if (fq && (t == "-F" || t == "--exclude-flags")) { a.flag_exclude = (uint32_t)parse_int(next()); a.has_exclude = true; }
+    else if (fq && (t == "-q" || t == "--min-mapq")) a.min_mapq = (int)parse_int(next());
+    else if (fq && t == "-v") a.def_qual = (int)parse_int(next());
+    else if (fq && (t == "-l" || t == "--level")) { a.level = (int)parse_int(next()); a.has_level = true; }
+    else if (fq && t.size() > 1 && t[0] == '-')
+      throw Error(SBH_E_ARG, "usage: " + a.cmd + " [-o FILE] [-1 FILE] [-2 FILE] [-0 FILE] [-n|-N] [-f INT] [-F INT] [-q INT] [-v INT] "
+                                                 "[--level N] <bam> (unknown option " + t + ")");
     else if (a.cmd == "depth" && t == "-a") a.depth_all = true;
     else if (a.cmd == "depth" && (t == "-r" || t == "--region")) a.region = next();
     else if (a.cmd == "depth" && (t == "-f" || t == "--require-flags")) a.flag_require = (uint32_t)parse_int(next());
@@ -359,7 +387,9 @@ Args parse(int argc, char **argv) {
         (pos[0].size() > 1 && pos[0][0] == '-'))
       throw Error(SBH_E_ARG, "usage: view -c [-f INT] [-F INT] [-q INT] <bam>");
   }
-  if (pos.size() > 1 && a.cmd != "depth" && !tally) a.out = pos[1];
+  if (pos.size() > 1 && a.cmd != "depth" && !tally && !fq) a.out = pos[1];
+  if (fq && !a.has_exclude) a.flag_exclude = 0x900;  // SECONDARY, SUPPLEMENTARY: samtools fastq's
+  if (fq && a.suffix_never && a.suffix_always) throw Error(SBH_E_ARG, "usage: " + a.cmd + " takes -n or -N, not both");
   if (a.cmd == "depth" && !a.has_exclude) a.flag_exclude = 1796;  // UNMAP, SECONDARY, QCFAIL, DUP: samtools depth's
   if (a.cmd == "sort") {
     a.bam_out = a.sort = true;
@@ -1212,6 +1242,94 @@ int tally(const Args &a) {
   return 0;
 }
 
+// fastq, fasta: the records that pass -f / -F / -q as FASTQ or FASTA text, whole file resident as depth
+// holds it, rendered on the device (sbh_records_fastq_scan).  One sink (-o, or the terminal) takes the
+// text in file order; with any of -1 / -2 / -0 the text comes in three parts -- read 1, read 2, the
+// others -- and each part goes to its own sink, to -o without one, or nowhere.  A sink ending in
+// .gz, and every sink with --level, receives BGZF members compressed from device memory.
+int fastq(const Args &a) {
+  static_assert(SBH_FASTQ_SPLIT == sbh_fq::MODE_SPLIT && SBH_FASTQ_FASTA == sbh_fq::MODE_FASTA, "fastq_core.h restates the header's bits");
+  if (a.def_qual < 0 || a.def_qual > sbh_fq::QUAL_MAX) throw Error(SBH_E_ARG, a.cmd + ": -v takes 0.." + std::to_string(sbh_fq::QUAL_MAX));
+  const bool split = !a.out_part[0].empty() || !a.out_part[1].empty() || !a.out_part[2].empty();
+  const uint32_t mode = (a.cmd == "fasta" ? SBH_FASTQ_FASTA : 0u) | (split ? SBH_FASTQ_SPLIT : 0u) |
+                        (a.suffix_always ? SBH_FASTQ_SUFFIX_ALWAYS : a.suffix_never ? 0u : SBH_FASTQ_SUFFIX);
+  Loaded L(a.path);
+  uint64_t seg_end = L.flat;
+  for (const sbh_block &b : L.blocks)
+    if (b.flags & SBH_BLOCK_EMPTY) { seg_end = b.ustart; break; }
+  sbh_fastq_sizes sz{};
+  if (seg_end > L.hdr.end) {
+    uint64_t n = 0;
+    chk(sbh_check_eager(L.sh, L.hdr.end, seg_end, a.reads_to_check, nullptr, &n), "eager");
+    sbh_records_sizes rs{};
+    chk(sbh_records_scan(L.sh, L.hdr.end, seg_end, &rs), "records scan");
+    sbh_record_filter f{};
+    f.flag_require = a.flag_require;
+    f.flag_exclude = a.flag_exclude;
+    f.min_mapq = a.min_mapq;
+    chk(sbh_records_fastq_scan(L.sh, &f, mode, a.def_qual, &sz), "fastq scan");
+  }
+  // the sink of each part (a path; "": the terminal), a sink named twice opened once
+  struct Sink {
+    std::string path;
+    FILE *f = nullptr;
+    bool gz = false;
+  };
+  std::vector<Sink> sinks;
+  int of_part[sbh_fq::PARTS] = {-1, -1, -1};
+  auto sink_of = [&](const std::string &path) {
+    for (size_t k = 0; k < sinks.size(); ++k)
+      if (sinks[k].path == path) return (int)k;
+    Sink s;
+    s.path = path;
+    s.gz = a.has_level || (path.size() > 3 && path.compare(path.size() - 3, 3, ".gz") == 0);
+    s.f = path.empty() ? stdout : fopen(path.c_str(), "wb");
+    if (!s.f) throw Error(SBH_E_ARG, "cannot write " + path);
+    sinks.push_back(s);
+    return (int)sinks.size() - 1;
+  };
+  if (!split) of_part[0] = sink_of(a.out);
+  else
+    for (uint32_t p = 0; p < sbh_fq::PARTS; ++p)
+      if (!a.out_part[p].empty()) of_part[p] = sink_of(a.out_part[p]);
+      else if (!a.out.empty()) of_part[p] = sink_of(a.out);
+  const char *dev = (const char *)sbh_records_fastq_device_ptr(L.sh);
+  std::vector<char> text;
+  bool plain = false;
+  for (uint32_t p = 0; p < sbh_fq::PARTS; ++p) plain |= of_part[p] >= 0 && !sinks[of_part[p]].gz && sz.part_bytes[p];
+  if (plain) {
+    text.resize(sz.text_bytes);
+    chk(sbh_records_fastq_fetch(L.sh, text.data(), nullptr, nullptr), "fastq fetch");
+  }
+  bool ok = true;
+  uint64_t at = 0;
+  std::vector<uint8_t> comp;
+  for (uint32_t p = 0; p < sbh_fq::PARTS; ++p) {
+    const uint64_t nb = sz.part_bytes[p];
+    if (nb && of_part[p] >= 0) {
+      Sink &s = sinks[of_part[p]];
+      if (!s.gz) {
+        ok = ok && fwrite(text.data() + at, 1, nb, s.f) == nb;
+      } else {
+        comp.resize(sbh_bgzf_compress_bound(nb));
+        uint64_t size = 0, members = 0;
+        chk(sbh_bgzf_compress_level(g_ctx, dev + at, nb, 1, a.level, comp.data(), comp.size(), &size, &members, nullptr),
+            "bgzf compress");
+        ok = ok && size >= 28 && fwrite(comp.data(), 1, size - 28, s.f) == size - 28;  // (its EOF member comes once, below)
+      }
+    }
+    at += nb;
+  }
+  static const uint8_t eof_member[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  for (Sink &s : sinks) {
+    if (s.gz) ok = ok && fwrite(eof_member, 1, 28, s.f) == 28;
+    ok = ok && fflush(s.f) == 0;
+    if (s.f != stdout) fclose(s.f);
+  }
+  if (!ok) throw Error(SBH_E_ARG, "short write");
+  return 0;
+}
+
 // HTSJDKRewrite (cli/.../rewrite/HTSJDKRewrite.scala:40-92): the BAM's uncompressed stream --
 // header, then every record, or only the records whose index is in -r (:48-58) -- re-cut into
 // 65498-byte BGZF members on the GPU (sbh_bgzf_compress) plus the EOF member; -b / -i then
@@ -1422,6 +1540,7 @@ int main(int argc, char **argv) {
     else if (a.cmd == "view" || a.cmd == "sort") rc = view(a);
     else if (a.cmd == "depth") rc = depth(a);
     else if (a.cmd == "flagstat" || a.cmd == "idxstats") rc = tally(a);
+    else if (a.cmd == "fastq" || a.cmd == "fasta") rc = fastq(a);
     else throw Error(SBH_E_ARG, "unknown command " + a.cmd);
     sbh_ctx_destroy(g_ctx);
     return rc;

@@ -809,6 +809,53 @@ int sbh_tally_add_host(const uint8_t *flat, uint64_t flat_size, const uint64_t *
                        const sbh_record_filter *filter, int32_t n_ref, uint64_t *flag, uint64_t *ref,
                        sbh_tally_add_result *out, uint64_t *bad_row);
 
+/* ---- FASTQ / FASTA text -------------------------------------------------------------------
+ * What samtools fastq and samtools fasta write, rendered on the device from the flat bytes and
+ * record starts of a scan (csrc/fastq_core.h holds the definition for device and host).  A row the
+ * filter keeps (NULL: every row) becomes
+ *     @NAME[/1|/2]\nSEQ\n+\nQUAL\n        or, with SBH_FASTQ_FASTA,        >NAME[/1|/2]\nSEQ\n
+ * NAME: the name bytes up to the first NUL, as SAM text's QNAME.  Suffix: with SBH_FASTQ_SUFFIX,
+ * /1 when flag & 0x1 and (flag & 0xC0) == 0x40, /2 when flag & 0x1 and (flag & 0xC0) == 0x80, else
+ * none; SBH_FASTQ_SUFFIX_ALWAYS drops the 0x1 condition (and wins over SBH_FASTQ_SUFFIX); neither
+ * bit: never a suffix.  SEQ: the "=ACMGRSVTWYHKDBN" letters, reverse-complemented when flag & 0x10
+ * (A<>T C<>G M<>K R<>Y V<>B H<>D; = S W N stay).  QUAL: min(q, 93) + 33 per base, reversed when
+ * flag & 0x10; when the first quality byte is 0xFF every byte is def_qual + 33 (samtools fastq -v,
+ * 1 by default there).  l_seq == 0 gives empty SEQ and QUAL lines.
+ * SBH_FASTQ_SPLIT: a kept row's class is 1 or 2 by the /1 and /2 conditions (without the 0x1
+ * condition under SBH_FASTQ_SUFFIX_ALWAYS), else 0, and the text is three parts one after another
+ * -- the class 1 lines, the class 2 lines, the class 0 lines, each in row order; part_bytes and
+ * part_rows are in that order.  Without the bit: one part in row order (part 0; parts 1 and 2
+ * empty).  samtools' -s singleton file needs reads collated by name and is not offered.
+ * rows = the rows of the last valid scan on this shard, in their order, as the BAM stream takes them
+ * (decode == 0 is enough); every row, kept or not, is validated as there.  The scan call leaves the
+ * scan's rows, columns, SAM text and BAM stream alone and synchronises the shard's stream before it
+ * returns, so the context-level compress call may follow directly on the device pointer (NULL
+ * without a valid FASTQ scan); a new scan or a load of the shard invalidates the text.  The fetch
+ * copies out what is asked for (any pointer may be NULL): the text, rec_off (n_kept + 1: where each
+ * line begins, in the text's order, then text_bytes) and rows (n_kept: the scan row of each line).
+ * Errors: SBH_E_STATE without a valid scan; SBH_E_ARG for unknown mode bits, def_qual outside
+ * [0, 93] or a bad filter; SBH_E_BAD_RECORD {row} for the first invalid row, SBH_E_NEED_HALO instead
+ * when that row merely runs past an open shard end.  n == 0 or n_kept == 0 gives text_bytes = 0 and
+ * rec_off = [0]. */
+#define SBH_FASTQ_FASTA 1u
+#define SBH_FASTQ_SUFFIX 2u
+#define SBH_FASTQ_SUFFIX_ALWAYS 4u
+#define SBH_FASTQ_SPLIT 8u
+typedef struct { uint64_t n, n_kept, text_bytes, part_bytes[3], part_rows[3]; } sbh_fastq_sizes;
+int sbh_records_fastq_scan(sbh_shard *sh, const sbh_record_filter *filter /* NULL: keep all */,
+                           uint32_t mode, int32_t def_qual, sbh_fastq_sizes *out);
+const void *sbh_records_fastq_device_ptr(sbh_shard *sh);
+int sbh_records_fastq_fetch(sbh_shard *sh, char *text /*[text_bytes]*/, uint64_t *rec_off /*[n_kept+1]*/,
+                            uint64_t *rows /*[n_kept]*/);
+/* HOST ONLY, no context, no GPU: the same text for the records at starts[] of a flat BAM stream.
+ * rec_off (room for n + 1) and rows (room for n) may be NULL; text == NULL: sizes only.
+ * SBH_E_BAD_RECORD with *bad_row = the first invalid row, kept or not; SBH_E_ARG for bad arguments
+ * as above or when text_cap < text_bytes (*sizes is set then). */
+int sbh_fastq_render_host(const uint8_t *flat, uint64_t flat_size, const uint64_t *starts, uint64_t n,
+                          const sbh_record_filter *filter, uint32_t mode, int32_t def_qual,
+                          char *text, uint64_t text_cap, uint64_t *rec_off, uint64_t *rows,
+                          sbh_fastq_sizes *sizes, uint64_t *bad_row);
+
 /* ---- BGZF writer -------------------------------------------------
  * The block compressor behind HTSJDKRewrite (cli/src/main/scala/org/hammerlab/bam/rewrite/
  * HTSJDKRewrite.scala:62-67: SAMFileWriterFactory.makeBAMWriter -> htsjdk

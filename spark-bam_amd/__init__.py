@@ -15,6 +15,7 @@ Import name: ``spark_bam_amd`` (the directory name contains a hyphen, so load it
   sort:   sort_bam (the records coordinate-sorted on the GPU), bam_sort_host
   depth:  depth (per-base coverage accumulated and scanned on the GPU), depth_host
   counts: flagstat, idxstats (flag and per-reference read counts, one pass on the GPU), tally_host
+  reads:  fastq (the records as FASTQ / FASTA text, rendered on the GPU), fastq_host
 """
 from ._lib import (BLOCK_EMPTY, BLOCK_TRUNCATED, FULL_FLAGS_MASK, FULL_N_SHIFT,  # noqa: F401
                    FULL_SUCCESS, FULL_UNKNOWN, HeaderParseException, HeaderSearchFailedException,
@@ -24,6 +25,8 @@ from .api import (FLAG_NAMES, htsjdk_rewrite, Header, Metadata, Pos, Split, bam_
                   file_splits, flagstat, full_check, idxstats, load_bam_count, load_reads, load_splits_and_reads,
                   parse_bam_header, sort_bam, view, view_bam)
 from .tally import TallyResult, flagstat_text, idxstats_text, tally_host  # noqa: F401
+from .fastq import FastqResult, fastq_host, fastq_mode  # noqa: F401
+from .api import fastq  # noqa: F401,E402  (after the submodule of the same name: the function is what the package exports)
 from .records import Reads, bam_gather_host, bam_header_set_so, bam_sort_host, sam_text_host  # noqa: F401
 from .coverage import DepthResult, depth_bedgraph, depth_host, depth_text  # noqa: F401
 from .checkers import GpuWindow, WindowedEagerChecker, WindowedFullChecker  # noqa: F401
@@ -43,4 +46,5 @@ __all__ = [
     "sort_bam", "bam_sort_host", "bam_header_set_so",
     "depth", "Depth", "DepthResult", "depth_host", "depth_text", "depth_bedgraph",
     "flagstat", "idxstats", "Tally", "TallyResult", "tally_host", "flagstat_text", "idxstats_text",
+    "fastq", "fastq_host", "fastq_mode", "FastqResult",
 ]

@@ -53,8 +53,10 @@ EXPORTS = [
     "sbh_depth_finish_host",
     "sbh_tally_create", "sbh_tally_destroy", "sbh_tally_reset", "sbh_records_tally_add", "sbh_tally_fetch",
     "sbh_tally_add_host",
+    "sbh_records_fastq_scan", "sbh_records_fastq_device_ptr", "sbh_records_fastq_fetch", "sbh_fastq_render_host",
 ]
 ORDER_SCAN, ORDER_COORDINATE = 0, 1  # SBH_ORDER_*
+FASTQ_FASTA, FASTQ_SUFFIX, FASTQ_SUFFIX_ALWAYS, FASTQ_SPLIT = 1, 2, 4, 8  # SBH_FASTQ_*
 LEVEL_HTSJDK, LEVEL_FAST = 5, -1  # sbh_bgzf_compress_level: htsjdk's zlib level 5 / this library's own coder
 
 
@@ -154,6 +156,11 @@ class SbhDepthSizes(C.Structure):
 
 class SbhTallyAddResult(C.Structure):
     _fields_ = [("n", C.c_uint64), ("n_kept", C.c_uint64)]
+
+
+class SbhFastqSizes(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("n_kept", C.c_uint64), ("text_bytes", C.c_uint64), ("part_bytes", C.c_uint64 * 3),
+                ("part_rows", C.c_uint64 * 3)]
 
 
 class SbhRecordsOut(C.Structure):  # host buffers (sbh_records_out); NULL = not copied
@@ -309,6 +316,10 @@ def lib():
         "sbh_records_tally_add": [P, P, C.POINTER(SbhRecordFilter), C.POINTER(SbhTallyAddResult)],
         "sbh_tally_fetch": [P, P, U64, U64, P],
         "sbh_tally_add_host": [P, U64, P, U64, C.POINTER(SbhRecordFilter), I32, P, P, C.POINTER(SbhTallyAddResult), PU64],
+        "sbh_records_fastq_scan": [P, C.POINTER(SbhRecordFilter), U32, I32, C.POINTER(SbhFastqSizes)],
+        "sbh_records_fastq_fetch": [P, P, P, P],
+        "sbh_fastq_render_host": [P, U64, P, U64, C.POINTER(SbhRecordFilter), U32, I32, P, U64, P, P,
+                                  C.POINTER(SbhFastqSizes), PU64],
         "sbh_bgzf_compress": [P, P, U64, I32, P, U64, PU64, PU64, C.POINTER(C.c_float)],
         "sbh_bgzf_compress_level": [P, P, U64, I32, I32, P, U64, PU64, PU64, C.POINTER(C.c_float)],
     }
@@ -332,7 +343,8 @@ def lib():
     L.sbh_last_error_detail.restype = I32
     L.sbh_version.argtypes = []
     L.sbh_version.restype = C.c_char_p
-    for name in ("sbh_shard_comp_device_ptr", "sbh_flat_device_ptr", "sbh_records_bam_device_ptr"):
+    for name in ("sbh_shard_comp_device_ptr", "sbh_flat_device_ptr", "sbh_records_bam_device_ptr",
+                 "sbh_records_fastq_device_ptr"):
         getattr(L, name).argtypes = [P]
         getattr(L, name).restype = P
     _lib = L

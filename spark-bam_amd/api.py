@@ -311,6 +311,7 @@ def view(path_or_bytes, header=False, out=None, window=None, ctx=None, reads_to_
 
 BGZF_PAYLOAD = 65498  # uncompressed bytes per member of the writer (htsjdk BlockCompressedOutputStream)
 BGZF_EOF_BYTES = 28
+BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")  # the empty member that ends a file
 
 
 def view_bam(path_or_bytes, out=None, flag_require=0, flag_exclude=0, min_mapq=0, rows=None, intervals=None,
@@ -554,6 +555,100 @@ def idxstats(path_or_bytes, flag_require=0, flag_exclude=0, min_mapq=0, window=N
     set, and in a last bin those without a reference.  The same pass, arguments and result as
     flagstat."""
     return _tally(path_or_bytes, flag_require, flag_exclude, min_mapq, window, ctx, reads_to_check)
+
+
+def fastq(path_or_bytes, out=None, out1=None, out2=None, out0=None, fasta=False, suffix="auto", flag_require=0,
+          flag_exclude=0x900, min_mapq=0, def_qual=1, level=None, window=None, ctx=None,
+          reads_to_check=DEFAULT_READS_TO_CHECK):
+    """The file's records as FASTQ text -- FASTA with `fasta` -- as `samtools fastq` / `samtools
+    fasta` write them, rendered on the GPU (Shard.records_fastq) a window at a time with iter_reads'
+    windowing: `@NAME[/1|/2]`, the bases (reverse-complemented for a reverse-strand read), `+`, the
+    qualities as min(q, 93) + 33 (reversed likewise; def_qual + 33 throughout when a record has
+    none).  A record is written when (flag & flag_require) == flag_require, (flag & flag_exclude) ==
+    0 (default 0x900: secondary and supplementary, samtools') and mapq >= min_mapq.  suffix: "auto"
+    (/1 and /2 on paired reads), "never" (-n), "always" (-N).
+
+    Sinks are paths or binary file objects.  `out` alone: one stream in file order.  Any of `out1`,
+    `out2`, `out0`: read 1, read 2 and the other reads go to their own sinks; a class without one
+    goes to `out`, or nowhere without `out`.  samtools' -s singleton file is not offered.  With
+    `level` (Context.bgzf_compress's levels), or for a path ending in .gz (level 5 then), a sink
+    receives BGZF members -- a valid multi-member gzip -- compressed from device memory, closed by
+    one EOF member: the text does not come to the host uncompressed.
+
+    Returns a fastq.FastqResult: .n, .n_kept, .part_bytes and .part_rows (uncompressed text bytes
+    and records per class in the order read 1, read 2, others; all in entry 0 when not split), and
+    .text (the text as bytes when no sink at all was given)."""
+    from .fastq import FastqResult, fastq_mode
+    split = any(s is not None for s in (out1, out2, out0))
+    mode = fastq_mode(fasta, suffix, split)
+    data = _file_array(path_or_bytes)
+    own_ctx = ctx is None
+    ctx = ctx or Context(0)
+    f = {"flag_require": flag_require, "flag_exclude": flag_exclude, "min_mapq": min_mapq}
+    wanted = [s if s is not None else out for s in (out1, out2, out0)] if split else [out, None, None]
+    collect = not split and out is None
+    opened, sinks = {}, []  # a sink given twice is opened once: (file object, compression level or None)
+    try:
+        for s in wanted:
+            if s is None:
+                sinks.append(None)
+                continue
+            key = os.fspath(s) if isinstance(s, (str, os.PathLike)) else id(s)
+            if key not in opened:
+                is_path = isinstance(s, (str, os.PathLike))
+                name = str(key) if is_path else str(getattr(s, "name", ""))
+                lv = level if level is not None else (5 if name.endswith(".gz") else None)
+                opened[key] = (open(s, "wb") if is_path else s, lv, is_path)
+            sinks.append(opened[key])
+        parts = []
+        totals = {"n": 0, "n_kept": 0, "part_bytes": [0, 0, 0], "part_rows": [0, 0, 0]}
+        plain = collect or any(lv is None for _, lv, _ in opened.values())  # some text comes to the host as it is
+
+        def deliver(sh, first, E, _names):
+            # the walk looks at the chain's exit only after this returns, and runs the window again
+            # with a larger halo when the chain leaves the resident bytes: look first, render after
+            # (api.depth's delivery), or a window that runs again would be written twice
+            _, x = sh.chain_from(first, E)
+            blocks = sh.blocks()
+            seg = next((b[3] for b in blocks if b[5] & 1 and b[3] >= first), None)
+            last = seg is not None and E == seg or sh.file_offset + sh.n == sh.file_size and E == sh.flat_size
+            if not last and x >= sh.flat_size:
+                raise SparkBamError(SBH_E_NEED_HALO, "the chain leaves the halo")
+            sh.records_scan(first, E)
+            got = sh.records_fastq(f, mode=mode, def_qual=def_qual, want_text=plain)
+            text = got[0] if plain else None
+            sz = sh.fastq_sizes
+            at = 0
+            for k in range(3):
+                nb = sz["part_bytes"][k]
+                if nb and sinks[k] is not None:
+                    fh, lv, _ = sinks[k]
+                    if lv is None:
+                        fh.write(text[at:at + nb].data)
+                    else:
+                        fh.write(ctx.bgzf_compress(sh.fastq_ptr() + at, nb, level=lv)[0][:-BGZF_EOF_BYTES].data)
+                elif nb and collect:
+                    parts.append(text[at:at + nb].tobytes())
+                at += nb
+            return [sz]
+
+        for (sz,) in _iter_windows(data, deliver, window, ctx=ctx, reads_to_check=reads_to_check):
+            totals["n"] += sz["n"]
+            totals["n_kept"] += sz["n_kept"]
+            for k in range(3):
+                totals["part_bytes"][k] += sz["part_bytes"][k]
+                totals["part_rows"][k] += sz["part_rows"][k]
+        for fh, lv, _ in opened.values():
+            if lv is not None:
+                fh.write(BGZF_EOF)
+        return FastqResult(totals["n"], totals["n_kept"], totals["part_bytes"], totals["part_rows"],
+                           b"".join(parts) if collect else None)
+    finally:
+        for fh, _, is_path in opened.values():
+            if is_path:
+                fh.close()
+        if own_ctx:
+            ctx.close()
 
 
 def _header_flat(ctx, data):

@@ -25,6 +25,7 @@ int sbh_records_scan(sbh_shard *sh, uint64_t first, uint64_t end_flat, sbh_recor
   R.valid = false;
   sh->sam.valid = false;
   sh->bam.valid = false;
+  sh->fq.valid = false;
   const uint64_t total = seg_end_of(sh, first);
   const uint64_t E = std::min(std::min(end_flat, sh->utotal), total);
   uint64_t n = 0;
@@ -55,6 +56,7 @@ int sbh_split_records(sbh_shard *sh, uint64_t start, uint64_t end, int32_t k, in
   R.valid = R.decoded = false;
   sh->sam.valid = false;
   sh->bam.valid = false;
+  sh->fq.valid = false;
   uint64_t b = 0;
   rc = sbh_find_block_start(sh, start, k, &b);
   if (rc) return rc;
@@ -150,6 +152,7 @@ int sbh_split_records_batch(sbh_shard *sh, const uint64_t *starts, const uint64_
   R.valid = R.decoded = false;
   sh->sam.valid = false;
   sh->bam.valid = false;
+  sh->fq.valid = false;
   // the chain starts at the first split whose FindBlockStart succeeds; a split before it keeps
   // its own failure (HeaderSearchFailedException(path, start, positionsAttempted))
   uint64_t j0 = 0, b = 0;
@@ -403,6 +406,7 @@ int sbh_records_scan_regions(sbh_shard *sh, const uint64_t *chunk_begin, const u
   R.valid = false;
   sh->sam.valid = false;
   sh->bam.valid = false;
+  sh->fq.valid = false;
   std::vector<uint64_t> cn(n_chunks, 0), cfirst(n_chunks, 0), cE(n_chunks, 0), ctot(n_chunks, 0);
   std::vector<int32_t> can(n_chunks, 0);
   uint64_t n = 0;

@@ -77,6 +77,25 @@ SBH_HD inline Fixed fixed_of(const uint8_t *r) {
   return f;
 }
 
+// QNAME: the l_name name bytes up to the first NUL (may be empty).  Sixteen bytes a step, each read
+// at an index clamped below l_name: the reads of a step do not depend on one another, so a lane
+// waits for memory once per step and not once per byte.
+SBH_HD inline uint32_t qname_len(const uint8_t *name, uint32_t l_name) {
+  for (uint32_t base = 0; base < l_name; base += 16) {
+    uint32_t nul = 0;
+    for (uint32_t j = 0; j < 16; ++j) {
+      const uint32_t k = base + j < l_name ? base + j : l_name - 1;
+      nul |= (uint32_t)(name[k] == 0) << j;
+    }
+    if (nul) {
+      uint32_t j = 0;
+      while (!((nul >> j) & 1u)) ++j;
+      return base + j < l_name ? base + j : l_name;
+    }
+  }
+  return l_name;
+}
+
 // reference names packed: name k = names[off[k] .. off[k + 1])
 struct Refs {
   const char *names;
@@ -281,8 +300,7 @@ inline uint64_t render_record(const uint8_t *r, uint64_t rec_bytes, const Refs &
     else if (k == REF_EQ) ch('=');
     else bytes(R.names + R.off[k], R.off[k + 1] - R.off[k]);
   };
-  uint32_t name_len = 0;
-  while (name_len < f.l_name && name[name_len]) ++name_len;
+  const uint32_t name_len = qname_len(name, f.l_name);
   bytes(name, name_len);
   ch('\t');
   bytes(num, put_dec(num, f.flag));

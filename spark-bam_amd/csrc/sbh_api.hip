@@ -93,6 +93,7 @@ void sbh::resident_changed(sbh_shard *sh, uint64_t file_off, uint64_t n) {
   sh->bai.valid = false;
   sh->sam.valid = false;
   sh->bam.valid = false;
+  sh->fq.valid = false;
   sh->ncand = 0;
   sh->scan_from = ~0ull;
   sh->hb.clear();

@@ -1,7 +1,7 @@
 // sbh_host.h -- the host side's private header: the context, the shard and the other structs
 // behind the opaque handles of include/sparkbam.h, the error helpers, and the host helpers that
 // one file's entry points (sbh_api.hip, api_check.hip, api_records.hip, and the output stages' calls
-// behind the kernels of bai.hip, sam.hip, bam_gather.hip, depth.hip, tally.hip, zdeflate.hip) borrow from another's.  Launchers are
+// behind the kernels of bai.hip, sam.hip, bam_gather.hip, depth.hip, tally.hip, fastq.hip, zdeflate.hip) borrow from another's.  Launchers are
 // declared in sbh_internal.h; nothing here is seen by device code.
 #pragma once
 #include <algorithm>
@@ -238,6 +238,17 @@ struct sbh_shard {
   struct Depth {
     sbh::DBuf<uint64_t> keep, ranges;
   } dep;
+  // FASTQ / FASTA text of the last scan's selected rows (sbh_records_fastq_scan / fetch): per part of
+  // the text (fastq_core.h) the rows' line lengths and keep flags with their prefixes, the class byte,
+  // each row's offset, the lines' offsets and rows in layout order, the parts' totals, the device copy
+  // of the row ranges, the text
+  struct Fastq {
+    sbh::DBuf<uint64_t> len, keep, lpre, kpre, off, rec_off, rows, sums, ranges;
+    sbh::DBuf<uint8_t> cls;
+    sbh::DBuf<char> text;
+    sbh_fastq_sizes sz{};
+    bool valid = false;
+  } fq;
   std::vector<int32_t> h_ctg;  // host copy of the contig lengths (sbh_set_contigs)
   // batched splits (sbh_split_starts) and check-bam truth (sbh_check_records)
   sbh::DBuf<uint64_t> sp_start, sp_end, sp_first, sp_E, sp_vpos;

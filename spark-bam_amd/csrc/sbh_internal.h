@@ -343,6 +343,10 @@ constexpr uint32_t DEPTH_END = DEPTH_BAD + 6;
 // words: first bad row, first row that only runs past the stream's end, kept rows (QC-pass, QC-fail)
 constexpr uint32_t H_TALLY_BAD = DEPTH_END, H_TALLY_PAST = H_TALLY_BAD + 1, H_TALLY_KEPT = H_TALLY_BAD + 2;
 constexpr uint32_t TALLY_END = H_TALLY_BAD + 4;
+// FASTQ scan (sbh_records_fastq_scan): first invalid row, first row that only runs past the stream's
+// end; h_ctr only: the parts' bytes (3 words), then their lines (3 words)
+constexpr uint32_t FASTQ_BAD = TALLY_END, FASTQ_PAST = FASTQ_BAD + 1, H_FASTQ_SUMS = FASTQ_BAD + 2;
+constexpr uint32_t FASTQ_END = H_FASTQ_SUMS + 6;
 // inflate status (launch_first_bad): the first block whose status is not INF_OK
 constexpr uint32_t FIRST_BAD = 100;
 // h_ctr only: that block's status (u32), fetched after the run's copy of [0, CTR_RUN_WORDS)
@@ -360,6 +364,7 @@ static_assert(CTR_CALL_END <= CTR_TRUE_SPREAD && CTR_NEXT18 + 4 <= CTR_WORDS, "c
 static_assert(ctr::FULL_END == CTR_CALL_END, "the full checker's counters end the per-call region");
 static_assert(ctr::DEPTH_END <= ctr::FIRST_BAD, "the depth counters end before the first bad block");
 static_assert(ctr::TALLY_END <= ctr::FIRST_BAD, "the tally add's mirror words end before the first bad block");
+static_assert(ctr::FASTQ_END <= ctr::FIRST_BAD, "the FASTQ scan's words end before the first bad block");
 // what the run template presets (the eager counters, FindRecordStart's best, the proof
 // counters, the first bad block) travels in the run's one copy each way ...
 static_assert(ctr::EAGER_END <= CTR_RUN_WORDS && ctr::FRS_BEST < CTR_RUN_WORDS &&

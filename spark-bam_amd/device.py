@@ -9,7 +9,7 @@ from .coverage import DEPTH_DEL, DEPTH_RUN_DTYPE, span_array
 from .records import pack_ref_names, record_columns, record_filter
 
 from ._lib import (ORDER_COORDINATE, SBH_OK, SbhBaiSizes, SbhBamSizes, SbhBatchSplit, SbhBlock, SbhCheckOpts, SbhCheckResult, SbhDepthAddResult,
-                   SbhDepthSizes, SbhRecordsOut,
+                   SbhDepthSizes, SbhFastqSizes, SbhRecordsOut,
                    SbhRecordsSizes, SbhSamSizes, SbhShardResult, SbhSplitBatchResult, SbhSplitRecordsResult,
                    SbhStreamOpts, SbhStreamResult, SbhTallyAddResult, SparkBamError, error_for, lib)
 
@@ -784,6 +784,37 @@ class Shard:
         if out.size:
             self._c(lib().sbh_records_bam_read(self.h, int(begin), int(out.size), _ptr(out)))
         return out
+
+    def records_fastq(self, filter=None, fasta=False, suffix="auto", split=False, def_qual=1, want_text=True, mode=None):
+        """The rows of the last scan on this shard that `filter` keeps (records.record_filter's dict,
+        None: all) as FASTQ text -- FASTA with `fasta` -- rendered on the GPU (sbh_records_fastq_scan
+        + sbh_records_fastq_fetch; the format and `suffix`, `split`, `def_qual` in fastq.fastq_mode
+        and include/sparkbam.h).  Returns (text uint8, rec_off uint64 [n_kept + 1], rows uint64
+        [n_kept]): line k of the text is text[rec_off[k]:rec_off[k + 1]] and came from scan row
+        rows[k].  `self.fastq_sizes`: n, n_kept, text_bytes, part_bytes, part_rows.  want_text=False
+        returns None and leaves the text on the device: fastq_ptr() (+ an offset) is what
+        Context.bgzf_compress takes."""
+        from .fastq import fastq_mode, sizes_dict
+        mode = fastq_mode(fasta, suffix, split) if mode is None else int(mode)
+        f, keep = record_filter(filter)
+        sz = SbhFastqSizes()
+        self._c(lib().sbh_records_fastq_scan(self.h, C.byref(f) if f is not None else None, mode, int(def_qual),
+                                             C.byref(sz)))
+        del keep
+        self.fastq_sizes = sizes_dict(sz)
+        if not want_text:
+            return None
+        text = np.empty(sz.text_bytes, dtype=np.uint8)
+        rec_off = np.zeros(sz.n_kept + 1, dtype=np.uint64)
+        rows = np.zeros(sz.n_kept, dtype=np.uint64)
+        self._c(lib().sbh_records_fastq_fetch(self.h, _ptr(text) if text.size else None, _ptr(rec_off),
+                                              _ptr(rows) if rows.size else None))
+        return text, rec_off, rows
+
+    def fastq_ptr(self):
+        """Device pointer of the last records_fastq text (sbh_records_fastq_device_ptr; None when a
+        new scan or load has invalidated it)."""
+        return lib().sbh_records_fastq_device_ptr(self.h)
 
     def bai_scan(self, first_flat, end_flat):
         """The BAI runs and linear-index minima of the records from first_flat while the start
