@@ -263,6 +263,11 @@ struct Args {
   // depth: -a every position of the spans, -r REGION, -J D ops cover, --bedgraph; -F defaults to 1796
   bool depth_all = false, count_del = false, bedgraph = false, has_exclude = false;
   std::string region;
+  // pileup, consensus: -a / -r / -f / -F / -q as depth's, -H a header line, -Q the least base quality a
+  // letter needs, -d / -c consensus's least depth and percentage, --max-positions the accumulator's budget
+  bool pile_header = false;
+  int min_baseq = 0, min_depth = 1, call_pct = 75;
+  long long max_positions = -1;  // (-1: sbh_pileup_budget's)
   bool count_only = false;  // view -c: the number of records that pass -f / -F / -q, nothing else
   // fastq, fasta: -1 / -2 / -0 the sinks of read 1, read 2 and the others (any of them: the output is split),
   // -n no /1 /2 suffixes, -N always, -v the quality of a record without qualities; -F defaults to 0x900;
@@ -291,7 +296,7 @@ Args parse(int argc, char **argv) {
     throw Error(SBH_E_ARG,
                 "usage: spark-bam <command> [options] <bam>\n"
                 "  commands: compute-splits count-reads check-bam full-check index-blocks index-records index-bai\n"
-                "            check-blocks htsjdk-rewrite view sort depth flagstat idxstats fastq fasta\n"
+                "            check-blocks htsjdk-rewrite view sort depth pileup consensus flagstat idxstats fastq fasta\n"
                 "  view [-h|--header] [-o FILE] <bam>: the records as SAM text (-h: the header text first)\n"
                 "  view -b -o OUT [-f INT] [-F INT] [-q INT] [-r ROWS] [--level N] [--index-bai] [--sort] <bam>: the records with\n"
                 "       (flag & f) == f, (flag & F) == 0, mapq >= q and an index in ROWS (a-b,c-d: htsjdk-rewrite's -r)\n"
@@ -302,6 +307,13 @@ Args parse(int argc, char **argv) {
                 "       RNAME POS DEPTH lines (samtools depth; -a: zero-depth positions too) or, with --bedgraph, RNAME BEG END\n"
                 "       DEPTH runs (genomecov -bg); REGION is NAME or NAME:BEG-END (1-based, inclusive); -F defaults to 1796;\n"
                 "       -J: deletions count\n"
+                "  pileup [-a] [-H] [-r REGION] [-f INT] [-F INT] [-q INT] [-Q INT] [-o FILE] <bam>: per-base allele counts as\n"
+                "       NAME POS A C G T N DEL INS LOWQ lines (POS 1-based) for every position any kept read touches (-a: every\n"
+                "       position of the region; -H: a header line first); -Q: bases of lower quality count as LOWQ (0; samtools\n"
+                "       mpileup's is 13); -F defaults to 1796; 33 bytes of device memory per position: without -r a genome that\n"
+                "       does not fit is refused (--max-positions N overrides the budget)\n"
+                "  consensus [-r REGION] [-f INT] [-F INT] [-q INT] [-Q INT] [-d MIN_DEPTH] [-c PCT] [-o FILE] <bam>: FASTA of the\n"
+                "       base at least PCT percent (75) of at least MIN_DEPTH (1) reads agree on, N elsewhere, deletions dropped\n"
                 "  flagstat [-f INT] [-F INT] [-q INT] [-o FILE] <bam>: samtools flagstat's sixteen lines of the records that pass\n"
                 "  idxstats [-f INT] [-F INT] [-q INT] [-o FILE] <bam>: NAME LENGTH MAPPED UNMAPPED per reference, then the `*` line\n"
                 "       (samtools idxstats), counted from the records: no index is read, any order will do\n"
@@ -314,7 +326,7 @@ Args parse(int argc, char **argv) {
                 "  fasta: the same flags, >NAME and the bases only (samtools fasta)");
   a.cmd = argv[1];
   const bool rewrite = a.cmd == "htsjdk-rewrite", tally = a.cmd == "flagstat" || a.cmd == "idxstats";
-  const bool fq = a.cmd == "fastq" || a.cmd == "fasta";
+  const bool fq = a.cmd == "fastq" || a.cmd == "fasta", pile = a.cmd == "pileup" || a.cmd == "consensus";
   std::vector<std::string> pos;
   for (int i = 2; i < argc; ++i) {
     std::string t = argv[i];
@@ -364,6 +376,20 @@ Args parse(int argc, char **argv) {
     else if (a.cmd == "depth" && t == "-J") a.count_del = true;
     else if (a.cmd == "depth" && t == "--bedgraph") a.bedgraph = true;
     else if (a.cmd == "depth" && (t == "-o" || t == "--output")) a.out = next();
+    else if (pile && t == "-a" && a.cmd == "pileup") a.depth_all = true;
+    else if (pile && t == "-H" && a.cmd == "pileup") a.pile_header = true;
+    else if (pile && (t == "-r" || t == "--region")) a.region = next();
+    else if (pile && (t == "-f" || t == "--require-flags")) a.flag_require = (uint32_t)parse_int(next());
+    else if (pile && (t == "-F" || t == "--exclude-flags")) { a.flag_exclude = (uint32_t)parse_int(next()); a.has_exclude = true; }
+    else if (pile && (t == "-q" || t == "--min-mapq")) a.min_mapq = (int)parse_int(next());
+    else if (pile && (t == "-Q" || t == "--min-baseq")) a.min_baseq = (int)parse_int(next());
+    else if (pile && t == "-d" && a.cmd == "consensus") a.min_depth = (int)parse_int(next());
+    else if (pile && t == "-c" && a.cmd == "consensus") a.call_pct = (int)parse_int(next());
+    else if (pile && t == "--max-positions") a.max_positions = parse_int(next());
+    else if (pile && (t == "-o" || t == "--output")) a.out = next();
+    else if (pile && t.size() > 1 && t[0] == '-')
+      throw Error(SBH_E_ARG, a.cmd == "pileup" ? "usage: pileup [-a] [-H] [-r REGION] [-f INT] [-F INT] [-q INT] [-Q INT] [-o FILE] <bam> (unknown option " + t + ")"
+                                               : "usage: consensus [-r REGION] [-f INT] [-F INT] [-q INT] [-Q INT] [-d MIN_DEPTH] [-c PCT] [-o FILE] <bam> (unknown option " + t + ")");
     else if (a.cmd == "sort" && (t == "-o" || t == "--output")) a.out = next();
     else if (a.cmd == "sort" && (t == "-l" || t == "--level")) a.level = (int)parse_int(next());
     else if (a.cmd == "sort" && t == "--index-bai") a.idx_bai = true;
@@ -387,10 +413,10 @@ Args parse(int argc, char **argv) {
         (pos[0].size() > 1 && pos[0][0] == '-'))
       throw Error(SBH_E_ARG, "usage: view -c [-f INT] [-F INT] [-q INT] <bam>");
   }
-  if (pos.size() > 1 && a.cmd != "depth" && !tally && !fq) a.out = pos[1];
+  if (pos.size() > 1 && a.cmd != "depth" && !tally && !fq && !pile) a.out = pos[1];
   if (fq && !a.has_exclude) a.flag_exclude = 0x900;  // SECONDARY, SUPPLEMENTARY: samtools fastq's
   if (fq && a.suffix_never && a.suffix_always) throw Error(SBH_E_ARG, "usage: " + a.cmd + " takes -n or -N, not both");
-  if (a.cmd == "depth" && !a.has_exclude) a.flag_exclude = 1796;  // UNMAP, SECONDARY, QCFAIL, DUP: samtools depth's
+  if ((a.cmd == "depth" || pile) && !a.has_exclude) a.flag_exclude = 1796;  // UNMAP, SECONDARY, QCFAIL, DUP: samtools depth's
   if (a.cmd == "sort") {
     a.bam_out = a.sort = true;
     if (a.out.empty()) throw Error(SBH_E_ARG, "usage: sort needs -o OUT (a BAM is not written to the terminal)");
@@ -1114,6 +1140,38 @@ int view_bam(const Args &a) {
   return 0;
 }
 
+// The spans of -r REGION over the file's references: a reference name, or NAME:BEG-END with 1-based
+// inclusive positions; none: every reference whole.  cmd names the command in the error messages.
+template <class Header>
+std::vector<sbh_depth_span> region_spans(const Header &hdr, const std::string &region, const std::string &cmd) {
+  const int32_t n_ref = (int32_t)hdr.lens.size();
+  std::vector<sbh_depth_span> spans;
+  if (region.empty()) {
+    for (int32_t k = 0; k < n_ref; ++k)
+      if (hdr.lens[k] > 0) spans.push_back(sbh_depth_span{k, 0, 0, hdr.lens[k]});
+    return spans;
+  }
+  auto find = [&](const std::string &name) {
+    for (int32_t k = 0; k < n_ref; ++k)
+      if (hdr.names[k] == name) return k;
+    return (int32_t)-1;
+  };
+  int32_t k = find(region);
+  int64_t beg = 0, end = k >= 0 ? hdr.lens[k] : 0;
+  if (k < 0) {
+    const size_t c = region.rfind(':'), d = c == std::string::npos ? c : region.find('-', c);
+    auto digits = [](const std::string &t) { return !t.empty() && t.size() < 11 && t.find_first_not_of("0123456789") == std::string::npos; };
+    if (c == std::string::npos || d == std::string::npos || (k = find(region.substr(0, c))) < 0 ||
+        !digits(region.substr(c + 1, d - c - 1)) || !digits(region.substr(d + 1)))
+      throw Error(SBH_E_ARG, cmd + ": unknown reference in region " + region);
+    beg = std::stoll(region.substr(c + 1, d - c - 1)) - 1;
+    end = std::min<int64_t>(std::stoll(region.substr(d + 1)), hdr.lens[k]);
+  }
+  if (beg < 0 || beg >= end) throw Error(SBH_E_ARG, cmd + ": empty region " + region);
+  spans.push_back(sbh_depth_span{k, 0, beg, end});
+  return spans;
+}
+
 // depth: per-base depth of the records that pass the filters, whole file resident as view holds
 // it.  The records are scanned, their CIGARs walked and the depth scanned into runs on the device
 // (sbh_records_depth_add, sbh_depth_finish); the runs come back and are printed here -- samtools
@@ -1126,30 +1184,7 @@ int depth(const Args &a) {
   for (const sbh_block &b : L.blocks)
     if (b.flags & SBH_BLOCK_EMPTY) { seg_end = b.ustart; break; }
   const int32_t n_ref = (int32_t)L.hdr.lens.size();
-  std::vector<sbh_depth_span> spans;
-  if (a.region.empty()) {
-    for (int32_t k = 0; k < n_ref; ++k)
-      if (L.hdr.lens[k] > 0) spans.push_back(sbh_depth_span{k, 0, 0, L.hdr.lens[k]});
-  } else {
-    auto find = [&](const std::string &name) {
-      for (int32_t k = 0; k < n_ref; ++k)
-        if (L.hdr.names[k] == name) return k;
-      return (int32_t)-1;
-    };
-    int32_t k = find(a.region);
-    int64_t beg = 0, end = k >= 0 ? L.hdr.lens[k] : 0;
-    if (k < 0) {
-      const size_t c = a.region.rfind(':'), d = c == std::string::npos ? c : a.region.find('-', c);
-      auto digits = [](const std::string &t) { return !t.empty() && t.size() < 11 && t.find_first_not_of("0123456789") == std::string::npos; };
-      if (c == std::string::npos || d == std::string::npos || (k = find(a.region.substr(0, c))) < 0 ||
-          !digits(a.region.substr(c + 1, d - c - 1)) || !digits(a.region.substr(d + 1)))
-        throw Error(SBH_E_ARG, "depth: unknown reference in region " + a.region);
-      beg = std::stoll(a.region.substr(c + 1, d - c - 1)) - 1;
-      end = std::min<int64_t>(std::stoll(a.region.substr(d + 1)), L.hdr.lens[k]);
-    }
-    if (beg < 0 || beg >= end) throw Error(SBH_E_ARG, "depth: empty region " + a.region);
-    spans.push_back(sbh_depth_span{k, 0, beg, end});
-  }
+  const std::vector<sbh_depth_span> spans = region_spans(L.hdr, a.region, "depth");
   struct Acc {
     sbh_depth *d = nullptr;
     ~Acc() { sbh_depth_destroy(d); }
@@ -1196,6 +1231,115 @@ int depth(const Args &a) {
     }
   }
   ok = ok && fwrite(text.data(), 1, text.size(), f) == text.size() && fflush(f) == 0;
+  if (f != stdout) fclose(f);
+  if (!ok) throw Error(SBH_E_ARG, "short write to " + (a.out.empty() ? std::string("stdout") : a.out));
+  return 0;
+}
+
+// pileup, consensus: per-base allele counts of the records that pass the filters, whole file resident
+// as depth holds it.  The records are scanned and their CIGARs, bases and qualities walked into eight
+// counters per position on the device (sbh_records_pileup_add); the finish leaves a call byte per
+// position and the intervals any kept read touches (sbh_pileup_finish).  pileup prints the counters of
+// the intervals' positions (-a: of every position), consensus the call bytes as FASTA.
+int pileup(const Args &a) {
+  Loaded L(a.path);
+  uint64_t seg_end = L.flat;
+  for (const sbh_block &b : L.blocks)
+    if (b.flags & SBH_BLOCK_EMPTY) { seg_end = b.ustart; break; }
+  const int32_t n_ref = (int32_t)L.hdr.lens.size();
+  const std::vector<sbh_depth_span> spans = region_spans(L.hdr, a.region, a.cmd);
+  uint64_t positions = 0, budget = 0;
+  for (const sbh_depth_span &s : spans) positions += (uint64_t)(s.end - s.beg);
+  if (a.max_positions >= 0) budget = (uint64_t)a.max_positions;
+  else chk(sbh_pileup_budget(g_ctx, &budget), "pileup budget");
+  if (positions > budget)
+    throw Error(SBH_E_ARG, a.cmd + ": " + std::to_string(positions) + " positions at 33 bytes each do not fit the device memory budget of " +
+                               std::to_string(budget) + " positions: give a region with -r");
+  struct Acc {
+    sbh_pileup *p = nullptr;
+    ~Acc() { sbh_pileup_destroy(p); }
+  } acc;
+  chk(sbh_pileup_create(g_ctx, spans.data(), (uint32_t)spans.size(), n_ref, a.min_baseq, &acc.p), "pileup create");
+  if (seg_end > L.hdr.end) {
+    uint64_t n = 0;
+    chk(sbh_check_eager(L.sh, L.hdr.end, seg_end, a.reads_to_check, nullptr, &n), "eager");
+    sbh_records_sizes rs{};
+    chk(sbh_records_scan(L.sh, L.hdr.end, seg_end, &rs), "records scan");
+    sbh_record_filter f{};
+    f.flag_require = a.flag_require;
+    f.flag_exclude = a.flag_exclude;
+    f.min_mapq = a.min_mapq;
+    sbh_pileup_add_result ar{};
+    chk(sbh_records_pileup_add(L.sh, acc.p, &f, &ar), "pileup add");
+  }
+  sbh_pileup_sizes sz{};
+  chk(sbh_pileup_finish(acc.p, (uint32_t)std::max(a.min_depth, 0), (uint32_t)std::max(a.call_pct, 0), &sz), "pileup finish");
+  FILE *f = a.out.empty() ? stdout : fopen(a.out.c_str(), "wb");
+  if (!f) throw Error(SBH_E_ARG, "cannot write " + a.out);
+  bool ok = true;
+  std::string text;
+  auto flush = [&](bool all) {
+    if (all || text.size() >= (1u << 20)) {
+      ok = ok && fwrite(text.data(), 1, text.size(), f) == text.size();
+      text.clear();
+    }
+  };
+  constexpr uint64_t CHUNK = 1 << 16;  // positions fetched at a time
+  if (a.cmd == "consensus") {
+    std::vector<uint8_t> calls(CHUNK);
+    for (uint32_t k = 0; k < spans.size(); ++k) {
+      const sbh_depth_span &s = spans[k];
+      const std::string &name = L.hdr.names[s.ref_id];
+      text += ">" + name;
+      if (s.beg != 0 || s.end != L.hdr.lens[s.ref_id]) text += ":" + std::to_string(s.beg + 1) + "-" + std::to_string(s.end);
+      text += '\n';
+      uint64_t col = 0;
+      for (uint64_t from = 0, len = (uint64_t)(s.end - s.beg); from < len; from += CHUNK) {
+        const uint64_t m = std::min(CHUNK, len - from);
+        chk(sbh_pileup_calls_fetch(acc.p, k, from, m, calls.data()), "pileup calls");
+        for (uint64_t i = 0; i < m; ++i) {
+          if (calls[i] == '*') continue;
+          text += calls[i] ? (char)calls[i] : 'N';
+          if (++col == 60) text += '\n', col = 0;
+        }
+        flush(false);
+      }
+      if (col) text += '\n';
+    }
+  } else {
+    if (a.pile_header) text += "#chrom\tpos\tA\tC\tG\tT\tN\tdel\tins\tlowq\n";
+    std::vector<sbh_depth_span> ivals(sz.n_intervals);
+    chk(sbh_pileup_intervals_fetch(acc.p, 0, sz.n_intervals, ivals.data()), "pileup intervals");
+    std::vector<uint32_t> counts(8 * CHUNK);
+    size_t iv = 0;
+    for (uint32_t k = 0; k < spans.size(); ++k) {
+      const sbh_depth_span &s = spans[k];
+      const std::string &name = L.hdr.names[s.ref_id];
+      // the stretches to print: the span, or its intervals (they come in span and position order)
+      std::vector<std::pair<int64_t, int64_t>> cut;
+      if (a.depth_all) cut.emplace_back(s.beg, s.end);
+      for (; iv < ivals.size() && ivals[iv].ref_id == s.ref_id; ++iv)
+        if (!a.depth_all) cut.emplace_back(ivals[iv].beg, ivals[iv].end);
+      for (const auto &c : cut)
+        for (int64_t x = c.first; x < c.second; x += (int64_t)CHUNK) {
+          const uint64_t m = std::min<uint64_t>(CHUNK, (uint64_t)(c.second - x));
+          chk(sbh_pileup_counts_fetch(acc.p, k, (uint64_t)(x - s.beg), m, counts.data()), "pileup counts");
+          for (uint64_t i = 0; i < m; ++i) {
+            text += name;
+            text += '\t';
+            text += std::to_string(x + (int64_t)i + 1);
+            for (int ch = 0; ch < 8; ++ch) {
+              text += '\t';
+              text += std::to_string(counts[8 * i + ch]);
+            }
+            text += '\n';
+            flush(false);
+          }
+        }
+    }
+  }
+  flush(true);
+  ok = ok && fflush(f) == 0;
   if (f != stdout) fclose(f);
   if (!ok) throw Error(SBH_E_ARG, "short write to " + (a.out.empty() ? std::string("stdout") : a.out));
   return 0;
@@ -1539,6 +1683,7 @@ int main(int argc, char **argv) {
     else if (a.cmd == "htsjdk-rewrite") rc = htsjdk_rewrite(a);
     else if (a.cmd == "view" || a.cmd == "sort") rc = view(a);
     else if (a.cmd == "depth") rc = depth(a);
+    else if (a.cmd == "pileup" || a.cmd == "consensus") rc = pileup(a);
     else if (a.cmd == "flagstat" || a.cmd == "idxstats") rc = tally(a);
     else if (a.cmd == "fastq" || a.cmd == "fasta") rc = fastq(a);
     else throw Error(SBH_E_ARG, "unknown command " + a.cmd);

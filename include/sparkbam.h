@@ -769,6 +769,88 @@ int sbh_depth_add_host(const uint8_t *flat, uint64_t flat_size, const uint64_t *
 int sbh_depth_finish_host(int32_t *slots /* in place -> depth */, const sbh_depth_span *spans, uint32_t n_spans,
                           sbh_depth_run *runs, uint64_t run_cap, sbh_depth_sizes *out);
 
+/* ---- Per-base allele counts (pileup) --------------------------------------------------------
+ * What the kept records show at each reference position: how many A, C, G, T, other codes,
+ * deletions, insertions and low-quality bases, and the base they agree on.  Computed on the device
+ * from the flat bytes and record starts of a scan and accumulated across shards in an sbh_pileup,
+ * which belongs to a context and outlives the shards added to it (csrc/pileup_core.h holds the
+ * definition for device and host).
+ * Spans as sbh_depth's.  Span k owns end - beg positions of one array; every position has eight
+ * uint32 channels, 32 bytes of HBM per position (SBH_E_NOMEM):
+ *   SBH_PILE_A, _C, _G, _T   an M / = / X base with 4-bit code 1 / 2 / 4 / 8 and quality >= min_baseq
+ *   SBH_PILE_N               the same with any other code (0, the IUPAC codes, 15)
+ *   SBH_PILE_DEL             a D op covers the position
+ *   SBH_PILE_INS             an I op of length >= 1 starts right after the position
+ *   SBH_PILE_LOWQ            an M / = / X base with quality < min_baseq, whatever its code
+ * Kept, placed and counted rows are sbh_depth's.  The walk starts at x = pos, q = 0: M, =, X give
+ * reference position x + j query base q + j; D adds to DEL over [x, x + len); I adds to INS at
+ * x - 1 when len >= 1 and x > pos (an insertion before the first reference-consuming base counts
+ * nowhere); N, S, H, P add nothing; M, I, S, =, X advance q and M, D, N, =, X advance x (64-bit
+ * arithmetic).  Quality bytes compare unsigned: 0xff passes every min_baseq.  With l_seq == 0
+ * (SEQ *) every M / = / X position counts into N without a quality test.  The stored CIGAR field
+ * counts: a CG:B,I tag is not followed.
+ * sbh_records_pileup_add uses the rows of the last valid scan on the shard as sbh_records_depth_add
+ * does and validates every row as it does; a kept row is bad too when an op code is above 8, when
+ * ref_id >= n_ref, or when n_cigar > 0, l_seq > 0 and the lengths of its M, I, S, =, X ops do not
+ * sum to l_seq.  SBH_E_BAD_RECORD {row} for the first bad row, SBH_E_NEED_HALO instead when that
+ * row merely runs past an open shard end; a failed add leaves the accumulator exactly as it was.
+ * totals[c] = what the add put into channel c.  One thread at a time per sbh_pileup.
+ * sbh_pileup_finish (min_depth >= 1, call_pct in [1, 100]): per position depth = A + C + G + T + N
+ * + LOWQ and total = A + C + G + T + N + DEL; the call byte is 0 when all eight channels are 0,
+ * else the letter ('A' 'C' 'G' 'T' '*') of the largest of A, C, G, T, DEL when that maximum is
+ * unique, total >= min_depth and best * 100 >= call_pct * total, else 'N'.  An interval is a
+ * maximal stretch of positions with a non-zero call byte inside one span.  nonzero = positions
+ * with a non-zero call byte, n_called = those called A, C, G, T or *, covered = positions of depth
+ * >= 1, totals = every add's totals together.  The counts are not changed by a finish.  After it an
+ * add or a second finish gives SBH_E_STATE until sbh_pileup_reset (zero, open for adds again);
+ * before it the call and interval fetches give SBH_E_STATE.  sbh_pileup_counts_fetch works before
+ * and after a finish and always writes [n][8] in channel order; sbh_pileup_device_ptr is the
+ * span's first position in the device array, which has the same layout: position-major,
+ * uint32 [positions][8], 32-byte rows (NULL for a span out of range).
+ * SBH_E_ARG for bad spans (as sbh_depth's), min_baseq outside [0, 255], min_depth < 1, call_pct
+ * outside [1, 100], and a shard of another context.
+ * sbh_pileup_budget: the positions an accumulator created now could hold -- three quarters of the
+ * device memory free at the call, at 33 bytes per position (the channels and the call byte). */
+#define SBH_PILE_A 0
+#define SBH_PILE_C 1
+#define SBH_PILE_G 2
+#define SBH_PILE_T 3
+#define SBH_PILE_N 4
+#define SBH_PILE_DEL 5
+#define SBH_PILE_INS 6
+#define SBH_PILE_LOWQ 7
+typedef struct sbh_pileup sbh_pileup;         /* owned by a context; outlives shards */
+typedef struct { uint64_t n, n_kept, n_counted, n_unplaced, totals[8]; } sbh_pileup_add_result;
+typedef struct {
+  uint64_t positions, n_intervals, nonzero, n_called, covered, totals[8];
+  uint32_t max_depth, pad;
+} sbh_pileup_sizes;
+
+int sbh_pileup_create(sbh_ctx *ctx, const sbh_depth_span *spans, uint32_t n_spans, int32_t n_ref,
+                      int32_t min_baseq, sbh_pileup **out);
+int sbh_pileup_destroy(sbh_pileup *p);
+int sbh_pileup_reset(sbh_pileup *p);
+int sbh_records_pileup_add(sbh_shard *sh, sbh_pileup *p, const sbh_record_filter *filter /* NULL: all */,
+                           sbh_pileup_add_result *out);
+int sbh_pileup_finish(sbh_pileup *p, uint32_t min_depth, uint32_t call_pct, sbh_pileup_sizes *out);
+int sbh_pileup_counts_fetch(sbh_pileup *p, uint32_t span, uint64_t from, uint64_t n, uint32_t *out /* [n][8] */);
+int sbh_pileup_calls_fetch(sbh_pileup *p, uint32_t span, uint64_t from, uint64_t n, uint8_t *out);
+int sbh_pileup_intervals_fetch(sbh_pileup *p, uint64_t first, uint64_t count, sbh_depth_span *out);
+const void *sbh_pileup_device_ptr(sbh_pileup *p, uint32_t span);
+int sbh_pileup_budget(sbh_ctx *ctx, uint64_t *max_positions);
+/* HOST ONLY, no context, no GPU.  sbh_pileup_add_host adds into counts[positions][8] (the caller
+ * zeroes it first; positions = the spans' end - beg together); SBH_E_BAD_RECORD with *bad_row =
+ * the first bad row, the counts untouched.  sbh_pileup_finish_host writes calls[positions] and the
+ * first interval_cap intervals (may be NULL with interval_cap 0); sizes->n_intervals counts them
+ * all. */
+int sbh_pileup_add_host(const uint8_t *flat, uint64_t flat_size, const uint64_t *starts, uint64_t n,
+                        const sbh_record_filter *filter, const sbh_depth_span *spans, uint32_t n_spans,
+                        int32_t n_ref, int32_t min_baseq, uint32_t *counts, sbh_pileup_add_result *out,
+                        uint64_t *bad_row);
+int sbh_pileup_finish_host(const uint32_t *counts, const sbh_depth_span *spans, uint32_t n_spans,
+                           uint32_t min_depth, uint32_t call_pct, uint8_t *calls, sbh_depth_span *intervals,
+                           uint64_t interval_cap, sbh_pileup_sizes *out);
+
 /* ---- Flag counts and per-reference read counts ---------------------------------------------
  * What samtools flagstat and samtools idxstats report, counted on the device in one pass over the
  * fixed fields of a record scan's rows and summed over any number of scans and shards in an

@@ -51,6 +51,9 @@ EXPORTS = [
     "sbh_depth_create", "sbh_depth_destroy", "sbh_depth_reset", "sbh_records_depth_add", "sbh_depth_finish",
     "sbh_depth_fetch", "sbh_depth_runs_fetch", "sbh_depth_device_ptr", "sbh_depth_slots", "sbh_depth_add_host",
     "sbh_depth_finish_host",
+    "sbh_pileup_create", "sbh_pileup_destroy", "sbh_pileup_reset", "sbh_records_pileup_add", "sbh_pileup_finish",
+    "sbh_pileup_counts_fetch", "sbh_pileup_calls_fetch", "sbh_pileup_intervals_fetch", "sbh_pileup_device_ptr", "sbh_pileup_budget",
+    "sbh_pileup_add_host", "sbh_pileup_finish_host",
     "sbh_tally_create", "sbh_tally_destroy", "sbh_tally_reset", "sbh_records_tally_add", "sbh_tally_fetch",
     "sbh_tally_add_host",
     "sbh_records_fastq_scan", "sbh_records_fastq_device_ptr", "sbh_records_fastq_fetch", "sbh_fastq_render_host",
@@ -147,6 +150,17 @@ class SbhBamSizes(C.Structure):
 class SbhDepthAddResult(C.Structure):
     _fields_ = [("n", C.c_uint64), ("n_kept", C.c_uint64), ("n_counted", C.c_uint64), ("n_unplaced", C.c_uint64),
                 ("cov_bases", C.c_uint64)]
+
+
+class SbhPileupAddResult(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("n_kept", C.c_uint64), ("n_counted", C.c_uint64), ("n_unplaced", C.c_uint64),
+                ("totals", C.c_uint64 * 8)]
+
+
+class SbhPileupSizes(C.Structure):
+    _fields_ = [("positions", C.c_uint64), ("n_intervals", C.c_uint64), ("nonzero", C.c_uint64),
+                ("n_called", C.c_uint64), ("covered", C.c_uint64), ("totals", C.c_uint64 * 8),
+                ("max_depth", C.c_uint32), ("pad", C.c_uint32)]
 
 
 class SbhDepthSizes(C.Structure):
@@ -310,6 +324,18 @@ def lib():
         "sbh_depth_add_host": [P, U64, P, U64, C.POINTER(SbhRecordFilter), P, U32, I32, U32, P,
                                C.POINTER(SbhDepthAddResult), PU64],
         "sbh_depth_finish_host": [P, P, U32, P, U64, C.POINTER(SbhDepthSizes)],
+        "sbh_pileup_create": [P, P, U32, I32, I32, C.POINTER(P)],
+        "sbh_pileup_destroy": [P],
+        "sbh_pileup_reset": [P],
+        "sbh_records_pileup_add": [P, P, C.POINTER(SbhRecordFilter), C.POINTER(SbhPileupAddResult)],
+        "sbh_pileup_finish": [P, U32, U32, C.POINTER(SbhPileupSizes)],
+        "sbh_pileup_counts_fetch": [P, U32, U64, U64, P],
+        "sbh_pileup_calls_fetch": [P, U32, U64, U64, P],
+        "sbh_pileup_intervals_fetch": [P, U64, U64, P],
+        "sbh_pileup_budget": [P, PU64],
+        "sbh_pileup_add_host": [P, U64, P, U64, C.POINTER(SbhRecordFilter), P, U32, I32, I32, P,
+                                C.POINTER(SbhPileupAddResult), PU64],
+        "sbh_pileup_finish_host": [P, P, U32, U32, U32, P, P, U64, C.POINTER(SbhPileupSizes)],
         "sbh_tally_create": [P, I32, C.POINTER(P)],
         "sbh_tally_destroy": [P],
         "sbh_tally_reset": [P],
@@ -335,6 +361,8 @@ def lib():
     L.sbh_depth_slots.restype = U64
     L.sbh_depth_device_ptr.argtypes = [P, U32]
     L.sbh_depth_device_ptr.restype = P
+    L.sbh_pileup_device_ptr.argtypes = [P, U32]
+    L.sbh_pileup_device_ptr.restype = P
     L.sbh_stage_times.argtypes = [P, C.POINTER(C.c_double), I32]
     L.sbh_stage_times.restype = C.c_int
     L.sbh_last_error.argtypes = [P]

@@ -496,6 +496,85 @@ def depth(path_or_bytes, region=None, flag_require=0, flag_exclude=0x704, min_ma
             ctx.close()
 
 
+def pileup(path_or_bytes, region=None, flag_require=0, flag_exclude=0x704, min_mapq=0, min_baseq=0, min_depth=1,
+           call_pct=75, max_positions=None, window=None, ctx=None, reads_to_check=DEFAULT_READS_TO_CHECK):
+    """Per-base allele counts of the file's records, computed on the GPU: how many A, C, G, T, other
+    codes (N), deletions, insertions and low-quality bases the kept records show at each position,
+    and the base they agree on.  Every window of iter_reads' walk is scanned and added into one
+    accumulator in HBM (Context.pileup), which is then turned into call bytes and intervals.
+
+    region and the record filter as depth's.  min_baseq: a base whose quality is below it counts
+    into LOWQ instead of its letter; the default 0 keeps every base, so that A+C+G+T+N+LOWQ is
+    depth's number (`samtools mpileup` users will want 13, its -Q default).  min_depth, call_pct:
+    a position is called A, C, G, T or * (deletion) when that channel alone is the largest, A+C+G+T+
+    N+DEL >= min_depth and the channel holds at least call_pct percent of it; else N.
+
+    The accumulator costs 33 bytes of HBM per position (all of GRCh37: about 99 GB), so the spans
+    are grouped greedily into passes of at most max_positions positions, one walk of the file per
+    pass, the results concatenated.  max_positions defaults to three quarters of the free device
+    memory / 33 (Context.pileup_budget); a single span larger than it is a ValueError naming the span.
+
+    Returns a pileup.PileupResult: `.intervals`, `.stats`, `.counts(name)`, `.calls(name)`,
+    `.text(all_positions=False, header=False)` and `.consensus()` (FASTA)."""
+    from .coverage import DEPTH_SPAN_DTYPE, region_spans
+    from .pileup import PileupResult, span_passes
+    data = _file_array(path_or_bytes)
+    own_ctx = ctx is None
+    ctx = ctx or Context(0)
+    acc = None
+    try:
+        names, contig_len, _ = file_header(ctx, data)
+        try:
+            spans = region_spans(region, names, contig_len)
+        except ValueError as err:
+            raise SparkBamError(SBH_E_ARG, str(err).replace("depth:", "pileup:"))
+        budget = ctx.pileup_budget() if max_positions is None else int(max_positions)
+        f = {"flag_require": flag_require, "flag_exclude": flag_exclude, "min_mapq": min_mapq}
+        stats, ivs, counts, calls = {"totals": [0] * 8}, [], [], []
+        for group in span_passes(spans, budget):
+            acc = ctx.pileup(group, len(contig_len), min_baseq)
+            totals = {}
+
+            def deliver(sh, first, E, _names):
+                # as depth's: the chain is looked at before the add, so that a window run again with
+                # a larger halo has added nothing yet
+                _, x = sh.chain_from(first, E)
+                blocks = sh.blocks()
+                seg = next((b[3] for b in blocks if b[5] & 1 and b[3] >= first), None)
+                last = seg is not None and E == seg or sh.file_offset + sh.n == sh.file_size and E == sh.flat_size
+                if not last and x >= sh.flat_size:
+                    raise SparkBamError(SBH_E_NEED_HALO, "the chain leaves the halo")
+                sh.records_scan(first, E)
+                return [acc.add(sh, f)]
+
+            for (got,) in _iter_windows(data, deliver, window, ctx=ctx, reads_to_check=reads_to_check):
+                for k in ("n", "n_kept", "n_counted", "n_unplaced"):
+                    totals[k] = totals.get(k, 0) + got[k]
+            sz = acc.finish(min_depth, call_pct)
+            for k in ("positions", "n_intervals", "nonzero", "n_called", "covered"):
+                stats[k] = stats.get(k, 0) + sz[k]
+            stats["max_depth"] = max(stats.get("max_depth", 0), sz["max_depth"])
+            stats["totals"] = [a + b for a, b in zip(stats["totals"], sz["totals"])]
+            # every pass walks every record: the rows are the file's; a row is counted in the pass
+            # that holds its reference's span
+            for k in ("n", "n_kept", "n_unplaced"):
+                stats[k] = totals.get(k, 0)
+            stats["n_counted"] = stats.get("n_counted", 0) + totals.get("n_counted", 0)
+            ivs.append(acc.intervals() if sz["n_intervals"] else np.zeros(0, dtype=DEPTH_SPAN_DTYPE))
+            for k in range(len(group)):
+                counts.append(acc.counts(k))
+                calls.append(acc.calls(k))
+            acc.close()
+            acc = None
+        return PileupResult(np.concatenate(ivs) if ivs else np.zeros(0, dtype=DEPTH_SPAN_DTYPE), stats, spans, names,
+                            counts, calls, contig_len)
+    finally:
+        if acc is not None:
+            acc.close()
+        if own_ctx:
+            ctx.close()
+
+
 def _tally(path_or_bytes, flag_require, flag_exclude, min_mapq, window, ctx, reads_to_check):
     """flagstat's and idxstats' one pass: every window of iter_reads' walk scanned
     and counted into one accumulator in HBM (Context.tally)."""

@@ -1,7 +1,7 @@
 // sbh_host.h -- the host side's private header: the context, the shard and the other structs
 // behind the opaque handles of include/sparkbam.h, the error helpers, and the host helpers that
 // one file's entry points (sbh_api.hip, api_check.hip, api_records.hip, and the output stages' calls
-// behind the kernels of bai.hip, sam.hip, bam_gather.hip, depth.hip, tally.hip, fastq.hip, zdeflate.hip) borrow from another's.  Launchers are
+// behind the kernels of bai.hip, sam.hip, bam_gather.hip, depth.hip, pileup.hip, tally.hip, fastq.hip, zdeflate.hip) borrow from another's.  Launchers are
 // declared in sbh_internal.h; nothing here is seen by device code.
 #pragma once
 #include <algorithm>
@@ -329,6 +329,34 @@ struct sbh_depth {
   sbh_depth_sizes sz{};
   bool finished = false;
   ~sbh_depth() {
+    if (ctx) (void)hipSetDevice(ctx->device);
+    if (st) {
+      (void)hipStreamSynchronize(st);
+      (void)hipStreamDestroy(st);
+    }
+  }
+};
+
+// A pileup accumulator (sbh_pileup_create): eight u32 channels per position, owned by a context, fed
+// by any number of its shards.  Streams as sbh_depth's: the adds run on the adding shard's stream
+// (with the shard's depth scratch: keep bits, row ranges) and synchronise it before they return;
+// reset, finish and the fetches run on the accumulator's own stream and synchronise that.
+struct sbh_pileup {
+  sbh_ctx *ctx = nullptr;
+  hipStream_t st = nullptr;
+  std::vector<sbh_depth_span> spans;
+  std::vector<uint64_t> off;  // n_spans + 1: the first position of each span, then S
+  int32_t n_ref = 0;
+  uint32_t min_baseq = 0;
+  uint64_t S = 0;
+  sbh::DBuf<uint4> counts;  // 2 S: position s is counts[2 s], counts[2 s + 1] (A C G T | N DEL INS LOWQ)
+  sbh::DBuf<uint8_t> calls;  // S, after finish
+  sbh::DBuf<sbh_depth_span> d_spans, ivals;
+  sbh::DBuf<uint64_t> d_off, heads, hbase, tstat, tmp;
+  sbh::DBuf<unsigned long long> acc;  // the folded tile stats
+  sbh_pileup_sizes sz{};
+  bool finished = false;
+  ~sbh_pileup() {
     if (ctx) (void)hipSetDevice(ctx->device);
     if (st) {
       (void)hipStreamSynchronize(st);

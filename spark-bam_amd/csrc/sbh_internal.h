@@ -347,6 +347,12 @@ constexpr uint32_t TALLY_END = H_TALLY_BAD + 4;
 // end; h_ctr only: the parts' bytes (3 words), then their lines (3 words)
 constexpr uint32_t FASTQ_BAD = TALLY_END, FASTQ_PAST = FASTQ_BAD + 1, H_FASTQ_SUMS = FASTQ_BAD + 2;
 constexpr uint32_t FASTQ_END = H_FASTQ_SUMS + 6;
+// pileup add (k_pile_check): first bad row, first row that only runs past the stream's end, kept
+// rows, kept rows without a reference; (k_pile_events): rows walked, then what went into each of
+// the eight channels
+constexpr uint32_t PILE_BAD = FASTQ_END, PILE_PAST = PILE_BAD + 1, PILE_KEPT = PILE_BAD + 2;
+constexpr uint32_t PILE_UNPLACED = PILE_BAD + 3, PILE_COUNTED = PILE_BAD + 4, PILE_TOTALS = PILE_BAD + 5;
+constexpr uint32_t PILE_END = PILE_TOTALS + 8;
 // inflate status (launch_first_bad): the first block whose status is not INF_OK
 constexpr uint32_t FIRST_BAD = 100;
 // h_ctr only: that block's status (u32), fetched after the run's copy of [0, CTR_RUN_WORDS)
@@ -365,6 +371,7 @@ static_assert(ctr::FULL_END == CTR_CALL_END, "the full checker's counters end th
 static_assert(ctr::DEPTH_END <= ctr::FIRST_BAD, "the depth counters end before the first bad block");
 static_assert(ctr::TALLY_END <= ctr::FIRST_BAD, "the tally add's mirror words end before the first bad block");
 static_assert(ctr::FASTQ_END <= ctr::FIRST_BAD, "the FASTQ scan's words end before the first bad block");
+static_assert(ctr::PILE_END <= ctr::FIRST_BAD, "the pileup add's counters end before the first bad block");
 // what the run template presets (the eager counters, FindRecordStart's best, the proof
 // counters, the first bad block) travels in the run's one copy each way ...
 static_assert(ctr::EAGER_END <= CTR_RUN_WORDS && ctr::FRS_BEST < CTR_RUN_WORDS &&

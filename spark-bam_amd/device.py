@@ -5,10 +5,10 @@ import weakref
 
 import numpy as np
 
-from .coverage import DEPTH_DEL, DEPTH_RUN_DTYPE, span_array
+from .coverage import DEPTH_DEL, DEPTH_RUN_DTYPE, DEPTH_SPAN_DTYPE, span_array
 from .records import pack_ref_names, record_columns, record_filter
 
-from ._lib import (ORDER_COORDINATE, SBH_OK, SbhBaiSizes, SbhBamSizes, SbhBatchSplit, SbhBlock, SbhCheckOpts, SbhCheckResult, SbhDepthAddResult,
+from ._lib import (ORDER_COORDINATE, SBH_OK, SbhBaiSizes, SbhBamSizes, SbhBatchSplit, SbhBlock, SbhCheckOpts, SbhCheckResult, SbhDepthAddResult, SbhPileupAddResult, SbhPileupSizes,
                    SbhDepthSizes, SbhFastqSizes, SbhRecordsOut,
                    SbhRecordsSizes, SbhSamSizes, SbhShardResult, SbhSplitBatchResult, SbhSplitRecordsResult,
                    SbhStreamOpts, SbhStreamResult, SbhTallyAddResult, SparkBamError, error_for, lib)
@@ -229,6 +229,20 @@ class Context:
         HBM per position plus one per span.  count_del: D ops cover (samtools depth -J)."""
         return Depth(self, spans, n_ref, count_del)
 
+    def pileup(self, spans, n_ref, min_baseq=0):
+        """A per-base allele-count accumulator over spans [(ref_id, beg, end), ...] (as depth's) of a
+        file with n_ref references (sbh_pileup_create): eight uint32 channels per position (A, C,
+        G, T, N, DEL, INS, LOWQ), 32 bytes of HBM per position plus one for the call byte.  A base
+        whose quality is below min_baseq counts into LOWQ instead of its letter."""
+        return Pileup(self, spans, n_ref, min_baseq)
+
+    def pileup_budget(self):
+        """The positions a pileup accumulator created now could hold: three quarters of the free
+        device memory at 33 bytes per position (sbh_pileup_budget)."""
+        n = C.c_uint64()
+        _check(self.h, lib().sbh_pileup_budget(self.h, C.byref(n)))
+        return int(n.value)
+
     def tally(self, n_ref):
         """A flag-count and per-reference-count accumulator for a file with n_ref references
         (sbh_tally_create): what samtools flagstat and idxstats report, counted on the GPU."""
@@ -352,6 +366,95 @@ class Depth:
     def reset(self):
         """Zero the slots and open the accumulator for adds again (sbh_depth_reset)."""
         _check(self.ctx.h, lib().sbh_depth_reset(self.h))
+        self.sizes = None
+
+
+class Pileup:
+    """sbh_pileup: scans of any number of this context's shards added into one table of per-base
+    allele counts (`add`), then turned into call bytes and intervals on the GPU (`finish`)."""
+
+    def __init__(self, ctx, spans, n_ref, min_baseq=0):
+        self.ctx = ctx
+        self.spans = [(int(r), int(b), int(e)) for r, b, e in spans]
+        sp = span_array(self.spans)
+        h = C.c_void_p()
+        _check(ctx.h, lib().sbh_pileup_create(ctx.h, _ptr(sp) if sp.size else None, int(sp.size), int(n_ref),
+                                              int(min_baseq), C.byref(h)))
+        self.h = h
+        self.sizes = None
+        ctx._shards.add(self)  # (closed with the context, before it)
+
+    def close(self):
+        if self.h:
+            if self.ctx.h:
+                lib().sbh_pileup_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, shard, filter=None):
+        """The rows of the last scan on `shard` that `filter` keeps (records.record_filter's dict,
+        None: all), added (sbh_records_pileup_add).  Returns the add's counts as a dict: n, n_kept,
+        n_counted, n_unplaced, totals (what went into each channel).  A failed add leaves the
+        accumulator as it was."""
+        from .pileup import add_dict
+        f, keep = record_filter(filter)
+        r = SbhPileupAddResult()
+        _check(self.ctx.h, lib().sbh_records_pileup_add(shard.h, self.h, C.byref(f) if f is not None else None,
+                                                        C.byref(r)))
+        del keep
+        return add_dict(r)
+
+    def finish(self, min_depth=1, call_pct=75):
+        """Counts -> call bytes, intervals and stats on the GPU (sbh_pileup_finish): a dict
+        positions, n_intervals, nonzero, n_called, covered, max_depth, totals.  No add may follow
+        until reset()."""
+        from .pileup import sizes_dict
+        sz = SbhPileupSizes()
+        _check(self.ctx.h, lib().sbh_pileup_finish(self.h, int(min_depth), int(call_pct), C.byref(sz)))
+        self.sizes = sizes_dict(sz)
+        return self.sizes
+
+    def _n(self, span, start, n):
+        _, b, e = self.spans[span]
+        return max(int((e - b) - start if n is None else n), 0)
+
+    def counts(self, span=0, start=0, n=None):
+        """uint32 [n, 8] of positions beg + start .. beg + start + n of span `span` (to its end by
+        default), before or after finish -- sbh_pileup_counts_fetch."""
+        out = np.zeros((self._n(span, start, n), 8), dtype=np.uint32)
+        _check(self.ctx.h, lib().sbh_pileup_counts_fetch(self.h, int(span), int(start), out.shape[0],
+                                                         _ptr(out) if out.size else None))
+        return out
+
+    def calls(self, span=0, start=0, n=None):
+        """The call bytes (uint8) of the same positions, after finish -- sbh_pileup_calls_fetch."""
+        out = np.zeros(self._n(span, start, n), dtype=np.uint8)
+        _check(self.ctx.h, lib().sbh_pileup_calls_fetch(self.h, int(span), int(start), out.size,
+                                                        _ptr(out) if out.size else None))
+        return out
+
+    def intervals(self, first=0, count=None):
+        """Intervals [first, first + count) (all by default) as a DEPTH_SPAN_DTYPE array."""
+        if self.sizes is None:  # (the library says SBH_E_STATE)
+            _check(self.ctx.h, lib().sbh_pileup_intervals_fetch(self.h, 0, 0, None))
+        count = self.sizes["n_intervals"] - first if count is None else count
+        out = np.zeros(max(int(count), 0), dtype=DEPTH_SPAN_DTYPE)
+        _check(self.ctx.h, lib().sbh_pileup_intervals_fetch(self.h, int(first), int(count),
+                                                            _ptr(out) if out.size else None))
+        return out
+
+    def device_ptr(self, span=0):
+        """Device pointer of the span's counts: uint32 [positions][8], position-major."""
+        return lib().sbh_pileup_device_ptr(self.h, int(span))
+
+    def reset(self):
+        """Zero the counts and open the accumulator for adds again (sbh_pileup_reset)."""
+        _check(self.ctx.h, lib().sbh_pileup_reset(self.h))
         self.sizes = None
 
 
