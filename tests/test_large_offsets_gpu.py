@@ -7,7 +7,9 @@ The file: the synthetic BAM header, then 2^31 + 1 MiB of zero bytes (BGZF-compre
 few MB), then config-D long reads (10-50 kb, CIGARs of 50-500 ops), so the long-read
 records sit at flat offsets above 2^31.  The eager call at every position of that region
 and the record chain through it equal the CPU oracle's (parity at the reference's
-semantics: eager/Checker.scala:24-126, PosStream.scala:14-22)."""
+semantics: eager/Checker.scala:24-126, PosStream.scala:14-22).  The stages behind the chain
+(record decode, intervals, batched splits, BAI, SAM, BAM gather and sort, depth, pileup, tally, FASTQ)
+meet offsets past 2^31 and 2^32 in test_large_record_offsets_gpu.py."""
 import os
 import sys
 
