@@ -7,6 +7,9 @@
 //   (scans)      len -> off, kh -> khpre (kept rows before i | runs before i << 32)
 //   k_bam_index  rec_off / rows per kept row, (dst, src) per run, the closing entries
 //   k_bam_copy   one 16-byte-aligned granule of the OUTPUT per lane
+//
+// This file also defines the frame every filtered row stage shares (sbh_host.h; DESIGN "Row stages"):
+// bam_filter_of / row_filter, stage_row_ranges and rows_verdict.
 #include <algorithm>
 #include <cstring>
 
@@ -18,7 +21,6 @@
 namespace sbh {
 namespace {
 
-constexpr uint32_t KEEP_GRID = 1024;             // k_bam_keep / _heads / _index: 262144 rows a pass
 constexpr uint32_t COPY_T = 256, COPY_TILE = COPY_T * 16;  // bytes of output per workgroup and pass
 constexpr uint32_t COPY_GRID = 2048;             // k_bam_copy: 8 MiB of output a pass
 
@@ -32,6 +34,7 @@ __global__ __launch_bounds__(256) void k_bam_keep(const uint8_t *__restrict__ U,
     const int v = sbh_bam::row_check(U, total, p, &bytes);
     bool k = false;
     if (v != sbh_bam::ROW_OK) {
+      // (per-row atomics, not RowMinima: the same two minima, and two loop-carried words fewer)
       atomicMin(bad, (unsigned long long)i);
       if (v == sbh_bam::ROW_PAST) atomicMin(past, (unsigned long long)i);
     } else {
@@ -133,18 +136,14 @@ __global__ __launch_bounds__(COPY_T) void k_bam_copy(const uint8_t *__restrict__
   }
 }
 
-uint32_t rows_grid(uint64_t n) { return (uint32_t)std::min<uint64_t>((n + 255) / 256, KEEP_GRID); }
-
 }  // namespace
 
 // len, kh: n + 1 words (the caller zeroes entry n); bad, past preset to ~0: the first invalid row, the
-// first row invalid only because the stream ends too early
-static hipError_t launch_bam_keep(const uint8_t *U, const uint64_t *pos, uint64_t n, uint64_t total, uint32_t flag_require,
-                                  uint32_t flag_exclude, int32_t min_mapq, const uint64_t *row_begin, const uint64_t *row_end,
-                                  uint64_t n_row_ranges, uint64_t *len, uint64_t *kh, unsigned long long *bad,
-                                  unsigned long long *past, hipStream_t st) {
+// first row invalid only because the stream ends too early.  F's row ranges are device memory.
+static hipError_t launch_bam_keep(const uint8_t *U, const uint64_t *pos, uint64_t n, uint64_t total, const sbh_bam::Filter &F,
+                                  uint64_t *len, uint64_t *kh, unsigned long long *bad, unsigned long long *past,
+                                  hipStream_t st) {
   if (!n) return hipSuccess;
-  const sbh_bam::Filter F{flag_require, flag_exclude, min_mapq, row_begin, row_end, n_row_ranges};
   hipLaunchKernelGGL(k_bam_keep, dim3(rows_grid(n)), dim3(256), 0, st, U, pos, n, total, F, len, kh, bad, past);
   hipLaunchKernelGGL(k_bam_heads, dim3(rows_grid(n)), dim3(256), 0, st, pos, len, n, kh);
   return hipGetLastError();
@@ -183,6 +182,30 @@ bool bam_filter_of(const sbh_record_filter *f, sbh_bam::Filter *F) {
   return sbh_bam::filter_ok(*F);
 }
 
+int row_filter(sbh_ctx *ctx, const sbh_record_filter *f, sbh_bam::Filter *F) {
+  if (bam_filter_of(f, F)) return SBH_OK;
+  return fail(ctx, SBH_E_ARG, "record filter: flags < 65536, 0 <= min_mapq <= 255, row ranges sorted, disjoint and non-empty");
+}
+
+hipError_t stage_row_ranges(sbh_shard *sh, sbh_bam::Filter *F) {
+  const uint64_t nr = F->n_row_ranges;
+  hipError_t e = sh->row_ranges.ensure(2 * nr);
+  uint64_t *d = sh->row_ranges.p;
+  if (e == hipSuccess && nr) e = hipMemcpyAsync(d, F->row_begin, 8 * nr, hipMemcpyHostToDevice, sh->st);
+  if (e == hipSuccess && nr) e = hipMemcpyAsync(d + nr, F->row_end, 8 * nr, hipMemcpyHostToDevice, sh->st);
+  F->row_begin = d, F->row_end = d + nr;
+  return e;
+}
+
+int rows_verdict(sbh_shard *sh, uint64_t bad, uint64_t past, const char *also) {
+  if (bad == ~0ull) return SBH_OK;
+  // only a record that runs past the resident bytes can be cured by more of them
+  if (past == bad && !sh->at_eof)
+    return fail(sh->ctx, SBH_E_NEED_HALO, "record %llu of the scan may run past the shard", (unsigned long long)bad);
+  return fail_with(sh->ctx, SBH_E_BAD_RECORD, {(int64_t)bad}, "record %llu of the scan does not fit its block or the stream%s",
+                   (unsigned long long)bad, also);
+}
+
 }  // namespace sbh
 
 using namespace sbh;
@@ -215,12 +238,12 @@ int sbh_records_bam_scan_order(sbh_shard *sh, const uint8_t *head, uint64_t head
   const bool sorted = order == SBH_ORDER_COORDINATE;
   if (!R.valid) return fail(ctx, SBH_E_STATE, "records_bam_scan without a records scan");
   sbh_bam::Filter F;
-  if (!bam_filter_of(filter, &F))
-    return fail(ctx, SBH_E_ARG, "record filter: flags < 65536, 0 <= min_mapq <= 255, row ranges sorted, disjoint and non-empty");
-  const uint64_t n = R.sz.n, nr = F.n_row_ranges;
+  int rc = row_filter(ctx, filter, &F);
+  if (rc) return rc;
+  const uint64_t n = R.sz.n;
   if (n >= 0xffffffffull)
     return fail(ctx, SBH_E_ARG, "records_bam_scan: %llu rows in one scan (scan in windows)", (unsigned long long)n);
-  int rc = set_device(ctx);
+  rc = set_device(ctx);
   if (rc) return rc;
   hipStream_t st = sh->st;
   B.valid = false;
@@ -236,19 +259,14 @@ int sbh_records_bam_scan_order(sbh_shard *sh, const uint8_t *head, uint64_t head
   }
   bool already = true;
   if (n) {
-    HIPCHK(ctx, B.ranges.ensure(2 * nr));
-    if (nr) {
-      HIPCHK(ctx, hipMemcpyAsync(B.ranges.p, F.row_begin, 8 * nr, hipMemcpyHostToDevice, st));
-      HIPCHK(ctx, hipMemcpyAsync(B.ranges.p + nr, F.row_end, 8 * nr, hipMemcpyHostToDevice, st));
-    }
+    HIPCHK(ctx, stage_row_ranges(sh, &F));
     HIPCHK(ctx, sh->tmp.ensure(scan_tmp_words(n + 1)));
     HIPCHK(ctx, hipMemsetAsync(B.len.p + n, 0, 8, st));
     HIPCHK(ctx, hipMemsetAsync(B.kh.p + n, 0, 8, st));
     unsigned long long *bad = sh->ctr.p + ctr::BAM_BAD;  // (BAM_PAST is the next word)
     static_assert(ctr::BAM_PAST == ctr::BAM_BAD + 1, "one memset, one copy");
     HIPCHK(ctx, hipMemsetAsync(bad, 0xff, 16, st));
-    HIPCHK(ctx, launch_bam_keep(sh->U.p, R.pos.p, n, sh->utotal, F.flag_require, F.flag_exclude, F.min_mapq, B.ranges.p,
-                                B.ranges.p + nr, nr, B.len.p, B.kh.p, bad, bad + 1, st));
+    HIPCHK(ctx, launch_bam_keep(sh->U.p, R.pos.p, n, sh->utotal, F, B.len.p, B.kh.p, bad, bad + 1, st));
     HIPCHK(ctx, scan_exclusive_u64(B.len.p, B.off.p, n + 1, sh->tmp.p, st));
     HIPCHK(ctx, scan_exclusive_u64(B.kh.p, B.khpre.p, n + 1, sh->tmp.p, st));
     HIPCHK(ctx, launch_bam_index(R.pos.p, B.off.p, B.kh.p, B.khpre.p, n, head_bytes, B.rec_off.p, B.rows.p, B.run_dst.p,
@@ -265,14 +283,8 @@ int sbh_records_bam_scan_order(sbh_shard *sh, const uint8_t *head, uint64_t head
     HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::H_BAM_BYTES, B.off.p + n, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::H_BAM_KH, B.khpre.p + n, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
-    const uint64_t row = sh->h_ctr[ctr::BAM_BAD];
-    if (row != ~0ull) {
-      // only a record that runs past the resident bytes can be cured by more of them
-      if (sh->h_ctr[ctr::BAM_PAST] == row && !sh->at_eof)
-        return fail(ctx, SBH_E_NEED_HALO, "record %llu of the scan may run past the shard", (unsigned long long)row);
-      return fail_with(ctx, SBH_E_BAD_RECORD, {(int64_t)row}, "record %llu of the scan does not fit its block or the stream",
-                       (unsigned long long)row);
-    }
+    rc = rows_verdict(sh, sh->h_ctr[ctr::BAM_BAD], sh->h_ctr[ctr::BAM_PAST], "");
+    if (rc) return rc;
     bytes += sh->h_ctr[ctr::H_BAM_BYTES];
     n_kept = sh->h_ctr[ctr::H_BAM_KH] & 0xffffffffull;
     n_runs = sh->h_ctr[ctr::H_BAM_KH] >> 32;

@@ -33,7 +33,6 @@ using sbh_bam::SORT_ITEMS;
 using sbh_bam::SORT_TILE;
 using sbh_bam::SORT_WAVES;
 constexpr uint32_t SORT_T = SORT_WAVES * 64;  // lanes of a sort workgroup
-constexpr uint32_t ROWS_GRID = 1024;          // the row kernels: 262144 rows a pass, as k_bam_keep
 
 __device__ __forceinline__ uint64_t wave_or(uint64_t v) {
   for (int m = 1; m < 64; m <<= 1) v |= (uint64_t)__shfl_xor((unsigned long long)v, m);
@@ -188,8 +187,6 @@ __global__ __launch_bounds__(256) void k_sort_rows(const uint32_t *row, uint64_t
   const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
   for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < m; k += step) rows[k] = row[k];
 }
-
-uint32_t rows_grid(uint64_t n) { return (uint32_t)std::min<uint64_t>((n + 255) / 256, ROWS_GRID); }
 
 }  // namespace
 

@@ -4,8 +4,9 @@
 //
 //   k_depth_check      one row per lane: row_check, row_keep and, for kept rows, the reference range
 //                      and every op code; a keep bit per row (one ballot word per wave and pass), the
-//                      smallest bad row and the smallest row that only runs past the stream, n_kept,
-//                      n_unplaced (one atomic per workgroup and counter)
+//                      smallest bad row and the smallest row that only runs past the stream (RowMinima,
+//                      sbh_internal.h; the host's rows_verdict reads them), n_kept, n_unplaced (block_add:
+//                      one atomic per workgroup and counter)
 //   k_depth_events     kept rows only, one row per lane: +1 / -1 into the slots by no-return integer
 //                      atomics.  A lane walks up to DEPTH_LANE_OPS ops itself; a row with more is
 //                      handed to its wave by ballot, and the wave takes such rows one at a time, 64
@@ -41,26 +42,8 @@ namespace {
 using sbh_dep::DEPTH_LANE_OPS;
 using sbh_dep::DEPTH_TILE;
 using sbh_dep::Span;
-constexpr uint32_t ROWS_GRID = 1024;  // the row kernels: 262144 rows a pass, as k_bam_keep
 constexpr uint32_t TILE_T = 256, TILE_ROUNDS = 4;
 static_assert(DEPTH_TILE == TILE_T * TILE_ROUNDS * 4, "a tile is 4 waves x 4 rounds x 64 lanes x 4 slots");
-
-__device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
-  for (int m = 1; m < 64; m <<= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, m);
-  return v;
-}
-
-// One value per workgroup into *dst: v summed over the 4 waves (every lane calls; s_red: 4 words).
-__device__ __forceinline__ void block_add(uint64_t v, uint64_t *s_red, unsigned long long *dst) {
-  v = wave_sum(v);
-  __syncthreads();  // (s_red may still be read from the call before)
-  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const uint64_t t = s_red[0] + s_red[1] + s_red[2] + s_red[3];
-    if (t) atomicAdd(dst, (unsigned long long)t);
-  }
-}
 
 // keep: one u64 per 64 rows, bit (i & 63) of word i >> 6; every word below ceil(n / 64) is written.
 // acc: bad, past (preset ~0), n_kept, n_unplaced (preset 0).
@@ -69,7 +52,8 @@ __global__ __launch_bounds__(256) void k_depth_check(const uint8_t *__restrict__
                                                      unsigned long long *acc) {
   __shared__ uint64_t s_red[4];
   const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
-  uint64_t kept = 0, unplaced = 0, bad = ~0ull, past = ~0ull;
+  uint64_t kept = 0, unplaced = 0;
+  RowMinima m;
   // (the loop is uniform in the workgroup: the ballot runs with every lane of the wave)
   for (uint64_t base = (uint64_t)blockIdx.x * blockDim.x; base < n; base += step) {
     const uint64_t i = base + threadIdx.x;
@@ -79,13 +63,12 @@ __global__ __launch_bounds__(256) void k_depth_check(const uint8_t *__restrict__
       uint64_t bytes = 0;
       const int v = sbh_bam::row_check(U, total, p, &bytes);
       if (v != sbh_bam::ROW_OK) {
-        bad = bad < i ? bad : i;
-        if (v == sbh_bam::ROW_PAST) past = past < i ? past : i;
+        m.refused(i, v == sbh_bam::ROW_PAST);
       } else if (sbh_bam::row_keep(U + p, i, F)) {
         const uint8_t *r = U + p;
         const int32_t ref_id = (int32_t)sbh_bam::ld32(r + 4);
         if (ref_id >= n_ref || !sbh_dep::ops_ok(r)) {
-          bad = bad < i ? bad : i;
+          m.rejected(i);
         } else {
           k = true;
           ++kept;
@@ -96,8 +79,7 @@ __global__ __launch_bounds__(256) void k_depth_check(const uint8_t *__restrict__
     const uint64_t word = __ballot(k);
     if ((threadIdx.x & 63) == 0 && i < n) keep[i >> 6] = word;
   }
-  if (bad != ~0ull) atomicMin(acc + 0, (unsigned long long)bad);
-  if (past != ~0ull) atomicMin(acc + 1, (unsigned long long)past);
+  m.send(acc + 0, acc + 1);
   block_add(kept, s_red, acc + 2);
   block_add(unplaced, s_red, acc + 3);
 }
@@ -439,8 +421,6 @@ __global__ __launch_bounds__(TILE_T) void k_depth_runs(const int32_t *depth, uin
   }
 }
 
-uint32_t rows_grid(uint64_t n) { return (uint32_t)std::min<uint64_t>((n + 255) / 256, ROWS_GRID); }
-
 }  // namespace
 
 // The launchers, in the order the entry points below use them.  launch_depth_events: off has
@@ -449,13 +429,11 @@ uint32_t rows_grid(uint64_t n) { return (uint32_t)std::min<uint64_t>((n + 255) /
 // the last), the scan of heads as hbase, launch_depth_runs.
 static uint64_t depth_tiles(uint64_t S) { return (S + DEPTH_TILE - 1) / DEPTH_TILE; }
 
-// keep: ceil(n / 64) words; acc: ctr::DEPTH_BAD .. DEPTH_UNPLACED (preset ~0, ~0, 0, 0)
-static hipError_t launch_depth_check(const uint8_t *U, const uint64_t *pos, uint64_t n, uint64_t total, uint32_t flag_require,
-                                     uint32_t flag_exclude, int32_t min_mapq, const uint64_t *row_begin, const uint64_t *row_end,
-                                     uint64_t n_row_ranges, int32_t n_ref, uint64_t *keep, unsigned long long *acc,
-                                     hipStream_t st) {
+// keep: ceil(n / 64) words; acc: ctr::DEPTH_BAD .. DEPTH_UNPLACED (preset ~0, ~0, 0, 0).  F's row
+// ranges are device memory.
+static hipError_t launch_depth_check(const uint8_t *U, const uint64_t *pos, uint64_t n, uint64_t total, const sbh_bam::Filter &F,
+                                     int32_t n_ref, uint64_t *keep, unsigned long long *acc, hipStream_t st) {
   if (!n) return hipSuccess;
-  const sbh_bam::Filter F{flag_require, flag_exclude, min_mapq, row_begin, row_end, n_row_ranges};
   hipLaunchKernelGGL(k_depth_check, dim3(rows_grid(n)), dim3(256), 0, st, U, pos, n, total, F, n_ref, keep, acc);
   return hipGetLastError();
 }
@@ -583,21 +561,17 @@ int sbh_records_depth_add(sbh_shard *sh, sbh_depth *d, const sbh_record_filter *
   if (!R.valid) return fail(ctx, SBH_E_STATE, "records_depth_add without a records scan");
   if (d->finished) return fail(ctx, SBH_E_STATE, "records_depth_add after sbh_depth_finish (sbh_depth_reset reopens)");
   sbh_bam::Filter F;
-  if (!bam_filter_of(filter, &F))
-    return fail(ctx, SBH_E_ARG, "record filter: flags < 65536, 0 <= min_mapq <= 255, row ranges sorted, disjoint and non-empty");
-  const uint64_t n = R.sz.n, nr = F.n_row_ranges;
+  int rc = row_filter(ctx, filter, &F);
+  if (rc) return rc;
+  const uint64_t n = R.sz.n;
   *out = sbh_depth_add_result{n, 0, 0, 0, 0};
   if (!n) return SBH_OK;
-  int rc = set_device(ctx);
+  rc = set_device(ctx);
   if (rc) return rc;
   hipStream_t st = sh->st;
   auto &D = sh->dep;
   HIPCHK(ctx, D.keep.ensure((n + 63) / 64));
-  HIPCHK(ctx, D.ranges.ensure(2 * nr));
-  if (nr) {
-    HIPCHK(ctx, hipMemcpyAsync(D.ranges.p, F.row_begin, 8 * nr, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(D.ranges.p + nr, F.row_end, 8 * nr, hipMemcpyHostToDevice, st));
-  }
+  HIPCHK(ctx, stage_row_ranges(sh, &F));
   unsigned long long *acc = sh->ctr.p + ctr::DEPTH_BAD;
   static_assert(ctr::DEPTH_PAST == ctr::DEPTH_BAD + 1 && ctr::DEPTH_KEPT == ctr::DEPTH_BAD + 2 &&
                     ctr::DEPTH_UNPLACED == ctr::DEPTH_BAD + 3 && ctr::DEPTH_COUNTED == ctr::DEPTH_BAD + 4 &&
@@ -605,19 +579,11 @@ int sbh_records_depth_add(sbh_shard *sh, sbh_depth *d, const sbh_record_filter *
                 "two memsets, one copy each way");
   HIPCHK(ctx, hipMemsetAsync(acc, 0xff, 16, st));
   HIPCHK(ctx, hipMemsetAsync(acc + 2, 0, 32, st));
-  HIPCHK(ctx, launch_depth_check(sh->U.p, R.pos.p, n, sh->utotal, F.flag_require, F.flag_exclude, F.min_mapq, D.ranges.p,
-                                 D.ranges.p + nr, nr, d->n_ref, D.keep.p, acc, st));
+  HIPCHK(ctx, launch_depth_check(sh->U.p, R.pos.p, n, sh->utotal, F, d->n_ref, D.keep.p, acc, st));
   HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::DEPTH_BAD, acc, 32, hipMemcpyDeviceToHost, st));
   HIPCHK(ctx, hipStreamSynchronize(st));
-  const uint64_t row = sh->h_ctr[ctr::DEPTH_BAD];
-  if (row != ~0ull) {
-    // only a record that runs past the resident bytes can be cured by more of them
-    if (sh->h_ctr[ctr::DEPTH_PAST] == row && !sh->at_eof)
-      return fail(ctx, SBH_E_NEED_HALO, "record %llu of the scan may run past the shard", (unsigned long long)row);
-    return fail_with(ctx, SBH_E_BAD_RECORD, {(int64_t)row},
-                     "record %llu of the scan does not fit its block or the stream, or its CIGAR or reference is out of range",
-                     (unsigned long long)row);
-  }
+  rc = rows_verdict(sh, sh->h_ctr[ctr::DEPTH_BAD], sh->h_ctr[ctr::DEPTH_PAST], ", or its CIGAR or reference is out of range");
+  if (rc) return rc;
   out->n_kept = sh->h_ctr[ctr::DEPTH_KEPT];
   out->n_unplaced = sh->h_ctr[ctr::DEPTH_UNPLACED];
   if (out->n_kept > out->n_unplaced) {

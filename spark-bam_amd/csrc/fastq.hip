@@ -7,7 +7,8 @@
 //                  SBH_FASTQ_SPLIT) has its own columns len[p][i] and keep[p][i]: the row's line
 //                  length and 1 in the column of its part, 0 in every other column and for a row
 //                  the filter drops.  cls[i] = the class byte.  The first bad row and the first row
-//                  that only runs past the stream go out as per-lane minima behind the loop.
+//                  that only runs past the stream go out as per-lane minima behind the loop
+//                  (RowMinima, sbh_internal.h; the host's rows_verdict reads them).
 //   (scans)        len[p] -> lpre[p], keep[p] -> kpre[p], over n + 1 entries (entry n is 0, so
 //                  entry n of a scan is the column's total)
 //   k_fastq_index  off[i] = (bytes of the parts before p) + lpre[p][i]; the line's place in layout
@@ -43,7 +44,6 @@ namespace sbh {
 namespace {
 
 using sbh_fq::PARTS;
-constexpr uint32_t ROWS_GRID = 1024;  // k_fastq_sizes / _index: 262144 rows a pass, as k_tally_rows
 constexpr uint32_t EMIT_GRID = 16384;  // k_fastq_emit: 65536 rows a pass
 static_assert(sizeof(sbh_fastq_sizes) == sizeof(sbh_fq::Sizes), "fastq_core.h restates the header's layout");
 static_assert(SBH_FASTQ_FASTA == sbh_fq::MODE_FASTA && SBH_FASTQ_SUFFIX == sbh_fq::MODE_SUFFIX &&
@@ -57,15 +57,14 @@ __global__ __launch_bounds__(256) void k_fastq_sizes(const uint8_t *__restrict__
                                                      unsigned long long *past) {
   const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
   const uint32_t np = sbh_fq::n_parts(mode);
-  uint64_t b = ~0ull, ps = ~0ull;
+  RowMinima m;
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step) {
     const uint64_t p = pos[i];
     uint64_t bytes = 0, l = 0;
     uint32_t c = 0;
     const int v = sbh_bam::row_check(U, total, p, &bytes);
     if (v != sbh_bam::ROW_OK) {
-      b = b < i ? b : i;
-      if (v == sbh_bam::ROW_PAST) ps = ps < i ? ps : i;
+      m.refused(i, v == sbh_bam::ROW_PAST);
     } else if (sbh_bam::row_keep(U + p, i, F)) {
       const uint8_t *r = U + p;
       c = sbh_fq::class_of(sbh_sam::ld16(r + 18), mode);
@@ -79,8 +78,7 @@ __global__ __launch_bounds__(256) void k_fastq_sizes(const uint8_t *__restrict__
     }
     cls[i] = (uint8_t)c;
   }
-  if (b != ~0ull) atomicMin(bad, (unsigned long long)b);
-  if (ps != ~0ull) atomicMin(past, (unsigned long long)ps);
+  m.send(bad, past);
 }
 
 // sums: part_bytes[3], part_rows[3] (parts the mode does not have: 0)
@@ -179,8 +177,6 @@ __global__ __launch_bounds__(256) void k_fastq_emit(const uint8_t *__restrict__ 
   }
 }
 
-uint32_t rows_grid(uint64_t n) { return (uint32_t)std::min<uint64_t>((n + 255) / 256, ROWS_GRID); }
-
 }  // namespace
 
 // len, keep: n_parts(mode) x (n + 1) words, entry n of each column zeroed by the caller; bad, past preset ~0
@@ -236,10 +232,10 @@ int sbh_records_fastq_scan(sbh_shard *sh, const sbh_record_filter *filter, uint3
   if (!fastq_args_ok(mode, def_qual))
     return fail(ctx, SBH_E_ARG, "records_fastq_scan: mode 0x%x has unknown bits, or def_qual %d is outside [0, 93]", mode, def_qual);
   sbh_bam::Filter F;
-  if (!bam_filter_of(filter, &F))
-    return fail(ctx, SBH_E_ARG, "record filter: flags < 65536, 0 <= min_mapq <= 255, row ranges sorted, disjoint and non-empty");
-  const uint64_t n = R.sz.n, nr = F.n_row_ranges, np = sbh_fq::n_parts(mode);
-  int rc = set_device(ctx);
+  int rc = row_filter(ctx, filter, &F);
+  if (rc) return rc;
+  const uint64_t n = R.sz.n, np = sbh_fq::n_parts(mode);
+  rc = set_device(ctx);
   if (rc) return rc;
   hipStream_t st = sh->st;
   Q.valid = false;
@@ -254,13 +250,8 @@ int sbh_records_fastq_scan(sbh_shard *sh, const sbh_record_filter *filter, uint3
     for (auto *b : {&Q.off, &Q.rows}) HIPCHK(ctx, b->ensure(n + 1));
     HIPCHK(ctx, Q.cls.ensure(n));
     HIPCHK(ctx, Q.sums.ensure(2 * sbh_fq::PARTS));
-    HIPCHK(ctx, Q.ranges.ensure(2 * nr));
     HIPCHK(ctx, sh->tmp.ensure(scan_tmp_words(n + 1)));
-    if (nr) {
-      HIPCHK(ctx, hipMemcpyAsync(Q.ranges.p, F.row_begin, 8 * nr, hipMemcpyHostToDevice, st));
-      HIPCHK(ctx, hipMemcpyAsync(Q.ranges.p + nr, F.row_end, 8 * nr, hipMemcpyHostToDevice, st));
-    }
-    F.row_begin = Q.ranges.p, F.row_end = Q.ranges.p + nr;
+    HIPCHK(ctx, stage_row_ranges(sh, &F));
     for (uint64_t q = 0; q < np; ++q) {
       HIPCHK(ctx, hipMemsetAsync(Q.len.p + q * (n + 1) + n, 0, 8, st));
       HIPCHK(ctx, hipMemsetAsync(Q.keep.p + q * (n + 1) + n, 0, 8, st));
@@ -277,14 +268,8 @@ int sbh_records_fastq_scan(sbh_shard *sh, const sbh_record_filter *filter, uint3
     HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::FASTQ_BAD, bad, 16, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::H_FASTQ_SUMS, Q.sums.p, 8 * 2 * sbh_fq::PARTS, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
-    const uint64_t row = sh->h_ctr[ctr::FASTQ_BAD];
-    if (row != ~0ull) {
-      // only a record that runs past the resident bytes can be cured by more of them
-      if (sh->h_ctr[ctr::FASTQ_PAST] == row && !sh->at_eof)
-        return fail(ctx, SBH_E_NEED_HALO, "record %llu of the scan may run past the shard", (unsigned long long)row);
-      return fail_with(ctx, SBH_E_BAD_RECORD, {(int64_t)row}, "record %llu of the scan does not fit its block or the stream",
-                       (unsigned long long)row);
-    }
+    rc = rows_verdict(sh, sh->h_ctr[ctr::FASTQ_BAD], sh->h_ctr[ctr::FASTQ_PAST], "");
+    if (rc) return rc;
     for (uint32_t q = 0; q < sbh_fq::PARTS; ++q) {
       sz.part_bytes[q] = sh->h_ctr[ctr::H_FASTQ_SUMS + q];
       sz.part_rows[q] = sh->h_ctr[ctr::H_FASTQ_SUMS + sbh_fq::PARTS + q];

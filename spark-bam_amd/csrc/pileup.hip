@@ -6,7 +6,8 @@
 //                     every op code and the query-length sum; a row with more than PILE_LANE_OPS ops
 //                     is handed to its wave by ballot (lanes stride the ops, one wave sum).  A keep bit
 //                     per row (one ballot word per wave and pass), the smallest bad row and the
-//                     smallest row that only runs past the stream, n_kept, n_unplaced (one atomic per
+//                     smallest row that only runs past the stream (RowMinima, sbh_internal.h; the
+//                     host's rows_verdict reads them), n_kept, n_unplaced (block_add: one atomic per
 //                     workgroup and counter)
 //   k_pile_events     kept rows only.  A lane reads its row's fixed fields, first CIGAR word and span (64
 //                     rows at once, handed on by v_readlane as scalars); the wave then takes
@@ -39,16 +40,11 @@ using sbh_dep::Span;
 using sbh_pile::NCH;
 using sbh_pile::PILE_LANE_OPS;
 using sbh_pile::PILE_TILE;
-constexpr uint32_t ROWS_GRID = 1024;  // the row kernels: 262144 rows a pass, as k_depth_check
 constexpr uint32_t TILE_T = 256;
 constexpr uint32_t TSTAT = 12;  // per tile: max depth, nonzero, covered, called, eight channel sums
 static_assert(PILE_TILE == TILE_T * 4, "a tile is 256 lanes x 4 positions");
 static_assert(sbh_pile::PILE_GROUP == 64, "k_pile_events gives a wave to a read");
 
-__device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
-  for (int m = 1; m < 64; m <<= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, m);
-  return v;
-}
 __device__ __forceinline__ uint64_t wave_max(uint64_t v) {
   for (int m = 1; m < 64; m <<= 1) {
     const uint64_t o = (uint64_t)__shfl_xor((unsigned long long)v, m);
@@ -66,18 +62,6 @@ __device__ __forceinline__ uint64_t wave_incl_scan64(uint32_t v) {
   return (uint64_t)wave_incl_scan(v & 0xffffu) + ((uint64_t)wave_incl_scan(v >> 16) << 16);
 }
 
-// One value per workgroup into *dst: v summed over the 4 waves (every lane calls; s_red: 4 words).
-__device__ __forceinline__ void block_add(uint64_t v, uint64_t *s_red, unsigned long long *dst) {
-  v = wave_sum(v);
-  __syncthreads();  // (s_red may still be read from the call before)
-  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const uint64_t t = s_red[0] + s_red[1] + s_red[2] + s_red[3];
-    if (t) atomicAdd(dst, (unsigned long long)t);
-  }
-}
-
 // keep: one u64 per 64 rows, every word below ceil(n / 64) written.  acc: bad, past (preset ~0),
 // n_kept, n_unplaced (preset 0).
 __global__ __launch_bounds__(256) void k_pile_check(const uint8_t *__restrict__ U, const uint64_t *pos, uint64_t n,
@@ -86,7 +70,8 @@ __global__ __launch_bounds__(256) void k_pile_check(const uint8_t *__restrict__ 
   __shared__ uint64_t s_red[4];
   const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
   const uint32_t lane = threadIdx.x & 63;
-  uint64_t kept = 0, unplaced = 0, bad = ~0ull, past = ~0ull;
+  uint64_t kept = 0, unplaced = 0;
+  RowMinima m;
   // (the loop is uniform in the workgroup: the ballots run with every lane of the wave)
   for (uint64_t base = (uint64_t)blockIdx.x * blockDim.x; base < n; base += step) {
     const uint64_t i = base + threadIdx.x;
@@ -98,15 +83,14 @@ __global__ __launch_bounds__(256) void k_pile_check(const uint8_t *__restrict__ 
       uint64_t bytes = 0;
       const int v = sbh_bam::row_check(U, total, p, &bytes);
       if (v != sbh_bam::ROW_OK) {
-        bad = bad < i ? bad : i;
-        if (v == sbh_bam::ROW_PAST) past = past < i ? past : i;
+        m.refused(i, v == sbh_bam::ROW_PAST);
       } else if (sbh_bam::row_keep(U + p, i, F)) {
         r = U + p;
         ref_id = (int32_t)sbh_bam::ld32(r + 4);
-        if (ref_id >= n_ref) bad = bad < i ? bad : i;
+        if (ref_id >= n_ref) m.rejected(i);
         else if (sbh_dep::n_cigar_of(r) > PILE_LANE_OPS) is_long = true;
         else if (sbh_pile::walk_ok(r)) k = true;
-        else bad = bad < i ? bad : i;
+        else m.rejected(i);
       }
     }
     // the wave's long rows, one at a time (the mask is the same in every lane: uniform loops)
@@ -127,7 +111,7 @@ __global__ __launch_bounds__(256) void k_pile_check(const uint8_t *__restrict__ 
       const bool ok = __ballot(bad_op) == 0 && (ls == 0 || qsum == (uint64_t)ls);
       if ((int)lane == src) {
         if (ok) k = true;
-        else bad = bad < i ? bad : i;
+        else m.rejected(i);
       }
     }
     if (k) {
@@ -137,8 +121,7 @@ __global__ __launch_bounds__(256) void k_pile_check(const uint8_t *__restrict__ 
     const uint64_t word = __ballot(k);
     if (lane == 0 && i < n) keep[i >> 6] = word;
   }
-  if (bad != ~0ull) atomicMin(acc + 0, (unsigned long long)bad);
-  if (past != ~0ull) atomicMin(acc + 1, (unsigned long long)past);
+  m.send(acc + 0, acc + 1);
   block_add(kept, s_red, acc + 2);
   block_add(unplaced, s_red, acc + 3);
 }
@@ -469,7 +452,6 @@ __global__ __launch_bounds__(TILE_T) void k_pile_intervals(const uint8_t *__rest
   }
 }
 
-uint32_t rows_grid(uint64_t n) { return (uint32_t)std::min<uint64_t>((n + 255) / 256, ROWS_GRID); }
 uint64_t pile_tiles(uint64_t S) { return (S + PILE_TILE - 1) / PILE_TILE; }
 
 const sbh_dep::Span *pile_spans(const sbh_depth_span *s) {
@@ -563,22 +545,18 @@ int sbh_records_pileup_add(sbh_shard *sh, sbh_pileup *p, const sbh_record_filter
   if (!R.valid) return fail(ctx, SBH_E_STATE, "records_pileup_add without a records scan");
   if (p->finished) return fail(ctx, SBH_E_STATE, "records_pileup_add after sbh_pileup_finish (sbh_pileup_reset reopens)");
   sbh_bam::Filter F;
-  if (!bam_filter_of(filter, &F))
-    return fail(ctx, SBH_E_ARG, "record filter: flags < 65536, 0 <= min_mapq <= 255, row ranges sorted, disjoint and non-empty");
-  const uint64_t n = R.sz.n, nr = F.n_row_ranges;
+  int rc = row_filter(ctx, filter, &F);
+  if (rc) return rc;
+  const uint64_t n = R.sz.n;
   *out = sbh_pileup_add_result{};
   out->n = n;
   if (!n) return SBH_OK;
-  int rc = set_device(ctx);
+  rc = set_device(ctx);
   if (rc) return rc;
   hipStream_t st = sh->st;
-  auto &D = sh->dep;  // (the keep bits and row ranges of the last depth or pileup add)
+  auto &D = sh->dep;  // (the keep bits of the last depth or pileup add)
   HIPCHK(ctx, D.keep.ensure((n + 63) / 64));
-  HIPCHK(ctx, D.ranges.ensure(2 * nr));
-  if (nr) {
-    HIPCHK(ctx, hipMemcpyAsync(D.ranges.p, F.row_begin, 8 * nr, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(D.ranges.p + nr, F.row_end, 8 * nr, hipMemcpyHostToDevice, st));
-  }
+  HIPCHK(ctx, stage_row_ranges(sh, &F));
   unsigned long long *acc = sh->ctr.p + ctr::PILE_BAD;
   static_assert(ctr::PILE_PAST == ctr::PILE_BAD + 1 && ctr::PILE_KEPT == ctr::PILE_BAD + 2 &&
                     ctr::PILE_UNPLACED == ctr::PILE_BAD + 3 && ctr::PILE_COUNTED == ctr::PILE_BAD + 4 &&
@@ -586,22 +564,14 @@ int sbh_records_pileup_add(sbh_shard *sh, sbh_pileup *p, const sbh_record_filter
                 "two memsets, one copy each way");
   HIPCHK(ctx, hipMemsetAsync(acc, 0xff, 16, st));
   HIPCHK(ctx, hipMemsetAsync(acc + 2, 0, 8 * (ctr::PILE_END - ctr::PILE_KEPT), st));
-  F.row_begin = D.ranges.p, F.row_end = D.ranges.p + nr;
   hipLaunchKernelGGL(k_pile_check, dim3(rows_grid(n)), dim3(256), 0, st, sh->U.p, R.pos.p, n, sh->utotal, F, p->n_ref,
                      D.keep.p, acc);
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::PILE_BAD, acc, 32, hipMemcpyDeviceToHost, st));
   HIPCHK(ctx, hipStreamSynchronize(st));
-  const uint64_t row = sh->h_ctr[ctr::PILE_BAD];
-  if (row != ~0ull) {
-    // only a record that runs past the resident bytes can be cured by more of them
-    if (sh->h_ctr[ctr::PILE_PAST] == row && !sh->at_eof)
-      return fail(ctx, SBH_E_NEED_HALO, "record %llu of the scan may run past the shard", (unsigned long long)row);
-    return fail_with(ctx, SBH_E_BAD_RECORD, {(int64_t)row},
-                     "record %llu of the scan does not fit its block or the stream, or its CIGAR, query length or "
-                     "reference is out of range",
-                     (unsigned long long)row);
-  }
+  rc = rows_verdict(sh, sh->h_ctr[ctr::PILE_BAD], sh->h_ctr[ctr::PILE_PAST],
+                    ", or its CIGAR, query length or reference is out of range");
+  if (rc) return rc;
   out->n_kept = sh->h_ctr[ctr::PILE_KEPT];
   out->n_unplaced = sh->h_ctr[ctr::PILE_UNPLACED];
   if (out->n_kept > out->n_unplaced) {

@@ -3,6 +3,12 @@
 // one file's entry points (sbh_api.hip, api_check.hip, api_records.hip, and the output stages' calls
 // behind the kernels of bai.hip, sam.hip, bam_gather.hip, depth.hip, pileup.hip, tally.hip, fastq.hip, zdeflate.hip) borrow from another's.  Launchers are
 // declared in sbh_internal.h; nothing here is seen by device code.
+//
+// The stages that run over the rows of the last records scan under an sbh_record_filter
+// (bam_gather.hip, depth.hip, pileup.hip, tally.hip, fastq.hip) share one frame, declared at the end
+// of this header and defined in bam_gather.hip: row_filter (the filter and its one message),
+// stage_row_ranges (the device copy of the row ranges, sbh_shard::row_ranges) and rows_verdict (bad
+// row, past row -> SBH_OK / SBH_E_NEED_HALO / SBH_E_BAD_RECORD); the accumulators share sbh::Accum.
 #pragma once
 #include <algorithm>
 #include <cstdio>
@@ -170,6 +176,11 @@ struct sbh_shard {
   sbh::DBuf<uint32_t> opix;  // the full checker's bad-CIGAR-op index (launch_full)
   sbh::DBuf<uint64_t> close_pos;
   sbh::DBuf<uint32_t> close_word;
+  // the device copy of the row ranges of the filtered row stage under way (stage_row_ranges): the
+  // begins, then the ends.  One buffer serves every such stage: each of them synchronises the shard's
+  // stream before it returns and a shard belongs to one thread at a time, so no kernel still reads
+  // the ranges of the call before when the next call overwrites them.
+  sbh::DBuf<uint64_t> row_ranges;
   sbh::DBuf<unsigned long long> ctr;  // scratch counters
   unsigned long long *h_ctr = nullptr;  // pinned mirror
   uint64_t pad = 4096;
@@ -219,9 +230,9 @@ struct sbh_shard {
   } sam;
   // BAM stream of the last scan's selected rows (sbh_records_bam_scan / fetch): per-row lengths and
   // their prefix, keep | run head << 32 and its prefix, the kept rows' offsets and indices, the
-  // runs' (output, U) offsets, the device copy of the row ranges, the stream
+  // runs' (output, U) offsets, the stream
   struct Bam {
-    sbh::DBuf<uint64_t> len, off, kh, khpre, rec_off, rows, run_dst, run_src, ranges;
+    sbh::DBuf<uint64_t> len, off, kh, khpre, rec_off, rows, run_dst, run_src;
     sbh::DBuf<uint8_t> out;
     // coordinate order (bam_sort.hip; sizes in bam_sort_core.h): the two (key, row) arrays the passes
     // alternate between, the digit counts with their scan, the permuted starts and lengths
@@ -233,17 +244,16 @@ struct sbh_shard {
     bool already = false;  // a coordinate-order scan found its kept rows in order (no pass ran)
     bool valid = false;
   } bam;
-  // per-base depth (sbh_records_depth_add): the keep bits of the last add (a ballot word per 64 rows)
-  // and the device copy of the row ranges; the slots live in the sbh_depth
+  // per-base depth and pileup (sbh_records_depth_add, sbh_records_pileup_add): the keep bits of the
+  // last add of either (a ballot word per 64 rows); the slots live in the sbh_depth or sbh_pileup
   struct Depth {
-    sbh::DBuf<uint64_t> keep, ranges;
+    sbh::DBuf<uint64_t> keep;
   } dep;
   // FASTQ / FASTA text of the last scan's selected rows (sbh_records_fastq_scan / fetch): per part of
   // the text (fastq_core.h) the rows' line lengths and keep flags with their prefixes, the class byte,
-  // each row's offset, the lines' offsets and rows in layout order, the parts' totals, the device copy
-  // of the row ranges, the text
+  // each row's offset, the lines' offsets and rows in layout order, the parts' totals, the text
   struct Fastq {
-    sbh::DBuf<uint64_t> len, keep, lpre, kpre, off, rec_off, rows, sums, ranges;
+    sbh::DBuf<uint64_t> len, keep, lpre, kpre, off, rec_off, rows, sums;
     sbh::DBuf<uint8_t> cls;
     sbh::DBuf<char> text;
     sbh_fastq_sizes sz{};
@@ -309,13 +319,30 @@ struct sbh_shard {
   }
 };
 
-// A depth accumulator (sbh_depth_create): owned by a context, fed by any number of its shards.
-// The adds run on the adding shard's stream and synchronise it before they return; reset, finish
-// and the fetches run on a stream of the accumulator's own and synchronise that -- so no two of them
-// ever overlap on the device, and a shard may be destroyed right after its add.
-struct sbh_depth {
+namespace sbh {
+// What the accumulators (sbh_depth, sbh_pileup, sbh_tally) share: the owning context and a stream of
+// the accumulator's own.  The adds run on the adding shard's stream and synchronise it before they
+// return; reset, finish and the fetches run on `st` and synchronise that -- so no two of them ever
+// overlap on the device, and a shard may be destroyed right after its add.
+// drain() is the one destructor body of the three.  The derived destructors call it; it is not
+// ~Accum, because a base is destroyed after the derived struct's members and the DBufs must be freed
+// only once the stream is drained.
+struct Accum {
   sbh_ctx *ctx = nullptr;
   hipStream_t st = nullptr;
+  void drain() {
+    if (ctx) (void)hipSetDevice(ctx->device);
+    if (st) {
+      (void)hipStreamSynchronize(st);
+      (void)hipStreamDestroy(st);
+      st = nullptr;
+    }
+  }
+};
+}  // namespace sbh
+
+// A depth accumulator (sbh_depth_create): owned by a context, fed by any number of its shards.
+struct sbh_depth : sbh::Accum {
   std::vector<sbh_depth_span> spans;
   std::vector<uint64_t> off;  // n_spans + 1: the first slot of each span, then S
   int32_t n_ref = 0;
@@ -328,22 +355,12 @@ struct sbh_depth {
   sbh::DBuf<sbh_depth_run> runs;
   sbh_depth_sizes sz{};
   bool finished = false;
-  ~sbh_depth() {
-    if (ctx) (void)hipSetDevice(ctx->device);
-    if (st) {
-      (void)hipStreamSynchronize(st);
-      (void)hipStreamDestroy(st);
-    }
-  }
+  ~sbh_depth() { drain(); }
 };
 
 // A pileup accumulator (sbh_pileup_create): eight u32 channels per position, owned by a context, fed
-// by any number of its shards.  Streams as sbh_depth's: the adds run on the adding shard's stream
-// (with the shard's depth scratch: keep bits, row ranges) and synchronise it before they return;
-// reset, finish and the fetches run on the accumulator's own stream and synchronise that.
-struct sbh_pileup {
-  sbh_ctx *ctx = nullptr;
-  hipStream_t st = nullptr;
+// by any number of its shards.  An add borrows the adding shard's depth scratch (the keep bits).
+struct sbh_pileup : sbh::Accum {
   std::vector<sbh_depth_span> spans;
   std::vector<uint64_t> off;  // n_spans + 1: the first position of each span, then S
   int32_t n_ref = 0;
@@ -356,34 +373,18 @@ struct sbh_pileup {
   sbh::DBuf<unsigned long long> acc;  // the folded tile stats
   sbh_pileup_sizes sz{};
   bool finished = false;
-  ~sbh_pileup() {
-    if (ctx) (void)hipSetDevice(ctx->device);
-    if (st) {
-      (void)hipStreamSynchronize(st);
-      (void)hipStreamDestroy(st);
-    }
-  }
+  ~sbh_pileup() { drain(); }
 };
 
 // A tally accumulator (sbh_tally_create): flag counts and per-reference counts, owned by a context,
-// fed by any number of its shards.  Streams as sbh_depth's: the adds run on the adding shard's
-// stream and synchronise it before they return; reset and fetch run on the accumulator's own.
-struct sbh_tally {
-  sbh_ctx *ctx = nullptr;
-  hipStream_t st = nullptr;
+// fed by any number of its shards.
+struct sbh_tally : sbh::Accum {
   int32_t n_ref = 0;
   uint64_t words = 0;  // 2 SBH_TALLY_ROWS flag counters, then 2 (n_ref + 1) per-reference counters
   // stage: bad row, past row, then `words` counters of the add under way (k_tally_rows); totals:
   // `words` counters of every add that succeeded (k_tally_commit)
   sbh::DBuf<unsigned long long> stage, totals;
-  sbh::DBuf<uint64_t> ranges;  // the device copy of the last add's row ranges
-  ~sbh_tally() {
-    if (ctx) (void)hipSetDevice(ctx->device);
-    if (st) {
-      (void)hipStreamSynchronize(st);
-      (void)hipStreamDestroy(st);
-    }
-  }
+  ~sbh_tally() { drain(); }
 };
 
 struct StreamCache {
@@ -461,9 +462,20 @@ int records_positions(sbh_shard *sh, uint64_t first, uint64_t E, uint64_t total,
 // a record is malformed or runs past total.
 int records_finish(sbh_shard *sh, uint64_t n, uint64_t total, sbh_records_sizes *out);
 
-// ---- BAM stream (bam_gather.hip) ---------------------------------------------------------------
-// *F = the filter f describes (nullptr: keep every row); false when it is not a valid one.
+// ---- the filtered row stages' shared frame (bam_gather.hip) ------------------------------------
+// *F = the filter f describes (nullptr: keep every row); false when it is not a valid one.  (The
+// *_host entry points call it directly: they have no context to leave a message in.)
 bool bam_filter_of(const sbh_record_filter *f, sbh_bam::Filter *F);
+// bam_filter_of for a call on a context: SBH_OK, or SBH_E_ARG with the one message of every stage.
+int row_filter(sbh_ctx *ctx, const sbh_record_filter *f, sbh_bam::Filter *F);
+// Copies the host row ranges of *F to sh->row_ranges on the shard's stream (two copies; none without
+// ranges) and points F->row_begin / row_end at the copy.  The caller synchronises the stream before
+// it returns: until then its arrays are the copies' source.
+hipError_t stage_row_ranges(sbh_shard *sh, sbh_bam::Filter *F);
+// What a stage returns for the two words its row kernel sent back (sbh::RowMinima): bad = the first
+// row refused (~0: none, SBH_OK), past = the first row refused only because it runs past the stream.
+// `also` ends the SBH_E_BAD_RECORD message with what the stage refuses beyond row_check ("": nothing).
+int rows_verdict(sbh_shard *sh, uint64_t bad, uint64_t past, const char *also);
 
 }  // namespace sbh
 

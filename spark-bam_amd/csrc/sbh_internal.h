@@ -23,6 +23,51 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x) {
   return x;
 }
 
+// v summed over the 64 lanes of a wave, in every lane
+__device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
+  for (int m = 1; m < 64; m <<= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, m);
+  return v;
+}
+
+// One value per workgroup of 256 into *dst: v summed over the 4 waves (every lane calls; s_red: 4 words).
+__device__ __forceinline__ void block_add(uint64_t v, uint64_t *s_red, unsigned long long *dst) {
+  v = wave_sum(v);
+  __syncthreads();  // (s_red may still be read from the call before)
+  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const uint64_t t = s_red[0] + s_red[1] + s_red[2] + s_red[3];
+    if (t) atomicAdd(dst, (unsigned long long)t);
+  }
+}
+
+// The opening of a filtered row kernel (bam_gather.hip, depth.hip, pileup.hip, tally.hip, fastq.hip):
+// a lane's smallest bad row and its smallest row that is bad only because it runs past the stream,
+// kept over the lane's whole loop and sent out once behind it.  The host's rows_verdict reads the
+// two words: they are equal exactly when more resident bytes may cure the first bad row.
+struct RowMinima {
+  uint64_t bad = ~0ull, past = ~0ull;
+  // row i failed row_check; only_past: its verdict was ROW_PAST
+  __device__ __forceinline__ void refused(uint64_t i, bool only_past) {
+    bad = bad < i ? bad : i;
+    if (only_past) past = past < i ? past : i;
+  }
+  // row i is valid and kept, but the stage itself refuses it (reference or CIGAR out of range)
+  __device__ __forceinline__ void rejected(uint64_t i) { bad = bad < i ? bad : i; }
+  // bad_out, past_out: preset ~0 by the caller
+  __device__ __forceinline__ void send(unsigned long long *bad_out, unsigned long long *past_out) const {
+    if (bad != ~0ull) atomicMin(bad_out, (unsigned long long)bad);
+    if (past != ~0ull) atomicMin(past_out, (unsigned long long)past);
+  }
+};
+
+// The grid of a kernel that takes one row per lane, grid-stride, in workgroups of 256: 262144 rows a pass.
+constexpr uint32_t ROWS_GRID = 1024;
+inline uint32_t rows_grid(uint64_t n) {
+  const uint64_t g = (n + 255) / 256;
+  return (uint32_t)(g < ROWS_GRID ? g : ROWS_GRID);
+}
+
 // v from lane ^ M: quad DPP for 1 and 2, ds_swizzle (bit mode, within 32 lanes) for 4..16,
 // ds_bpermute for 32.
 template <uint32_t M>

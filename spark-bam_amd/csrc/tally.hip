@@ -6,7 +6,8 @@
 //                   counting in one pass over each record's fixed bytes.  It counts into the
 //                   accumulator's staging words (zero before every add), never into the totals:
 //                     the smallest bad row and the smallest row that only runs past the stream
-//                       (atomicMin, as k_depth_check records them);
+//                       (RowMinima, sbh_internal.h, as every filtered row kernel records them; the
+//                       host's rows_verdict reads them);
 //                     the 32 flag counters as ballot + popcount into wave-uniform registers over the
 //                       whole loop (per row both columns together, and the QC-fail column only in
 //                       a round that holds such a row), combined through LDS and sent out once per
@@ -32,7 +33,6 @@ namespace {
 
 using sbh_tal::TALLY_LDS_BINS;
 using sbh_tal::TALLY_ROWS;
-constexpr uint32_t ROWS_GRID = 1024;          // 262144 rows a pass, as k_depth_check
 constexpr uint32_t FLAG_WORDS = 2 * TALLY_ROWS;
 // the staging words: bad, past, the flag counters, the per-reference counters
 constexpr uint32_t ST_BAD = 0, ST_PAST = 1, ST_FLAG = 2, ST_REF = ST_FLAG + FLAG_WORDS;
@@ -59,7 +59,7 @@ __global__ __launch_bounds__(256) void k_tally_rows(const uint8_t *__restrict__ 
     __syncthreads();
   }
   const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
-  uint64_t bad = ~0ull, past = ~0ull;
+  RowMinima m;
   // wave-uniform: per row the kept rows of both columns, and those of the QC-fail column.  32 bits
   // hold them: a wave sees at most 64 rows a pass of 262144, and the launcher refuses n >= 2^43
   uint32_t all[TALLY_ROWS], fail[TALLY_ROWS];
@@ -77,13 +77,12 @@ __global__ __launch_bounds__(256) void k_tally_rows(const uint8_t *__restrict__ 
       uint64_t bytes = 0;
       const int v = sbh_bam::row_check(U, total, p, &bytes);
       if (v != sbh_bam::ROW_OK) {
-        bad = bad < i ? bad : i;
-        if (v == sbh_bam::ROW_PAST) past = past < i ? past : i;
+        m.refused(i, v == sbh_bam::ROW_PAST);
       } else if (sbh_bam::row_keep(U + p, i, F)) {
         const uint8_t *r = U + p;
         tid = (int32_t)sbh_bam::ld32(r + 4);
         if (tid >= n_ref) {
-          bad = bad < i ? bad : i;
+          m.rejected(i);
         } else {
           k = true;
           fl = sbh_bam::ld32(r + 16) >> 16;
@@ -125,8 +124,7 @@ __global__ __launch_bounds__(256) void k_tally_rows(const uint8_t *__restrict__ 
     if (run_m) count(2 * run_bin, run_m);
     if (run_u) count(2 * run_bin + 1, run_u);
   }
-  if (bad != ~0ull) atomicMin(stage + ST_BAD, (unsigned long long)bad);
-  if (past != ~0ull) atomicMin(stage + ST_PAST, (unsigned long long)past);
+  m.send(stage + ST_BAD, stage + ST_PAST);
   if (lane == 0) {
 #pragma unroll
     for (uint32_t c = 0; c < TALLY_ROWS; ++c) s_flag[wave][2 * c] = all[c] - fail[c], s_flag[wave][2 * c + 1] = fail[c];
@@ -158,15 +156,13 @@ static hipError_t launch_tally_rows(const uint8_t *U, const uint64_t *pos, uint6
                                     int32_t n_ref, unsigned long long *stage, hipStream_t st) {
   if (!n) return hipSuccess;
   if (n >> 43) return hipErrorInvalidValue;  // (k_tally_rows' 32-bit wave counters; no memory holds 2^43 records)
-  const uint32_t grid = (uint32_t)std::min<uint64_t>((n + 255) / 256, ROWS_GRID);
-  hipLaunchKernelGGL(k_tally_rows, dim3(grid), dim3(256), 0, st, U, pos, n, total, F, n_ref, 2 * ((uint64_t)n_ref + 1), stage);
+  hipLaunchKernelGGL(k_tally_rows, dim3(rows_grid(n)), dim3(256), 0, st, U, pos, n, total, F, n_ref, 2 * ((uint64_t)n_ref + 1), stage);
   return hipGetLastError();
 }
 
 static hipError_t launch_tally_commit(unsigned long long *totals, const unsigned long long *staged, uint64_t m,
                                       hipStream_t st) {
-  const uint32_t grid = (uint32_t)std::min<uint64_t>((m + 255) / 256, ROWS_GRID);
-  hipLaunchKernelGGL(k_tally_commit, dim3(grid), dim3(256), 0, st, totals, staged, m);
+  hipLaunchKernelGGL(k_tally_commit, dim3(rows_grid(m)), dim3(256), 0, st, totals, staged, m);
   return hipGetLastError();
 }
 
@@ -229,20 +225,15 @@ int sbh_records_tally_add(sbh_shard *sh, sbh_tally *t, const sbh_record_filter *
   auto &R = sh->rec;
   if (!R.valid) return fail(ctx, SBH_E_STATE, "records_tally_add without a records scan");
   sbh_bam::Filter F;
-  if (!bam_filter_of(filter, &F))
-    return fail(ctx, SBH_E_ARG, "record filter: flags < 65536, 0 <= min_mapq <= 255, row ranges sorted, disjoint and non-empty");
-  const uint64_t n = R.sz.n, nr = F.n_row_ranges;
+  int rc = row_filter(ctx, filter, &F);
+  if (rc) return rc;
+  const uint64_t n = R.sz.n;
   *out = sbh_tally_add_result{n, 0};
   if (!n) return SBH_OK;
-  int rc = set_device(ctx);
+  rc = set_device(ctx);
   if (rc) return rc;
   hipStream_t st = sh->st;
-  HIPCHK(ctx, t->ranges.ensure(2 * nr));
-  if (nr) {
-    HIPCHK(ctx, hipMemcpyAsync(t->ranges.p, F.row_begin, 8 * nr, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(t->ranges.p + nr, F.row_end, 8 * nr, hipMemcpyHostToDevice, st));
-  }
-  F.row_begin = t->ranges.p, F.row_end = t->ranges.p + nr;
+  HIPCHK(ctx, stage_row_ranges(sh, &F));
   static_assert(ST_BAD == 0 && ST_PAST == 1 && ST_FLAG == 2 && ctr::H_TALLY_PAST == ctr::H_TALLY_BAD + 1 &&
                     ctr::H_TALLY_KEPT == ctr::H_TALLY_BAD + 2,
                 "two memsets, one copy back: bad, past, total[QC-pass], total[QC-fail]");
@@ -251,15 +242,8 @@ int sbh_records_tally_add(sbh_shard *sh, sbh_tally *t, const sbh_record_filter *
   HIPCHK(ctx, launch_tally_rows(sh->U.p, R.pos.p, n, sh->utotal, F, t->n_ref, t->stage.p, st));
   HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::H_TALLY_BAD, t->stage.p, 32, hipMemcpyDeviceToHost, st));
   HIPCHK(ctx, hipStreamSynchronize(st));
-  const uint64_t row = sh->h_ctr[ctr::H_TALLY_BAD];
-  if (row != ~0ull) {
-    // only a record that runs past the resident bytes can be cured by more of them
-    if (sh->h_ctr[ctr::H_TALLY_PAST] == row && !sh->at_eof)
-      return fail(ctx, SBH_E_NEED_HALO, "record %llu of the scan may run past the shard", (unsigned long long)row);
-    return fail_with(ctx, SBH_E_BAD_RECORD, {(int64_t)row},
-                     "record %llu of the scan does not fit its block or the stream, or its reference is out of range",
-                     (unsigned long long)row);
-  }
+  rc = rows_verdict(sh, sh->h_ctr[ctr::H_TALLY_BAD], sh->h_ctr[ctr::H_TALLY_PAST], ", or its reference is out of range");
+  if (rc) return rc;
   out->n_kept = sh->h_ctr[ctr::H_TALLY_KEPT] + sh->h_ctr[ctr::H_TALLY_KEPT + 1];
   if (out->n_kept) {
     HIPCHK(ctx, launch_tally_commit(t->totals.p, t->stage.p + ST_FLAG, t->words, st));
