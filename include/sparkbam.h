@@ -140,7 +140,9 @@ int sbh_shard_destroy(sbh_shard *sh);
 /* Replace a shard's resident bytes with [file_offset, file_offset + n) of the same file (same
  * file_size), keeping its device allocations (grow-only): a window sliding along a file
  * (jni/Native.scala GpuWindow, sbh_check_stream) reuses one shard instead of allocating per
- * window.  Index, inflate and checker state are reset; the contig lengths are kept. */
+ * window.  Index, inflate and checker state are reset, and the last records scan with everything
+ * derived from it (see "What a shard remembers" at sbh_index); the contig lengths are kept.  No
+ * result of a later call depends on what the buffers held for the bytes before. */
 int sbh_shard_load(sbh_shard *sh, const void *comp, uint64_t n, uint64_t file_offset, int comp_on_device);
 /* Device pointer of the resident compressed bytes (padded). */
 const void *sbh_shard_comp_device_ptr(sbh_shard *sh);
@@ -152,7 +154,28 @@ int sbh_find_block_start(sbh_shard *sh, uint64_t start, int32_t bgzf_blocks_to_c
 
 /* MetadataStream from `start` (MetadataStream.scala:16-58) over the resident bytes:
  * builds the device block table (the chain of blocks from start, empty blocks
- * included and flagged) and the flat layout.  start must be a block start. */
+ * included and flagged) and the flat layout.  start must be a block start.
+ *
+ * What a shard remembers, and what forgets it.  A shard keeps the results of its stages on the
+ * device so that the next stage can use them; each event below voids what was derived from the
+ * state it replaces, and a call that needs a voided result returns SBH_E_STATE -- never a value
+ * computed from the old bytes or the old flat offsets:
+ *   sbh_shard_load, sbh_index, sbh_run_shard (which indexes; sbh_split_records and the batch run
+ *     it): every flat offset is rebased, so the inflated bytes, the eager bitmap and the chain
+ *     proof are void, and so are the last records scan (sbh_records_scan, _scan_regions,
+ *     sbh_split_records*) and everything derived from it: its columns, the SAM text, the BAM
+ *     stream, the FASTQ text, and the BAI scan.  sbh_index voids them even when it is given the
+ *     start it was given before, and even when it then fails.
+ *   sbh_inflate again: the same bytes at the same offsets; the scan and what was derived from it
+ *     stay valid, the eager bitmap and the chain proof are void.
+ *   sbh_set_contigs (the same lengths or others): the eager bitmap, the chain proof and the BAI
+ *     scan are void; the records scan, the SAM text, the BAM stream and the FASTQ text stay valid.
+ *   a new records scan: the SAM text, the BAM stream and the FASTQ text are void (the BAI scan,
+ *     which walks a range of its own, is not); a records scan that fails leaves no valid scan.
+ *   a stage call refused for its arguments (SBH_E_ARG: a bad record filter) voids nothing: the
+ *     stage's last good result is still there.
+ * The accumulators (sbh_depth, sbh_pileup, sbh_tally) belong to the context, not to a shard: none
+ * of these events touches what they hold, and an add that returns SBH_E_STATE adds nothing. */
 int sbh_index(sbh_shard *sh, uint64_t start, uint64_t *n_blocks, uint64_t *flat_size);
 int sbh_get_blocks(sbh_shard *sh, uint64_t first, uint64_t count, sbh_block *out);
 
@@ -285,6 +308,8 @@ typedef struct {
   int32_t anomalies;     /* chain/bitmap disagreements resolved by the walk   */
 } sbh_shard_result;
 
+/* (The run indexes the shard from index_start: like sbh_index it invalidates the last records scan
+ * and everything derived from it -- see "What a shard remembers" at sbh_index.) */
 int sbh_run_shard(sbh_shard *sh, uint64_t index_start, uint64_t own_end_file,
                   int32_t reads_to_check, int32_t max_read_size, sbh_shard_result *res);
 
@@ -439,6 +464,9 @@ typedef struct {
                                                               position (canonical Pos, Pos.scala:12-43);
                                                               available after sbh_split_records too */
 } sbh_records_out;
+/* A scan is valid until the next scan, sbh_shard_load, sbh_index or sbh_run_shard; a scan that fails
+ * leaves none.  The fetch and every stage over "the rows of the last scan" return SBH_E_STATE without
+ * a valid one (see "What a shard remembers" at sbh_index). */
 int sbh_records_scan(sbh_shard *sh, uint64_t first_flat, uint64_t end_flat, sbh_records_sizes *out);
 int sbh_records_fetch(sbh_shard *sh, const sbh_records_out *out);
 
@@ -564,6 +592,9 @@ typedef struct {
 typedef struct {
   uint64_t n_records, n_runs, n_no_coor, lin_size;
 } sbh_bai_sizes;
+/* The scan's result (sbh_bai_fetch, sbh_bai_edges) is valid until the next sbh_bai_scan,
+ * sbh_set_contigs, sbh_shard_load, sbh_index or sbh_run_shard; SBH_E_STATE after any of them.  A
+ * records scan does not touch it. */
 int sbh_bai_scan(sbh_shard *sh, uint64_t first_flat, uint64_t end_flat, sbh_bai_sizes *out);
 /* runs: n_runs entries; lin: lin_size entries (either may be NULL). */
 int sbh_bai_fetch(sbh_shard *sh, sbh_bai_run *runs, uint64_t *lin);
@@ -616,7 +647,9 @@ int sbh_bai_build(const sbh_bai_run *runs, uint64_t n_runs, const uint64_t *lin,
  * SBH_E_BAD_RECORD {row} for the first row whose CIGAR has an op code above 8 (htsjdk throws) or
  * whose tag area is malformed: an unknown type or B sub-type byte, a value running past the
  * record's tag bytes, a Z / H without a NUL inside them, a negative B count, 1 or 2 bytes left
- * after the last tag.  n == 0 gives text_bytes = 0 and line_off = [0]. */
+ * after the last tag.  n == 0 gives text_bytes = 0 and line_off = [0].
+ * A new scan, sbh_shard_load, sbh_index or sbh_run_shard invalidates the text (the fetch then
+ * returns SBH_E_STATE); sbh_inflate and sbh_set_contigs do not. */
 typedef struct { uint64_t n, text_bytes, n_host; } sbh_sam_sizes;
 int sbh_records_sam_scan(sbh_shard *sh, const char *ref_names, const uint64_t *ref_name_off,
                          int32_t n_ref, sbh_sam_sizes *out);
@@ -646,8 +679,10 @@ int sbh_sam_render_host(const uint8_t *flat, uint64_t flat_size, const uint64_t 
  * head: host memory copied to the front of the stream (the BAM header bytes, or the unfinished
  * tail of an earlier window's stream when a file is written window by window: BGZF members are
  * cut every 65498 bytes of the whole stream); rec_off[0] == head_bytes.
- * The call leaves the scan's rows, columns and SAM text as they are; a new scan or sbh_shard_load
- * invalidates the BAM stream.  It synchronises the shard's stream before it returns, so the
+ * The call leaves the scan's rows, columns and SAM text as they are; a new scan, sbh_shard_load,
+ * sbh_index or sbh_run_shard invalidates the BAM stream (and the scan it was built from: the next
+ * sbh_records_bam_scan returns SBH_E_STATE until there is a new scan); a call refused with SBH_E_ARG
+ * leaves the last stream in place.  It synchronises the shard's stream before it returns, so the
  * context-level compress call may follow directly on sbh_records_bam_device_ptr (NULL without a
  * valid BAM scan).  sbh_records_bam_fetch copies out what is asked for (any pointer may be NULL).
  * Errors: SBH_E_STATE without a valid scan; SBH_E_ARG for a filter outside the ranges below or
@@ -912,7 +947,8 @@ int sbh_tally_add_host(const uint8_t *flat, uint64_t flat_size, const uint64_t *
  * (decode == 0 is enough); every row, kept or not, is validated as there.  The scan call leaves the
  * scan's rows, columns, SAM text and BAM stream alone and synchronises the shard's stream before it
  * returns, so the context-level compress call may follow directly on the device pointer (NULL
- * without a valid FASTQ scan); a new scan or a load of the shard invalidates the text.  The fetch
+ * without a valid FASTQ scan); a new scan, sbh_shard_load, sbh_index or sbh_run_shard invalidates
+ * the text, and the last three the scan itself.  The fetch
  * copies out what is asked for (any pointer may be NULL): the text, rec_off (n_kept + 1: where each
  * line begins, in the text's order, then text_bytes) and rows (n_kept: the scan row of each line).
  * Errors: SBH_E_STATE without a valid scan; SBH_E_ARG for unknown mode bits, def_qual outside

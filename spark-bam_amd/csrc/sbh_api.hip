@@ -457,6 +457,13 @@ int sbh_index(sbh_shard *sh, uint64_t start, uint64_t *n_blocks, uint64_t *flat_
   if (rc) return rc;
   sh->sieve_nref1 = 0;
   sh->indexed = sh->inflated = sh->bits_valid = sh->chain_ok = sh->cm_valid = false;
+  // a new index rebases every flat offset: the last scan's positions, and what was rendered from
+  // them, describe a stream that is no longer there (what resident_changed voids of them)
+  sh->rec.valid = sh->rec.decoded = false;
+  sh->bai.valid = false;
+  sh->sam.valid = false;
+  sh->bam.valid = false;
+  sh->fq.valid = false;
   sh->ncand = 0;
   const uint64_t rel = start - sh->file_off;
   const uint64_t n = sh->n;

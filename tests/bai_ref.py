@@ -167,8 +167,11 @@ def serialise(n_ref, bins_of, meta_of, lin_of, n_no_coor):
     return b"".join(o)
 
 
-def build(data):
+def build(data, rows=None):
+    """rows = (a, b): only records [a, b) of the file are pushed (a scan of a sub-range)."""
     recs, lens = records_of(data)
+    if rows is not None:
+        recs = recs[rows[0]:rows[1]]
     n_ref = len(lens)
     lin_off = [0]
     for ln in lens:
