@@ -1509,187 +1509,217 @@ __device__ __forceinline__ LaneRun redo_asm(const WaveSmem &t, const uint32_t *s
 #ifndef SBH_ASM_EMIT
 #define SBH_ASM_EMIT 1  // pass 3 (RUN_EMIT over the LDS stage) as the hand-written loop below
 #endif
-// RUN_EMIT over the LDS stage as hand-written code (lane_run<RUN_EMIT>'s results): the decode
-// loop of spec_asm without the checkpoints, each token stored once (a literal at its code, a
-// match at its distance code) through a 32-bit offset from the block's token base `tk` (wave-
-// uniform).  A lane's tokens leave four at a time (16-byte stores from v124..v127; A/B r05m/r05n
-// against one 4-byte store per token: k_huff -7% E, +-0.2% B and D).  No too-far-back test per
-// distance code: k_lz tests each match token once, so `bad` comes back unchanged and the token /
-// byte counts that fed the test are not kept (the operands stay: the register assignment is
-// part of the measured loop).
-// (removed: the per-distance test here; measured and removed: the single-token stores.)
+// RUN_EMIT over the LDS stage as hand-written code (lane_run<RUN_EMIT>'s tokens): one token per
+// lane and loop iteration.  An iteration decodes a literal / length entry as spec_asm does (no
+// checkpoints); the lanes that hold a length code then decode its distance code in the same
+// iteration -- the window moves on, a second lookup in the distance table (long codes through
+// pk / sent, an entry that is no code leaves the loop without a token), and the match token is
+// built from both -- so the loop top is always a token boundary and the cut test needs no state:
+// a token whose first code starts before `stop` is the lane's.  The wave runs the distance part
+// whenever any lane holds a length code.
+// Every lane still in the loop has therefore produced the same number of tokens.  The loop is
+// unrolled by four: iteration j writes its token straight into v124 + j, and after the fourth
+// one 16-byte store per lane (all the loop's lanes together) puts them at the lane's `voff`, a
+// 32-bit offset from the block's token base `tk` (wave-uniform).  A lane that leaves in iteration
+// j of a group keeps its j tokens in v124.. (its exec bit is off from then on); sX1..sX3 collect
+// those lanes, and after the loop they write their 1-3 tokens with dword stores at their `voff`.
+// No too-far-back test per distance code: k_lz tests each match token once.
+// (measured and removed: the single-token stores; a per-lane four-token shift queue flushed when
+// the lane's own count reached four, one code per iteration -- the lanes' counts drift apart at
+// length codes, so the wave issued a partly filled 16-byte store in nearly every iteration.)
+// The long-code resolution (slow_lane's arithmetic, as in spec_asm) for the lanes in sS, whose
+// entry is in e and stream bits in `bits`: PK the kind's pk[kind][11], SENT its part of sent[].
+// Leaves the special lanes in sD.
+#define SBH_EMIT_SLOW(PK, SENT)                                                                        \
+      "s_and_saveexec_b64 %[sS], %[sS]\n\t"                                                            \
+      "v_bfrev_b32 %[r15], %[bits]\n\t"                                                                \
+      "v_lshrrev_b32 %[r15], 17, %[r15]\n\t"                                                           \
+      "v_mov_b32 %[q], " PK "\n\t"                                                                     \
+      "ds_read_b32 %[p11], %[q]\n\t"                                                                   \
+      "ds_read_b32 %[p12], %[q] offset:4\n\t"                                                          \
+      "ds_read_b32 %[p13], %[q] offset:8\n\t"                                                          \
+      "ds_read_b32 %[p14], %[q] offset:12\n\t"                                                         \
+      "ds_read_b32 %[p15], %[q] offset:16\n\t"                                                         \
+      "s_waitcnt lgkmcnt(0)\n\t"                                                                       \
+      "v_mov_b32 %[d], %[p11]\n\t"                                                                     \
+      "v_mov_b32 %[sh], 4\n\t"                                                                         \
+      "v_lshrrev_b32 %[tmp], 16, %[p11]\n\t"                                                           \
+      "v_cmp_le_u32 vcc, %[tmp], %[r15]\n\t"                                                           \
+      "s_nop 1\n\t"                                                                                    \
+      "v_cndmask_b32_e32 %[d], %[d], %[p12], vcc\n\t"                                                  \
+      "v_cndmask_b32_e64 %[sh], %[sh], 3, vcc\n\t"                                                     \
+      "v_lshrrev_b32 %[tmp], 16, %[p12]\n\t"                                                           \
+      "v_cmp_le_u32 vcc, %[tmp], %[r15]\n\t"                                                           \
+      "s_nop 1\n\t"                                                                                    \
+      "v_cndmask_b32_e32 %[d], %[d], %[p13], vcc\n\t"                                                  \
+      "v_cndmask_b32_e64 %[sh], %[sh], 2, vcc\n\t"                                                     \
+      "v_lshrrev_b32 %[tmp], 16, %[p13]\n\t"                                                           \
+      "v_cmp_le_u32 vcc, %[tmp], %[r15]\n\t"                                                           \
+      "s_nop 1\n\t"                                                                                    \
+      "v_cndmask_b32_e32 %[d], %[d], %[p14], vcc\n\t"                                                  \
+      "v_cndmask_b32_e64 %[sh], %[sh], 1, vcc\n\t"                                                     \
+      "v_lshrrev_b32 %[tmp], 16, %[p14]\n\t"                                                           \
+      "v_cmp_le_u32 vcc, %[tmp], %[r15]\n\t"                                                           \
+      "s_nop 1\n\t"                                                                                    \
+      "v_cndmask_b32_e32 %[d], %[d], %[p15], vcc\n\t"                                                  \
+      "v_cndmask_b32_e64 %[sh], %[sh], 0, vcc\n\t"                                                     \
+      "v_lshrrev_b32 %[tmp], %[sh], %[r15]\n\t" /* (d + (rev15 >> (15 - len))) & 0xffff */             \
+      "v_add_u32 %[tmp], %[tmp], %[d]\n\t"                                                             \
+      "v_and_b32 %[tmp], 0xffff, %[tmp]\n\t"                                                           \
+      "v_min_u32 %[tmp], 0x13f, %[tmp]\n\t" /* (inside sent[]; past it: invalid, replaced below) */    \
+      "v_lshl_add_u32 %[tmp], %[tmp], 2, " SENT "\n\t"                                                 \
+      "ds_read_b32 %[e], %[tmp]\n\t"                                                                   \
+      "v_lshrrev_b32 %[tmp], 16, %[p15]\n\t"                                                           \
+      "v_cmp_ge_u32 vcc, %[r15], %[tmp]\n\t"                                                           \
+      "s_waitcnt lgkmcnt(0)\n\t"                                                                       \
+      "s_nop 1\n\t"                                                                                    \
+      "v_cndmask_b32_e32 %[e], %[e], %[bad_e], vcc\n\t"                                                \
+      "s_mov_b64 exec, %[sS]\n\t"                                                                      \
+      "v_cmp_gt_i32 %[sD], 0, %[e]\n\t" /* special after the long-code lookup */
+// The entry at the window (table base TAB) into e, the stream dword after the window into nx.
+#define SBH_EMIT_LOOKUP(TAB)                                                                           \
+      "v_alignbit_b32 %[bits], %[hi], %[lo], %[pos]\n\t"                                               \
+      "v_and_b32 %[a], 0x3ff, %[bits]\n\t"                                                             \
+      "v_lshl_add_u32 %[a], %[a], 2, " TAB "\n\t"                                                      \
+      "ds_read_b32 %[e], %[a]\n\t"                                                                     \
+      "v_lshrrev_b32 %[a], 5, %[pos]\n\t"                                                              \
+      "v_lshl_add_u32 %[a], %[a], 2, %[stb]\n\t"                                                       \
+      "ds_read_b32 %[nx], %[a]\n\t"
+// The code's value into val, the position past it (and its extra bits) into np and pos; vcc: the
+// window moves on by a dword (lo / hi follow once nx has arrived).
+#define SBH_EMIT_VALUE                                                                                 \
+      "v_and_b32 %[tmp], 31, %[e]\n\t"                                                                 \
+      "v_bfe_u32 %[x], %[e], 5, 4\n\t"                                                                 \
+      "v_bfe_u32 %[ex], %[bits], %[e], %[x]\n\t"                                                       \
+      "v_add3_u32 %[np], %[pos], %[tmp], %[x]\n\t"                                                     \
+      "v_add_u32_sdwa %[val], %[ex], %[e] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_1\n\t" \
+      "v_xor_b32 %[tmp], %[np], %[pos]\n\t"                                                            \
+      "v_cmp_lt_u32 vcc, 31, %[tmp]\n\t"                                                               \
+      "v_mov_b32 %[pos], %[np]\n\t"
+#define SBH_EMIT_WINDOW                                                                                \
+      "s_waitcnt lgkmcnt(0)\n\t"                                                                       \
+      "v_cndmask_b32_e32 %[lo], %[lo], %[hi], vcc\n\t"                                                 \
+      "v_cndmask_b32_e32 %[hi], %[hi], %[nx], vcc\n\t"
+// Iteration J of a group (token register VT); XJ: the lanes leaving here keep J tokens.
+#define SBH_EMIT_ITER(J, VT, XJ)                                                                       \
+      "L_it" J "_%=:\n\t"                                                                              \
+      SBH_EMIT_LOOKUP("%[tabb]")                                                                       \
+      "v_cmp_ge_u32 %[sC], %[pos], %[stop]\n\t" /* the cut: the token would start past the slice */    \
+      "s_waitcnt lgkmcnt(1)\n\t"                                                                       \
+      "v_cmp_gt_i32 %[sD], 0, %[e]\n\t" /* special entries */                                          \
+      "s_and_b64 %[sD], %[sD], exec\n\t"                                                               \
+      "s_cbranch_scc0 L_nosp" J "_%=\n\t"                                                              \
+      "v_and_b32 %[tmp], 0x4000, %[e]\n\t" /* PE_SLOW */                                               \
+      "v_cmp_ne_u32 %[sS], 0, %[tmp]\n\t"                                                              \
+      "s_and_b64 %[sS], %[sS], %[sD]\n\t"                                                              \
+      "s_cbranch_scc0 L_nosp" J "_%=\n\t"                                                              \
+      SBH_EMIT_SLOW("%[pkl]", "%[sentb]")                                                              \
+      "\nL_nosp" J "_%=:\n\t"                                                                          \
+      /* lanes at their cut or a special entry leave the loop */                                       \
+      "s_or_b64 %[sD], %[sD], %[sC]\n\t"                                                               \
+      XJ                                                                                               \
+      "s_andn2_b64 exec, exec, %[sD]\n\t"                                                              \
+      "s_cbranch_execz L_end%=\n\t"                                                                    \
+      SBH_EMIT_VALUE                                                                                   \
+      "v_and_b32 %[q], 0x1000, %[e]\n\t" /* PE_LEN */                                                  \
+      /* the token of a literal (byte << 8) or a pair (byte2's bit 7 and TOK_PAIR from the entry) */   \
+      "v_lshlrev_b32 " VT ", 8, %[val]\n\t"                                                            \
+      "v_cmp_ne_u32 %[sL], 0, %[q]\n\t"                                                                \
+      "v_and_b32 %[tmp], 0x600, %[e]\n\t"                                                              \
+      "v_lshl_or_b32 " VT ", %[tmp], 14, " VT "\n\t"                                                   \
+      SBH_EMIT_WINDOW                                                                                  \
+      "s_and_b64 %[sL], %[sL], exec\n\t"                                                               \
+      "s_cbranch_scc0 L_nolen" J "_%=\n\t"                                                             \
+      /* the lanes with a length code: its distance code, and the match token from both */            \
+      "s_and_saveexec_b64 %[sM], %[sL]\n\t"                                                            \
+      "v_lshl_add_u32 %[ml], %[val], 16, %[mlk]\n\t" /* TOK_MATCH | length << 16 */                    \
+      SBH_EMIT_LOOKUP("%[tabd]")                                                                       \
+      "s_waitcnt lgkmcnt(1)\n\t"                                                                       \
+      "v_cmp_gt_i32 %[sD], 0, %[e]\n\t"                                                                \
+      "s_and_b64 %[sD], %[sD], exec\n\t"                                                               \
+      "s_cbranch_scc0 L_dok" J "_%=\n\t"                                                               \
+      "v_and_b32 %[tmp], 0x4000, %[e]\n\t"                                                             \
+      "v_cmp_ne_u32 %[sS], 0, %[tmp]\n\t"                                                              \
+      "s_and_b64 %[sS], %[sS], %[sD]\n\t"                                                              \
+      "s_cbranch_scc0 L_dsp" J "_%=\n\t"                                                               \
+      SBH_EMIT_SLOW("%[pkd]", "%[sentd]")                                                              \
+      "s_and_b64 %[sD], %[sD], exec\n\t"                                                               \
+      "s_cbranch_scc0 L_dok" J "_%=\n"                                                                 \
+      "L_dsp" J "_%=:\n\t" /* no distance code: these lanes leave, their length code without a token */ \
+      "s_waitcnt lgkmcnt(0)\n\t"                                                                       \
+      XJ                                                                                               \
+      "s_andn2_b64 %[sM], %[sM], %[sD]\n\t"                                                            \
+      "s_cbranch_scc0 L_end%=\n\t"                                                                     \
+      "s_andn2_b64 exec, exec, %[sD]\n\t"                                                              \
+      "s_cbranch_execz L_dend" J "_%=\n"                                                               \
+      "L_dok" J "_%=:\n\t"                                                                             \
+      SBH_EMIT_VALUE                                                                                   \
+      "v_or_b32 " VT ", %[ml], %[val]\n\t"                                                             \
+      SBH_EMIT_WINDOW                                                                                  \
+      "\nL_dend" J "_%=:\n\t"                                                                          \
+      "s_mov_b64 exec, %[sM]\n"                                                                        \
+      "L_nolen" J "_%=:\n\t"
 __device__ __forceinline__ void emit_asm(const WaveSmem &t, const uint32_t *stage, uint32_t A, uint32_t stop,
-                                         uint32_t limit, uint32_t *tk, uint32_t tidx, uint32_t out0, uint32_t &bad) {
+                                         uint32_t limit, uint32_t *tk, uint32_t tidx) {
   const uint32_t stop2 = stop < limit ? stop : limit;
   if (A >= stop2) return;
   const uint32_t tabb = uni((uint32_t)reinterpret_cast<uintptr_t>(t.tab));
+  const uint32_t tabd = tabb + PE_LEN;
   const uint32_t stb = uni((uint32_t)reinterpret_cast<uintptr_t>(stage) + 8u);
-  const uint32_t pkb = uni((uint32_t)reinterpret_cast<uintptr_t>(&t.pk[0][11]));
+  const uint32_t pkl = uni((uint32_t)reinterpret_cast<uintptr_t>(&t.pk[0][11]));
+  const uint32_t pkd = uni((uint32_t)reinterpret_cast<uintptr_t>(&t.pk[1][11]));
   const uint32_t sentb = uni((uint32_t)reinterpret_cast<uintptr_t>(t.sent));
   const uint32_t sentd = sentb + 288u * 4u;
   const uint64_t tkp = reinterpret_cast<uint64_t>(tk);
   const uint64_t tkb = (uint64_t)uni((uint32_t)tkp) | (uint64_t)uni((uint32_t)(tkp >> 32)) << 32;
   uint32_t pos = A, lo = stage[A >> 5], hi = stage[(A >> 5) + 1];
-  uint32_t vt = 0, tselb = tabb, ntok = 0, acc = 0, ml = 0, voff = tidx * 4u, badv = 0, cnt = 0;
-  const uint32_t om1 = out0 - 1u;
+  uint32_t voff = tidx * 4u;
   const uint32_t bad_e = 1u | PE_SPECIAL;
-  uint32_t e = 0, bits, a, nx, x, ex, val, np, tmp, r15, q, p11, p12, p13, p14, p15, d, sh, vtok, vb;
-  uint64_t sA, sB, sC, sD, sE, sL, sBad, sv;
+  uint32_t e, bits, a, nx, x, ex, val, np, tmp, r15, q, p11, p12, p13, p14, p15, d, sh, ml;
+  uint64_t sC, sD, sS, sL, sM, sX1, sX2, sX3, sv;
   asm volatile(
       "s_mov_b64 %[sv], exec\n\t"
-      "s_mov_b64 %[sBad], 0\n"
-      "L_top%=:\n\t"
-      "v_alignbit_b32 %[bits], %[hi], %[lo], %[pos]\n\t"
-      "v_and_b32 %[a], 0x3ff, %[bits]\n\t"
-      "v_lshl_add_u32 %[a], %[a], 2, %[tselb]\n\t"
-      "ds_read_b32 %[e], %[a]\n\t"
-      "v_lshrrev_b32 %[a], 5, %[pos]\n\t"
-      "v_lshl_add_u32 %[a], %[a], 2, %[stb]\n\t"
-      "ds_read_b32 %[nx], %[a]\n\t"
-      // while the entry is in flight: token boundary (sA), cut (sC), checkpoint hit (sB)
-      "v_cmp_eq_u32 %[sA], 0, %[vt]\n\t"
-      "v_cmp_ge_u32 %[sC], %[pos], %[stop]\n\t"
-      "s_and_b64 %[sC], %[sC], %[sA]\n"
-      "L_nock%=:\n\t"
-      "s_waitcnt lgkmcnt(1)\n\t"
-      "v_cmp_gt_i32 %[sD], 0, %[e]\n\t"  // special entries
-      "s_and_b64 %[sD], %[sD], exec\n\t"
-      "s_cbranch_scc0 L_nosp%=\n\t"
-      "v_and_b32 %[tmp], 0x4000, %[e]\n\t"  // PE_SLOW
-      "v_cmp_ne_u32 %[sB], 0, %[tmp]\n\t"
-      "s_and_b64 %[sB], %[sB], %[sD]\n\t"
-      "s_cbranch_scc0 L_nosp%=\n\t"
-      // long codes: the length is 11 + #{v in 11..14 : limit(v) <= rev15}; invalid past limit(15)
-      "s_and_saveexec_b64 %[sB], %[sB]\n\t"
-      "v_bfrev_b32 %[r15], %[bits]\n\t"
-      "v_lshrrev_b32 %[r15], 17, %[r15]\n\t"
-      "v_lshrrev_b32 %[q], 6, %[vt]\n\t"  // pk[kind]: 64 bytes per kind
-      "v_add_u32 %[q], %[pkb], %[q]\n\t"
-      "ds_read_b32 %[p11], %[q]\n\t"  // pk[kind][11..15]
-      "ds_read_b32 %[p12], %[q] offset:4\n\t"
-      "ds_read_b32 %[p13], %[q] offset:8\n\t"
-      "ds_read_b32 %[p14], %[q] offset:12\n\t"
-      "ds_read_b32 %[p15], %[q] offset:16\n\t"
-      "s_waitcnt lgkmcnt(0)\n\t"
-      "v_mov_b32 %[d], %[p11]\n\t"
-      "v_mov_b32 %[sh], 4\n\t"
-      "v_lshrrev_b32 %[tmp], 16, %[p11]\n\t"
-      "v_cmp_le_u32 vcc, %[tmp], %[r15]\n\t"
-      "s_nop 1\n\t"
-      "v_cndmask_b32_e32 %[d], %[d], %[p12], vcc\n\t"
-      "v_cndmask_b32_e64 %[sh], %[sh], 3, vcc\n\t"
-      "v_lshrrev_b32 %[tmp], 16, %[p12]\n\t"
-      "v_cmp_le_u32 vcc, %[tmp], %[r15]\n\t"
-      "s_nop 1\n\t"
-      "v_cndmask_b32_e32 %[d], %[d], %[p13], vcc\n\t"
-      "v_cndmask_b32_e64 %[sh], %[sh], 2, vcc\n\t"
-      "v_lshrrev_b32 %[tmp], 16, %[p13]\n\t"
-      "v_cmp_le_u32 vcc, %[tmp], %[r15]\n\t"
-      "s_nop 1\n\t"
-      "v_cndmask_b32_e32 %[d], %[d], %[p14], vcc\n\t"
-      "v_cndmask_b32_e64 %[sh], %[sh], 1, vcc\n\t"
-      "v_lshrrev_b32 %[tmp], 16, %[p14]\n\t"
-      "v_cmp_le_u32 vcc, %[tmp], %[r15]\n\t"
-      "s_nop 1\n\t"
-      "v_cndmask_b32_e32 %[d], %[d], %[p15], vcc\n\t"
-      "v_cndmask_b32_e64 %[sh], %[sh], 0, vcc\n\t"
-      "v_lshrrev_b32 %[tmp], %[sh], %[r15]\n\t"  // (d + (rev15 >> (15 - len))) & 0xffff
-      "v_add_u32 %[tmp], %[tmp], %[d]\n\t"
-      "v_and_b32 %[tmp], 0xffff, %[tmp]\n\t"
-      "v_min_u32 %[tmp], 0x13f, %[tmp]\n\t"  // (inside sent[]; an index past it is an invalid code, replaced below)
-      "v_cmp_ne_u32 vcc, 0, %[vt]\n\t"
-      "v_mov_b32 %[q], %[sentd]\n\t"
-      "v_mov_b32 %[d], %[sentb]\n\t"
-      "v_cndmask_b32_e32 %[q], %[d], %[q], vcc\n\t"
-      "v_lshl_add_u32 %[tmp], %[tmp], 2, %[q]\n\t"
-      "ds_read_b32 %[e], %[tmp]\n\t"
-      "v_lshrrev_b32 %[tmp], 16, %[p15]\n\t"
-      "v_cmp_ge_u32 vcc, %[r15], %[tmp]\n\t"
-      "s_waitcnt lgkmcnt(0)\n\t"
-      "s_nop 1\n\t"
-      "v_cndmask_b32_e32 %[e], %[e], %[bad_e], vcc\n\t"
-      "s_mov_b64 exec, %[sB]\n\t"
-      "v_cmp_gt_i32 %[sD], 0, %[e]\n"  // special after the long-code lookup
-      "L_nosp%=:\n\t"
-      "s_or_b64 %[sD], %[sD], %[sC]\n\t"
-      "s_andn2_b64 exec, exec, %[sD]\n\t"
-      "s_cbranch_execz L_end%=\n\t"
-      "v_and_b32 %[tmp], 31, %[e]\n\t"
-      "v_bfe_u32 %[x], %[e], 5, 4\n\t"
-      "v_bfe_u32 %[ex], %[bits], %[e], %[x]\n\t"
-      "v_add3_u32 %[np], %[pos], %[tmp], %[x]\n\t"
-      "v_add_u32_sdwa %[val], %[ex], %[e] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_1\n\t"
-      "v_and_b32 %[vt], 0x1000, %[e]\n\t"  // (the next code's state; this one's is in sA)
-      "v_xor_b32 %[tmp], %[np], %[pos]\n\t"
-      "v_cmp_ne_u32 %[sL], 0, %[vt]\n\t"  // a length code
-      "v_cmp_lt_u32 vcc, 31, %[tmp]\n\t"
-      "v_mov_b32 %[pos], %[np]\n\t"
-      // the token: a literal (byte << 8) or the match completed by this distance code
-      "v_lshlrev_b32 %[vtok], 8, %[val]\n\t"
-      "v_and_b32 %[tmp], 0x600, %[e]\n\t"  // (a literal pair: byte2's bit 7 and TOK_PAIR)
-      "v_lshl_or_b32 %[vtok], %[tmp], 14, %[vtok]\n\t"
-      // (ml: the match token's upper half, TOK_MATCH | length << 16, set by every code -- only a
-      // length code's is ever read, by the distance code after it)
-      "v_or_b32 %[np], %[ml], %[val]\n\t"
-      "v_lshl_add_u32 %[ml], %[val], 16, %[mlk]\n\t"
-      "v_cndmask_b32_e64 %[vtok], %[np], %[vtok], %[sA]\n\t"
-      "s_waitcnt lgkmcnt(0)\n\t"
-      "v_cndmask_b32_e32 %[lo], %[lo], %[hi], vcc\n\t"
-      "v_cndmask_b32_e32 %[hi], %[hi], %[nx], vcc\n\t"
-      // store every code but a length code
-      "s_and_b64 %[sE], %[sA], %[sL]\n\t"
-      "s_mov_b64 %[sB], exec\n\t"
-      "s_andn2_b64 exec, exec, %[sE]\n\t"
-      // tokens gather in v124..v127 (oldest first) and leave four at a time in one 16-byte store
-      "v_mov_b32 v124, v125\n\t"
-      "v_mov_b32 v125, v126\n\t"
-      "v_mov_b32 v126, v127\n\t"
-      "v_mov_b32 v127, %[vtok]\n\t"
-      "v_add_u32 %[cnt], 1, %[cnt]\n\t"
-      "v_cmp_eq_u32 %[sE], 4, %[cnt]\n\t"
-      "s_and_b64 exec, exec, %[sE]\n\t"
-      "s_cbranch_execz L_nofl%=\n\t"
+      "s_mov_b64 %[sX1], 0\n\t"
+      "s_mov_b64 %[sX2], 0\n\t"
+      "s_mov_b64 %[sX3], 0\n"
+      SBH_EMIT_ITER("0", "v124", "")
+      SBH_EMIT_ITER("1", "v125", "s_or_b64 %[sX1], %[sX1], %[sD]\n\t")
+      SBH_EMIT_ITER("2", "v126", "s_or_b64 %[sX2], %[sX2], %[sD]\n\t")
+      SBH_EMIT_ITER("3", "v127", "s_or_b64 %[sX3], %[sX3], %[sD]\n\t")
+      // the group's four tokens of every lane still here, in one store
       "global_store_dwordx4 %[voff], v[124:127], %[tkb]\n\t"
       "s_nop 1\n\t"  // (a VALU write of a > 8-byte store's data VGPRs waits for the store to read them)
       "v_add_u32 %[voff], 16, %[voff]\n\t"
-      "v_mov_b32 %[cnt], 0\n"
-      "L_nofl%=:\n\t"
-      "s_mov_b64 exec, %[sB]\n\t"
-      "v_add_u32 %[tselb], %[tabb], %[vt]\n\t"
-      "s_branch L_top%=\n"
+      "s_branch L_it0_%=\n"
       "L_end%=:\n\t"
       "s_waitcnt lgkmcnt(0)\n\t"
-      "s_mov_b64 exec, %[sv]\n\t"
-      // the last cnt (< 4) tokens of each lane: v127 (newest) at voff + 4 (cnt - 1), v126 before it, ...
-      "v_cmp_le_u32 %[sE], 1, %[cnt]\n\t"
-      "s_and_b64 exec, exec, %[sE]\n\t"
+      // the lanes that left inside a group: 1, 2 or 3 tokens in v124, v125, v126
+      "s_or_b64 %[sX2], %[sX2], %[sX3]\n\t"
+      "s_or_b64 %[sX1], %[sX1], %[sX2]\n\t"
+      "s_mov_b64 exec, %[sX1]\n\t"
       "s_cbranch_execz L_fld%=\n\t"
-      "v_lshl_add_u32 %[tmp], %[cnt], 2, %[voff]\n\t"
-      "global_store_dword %[tmp], v127, %[tkb] offset:-4\n\t"
-      "v_cmp_le_u32 %[sE], 2, %[cnt]\n\t"
-      "s_and_b64 exec, exec, %[sE]\n\t"
-      "global_store_dword %[tmp], v126, %[tkb] offset:-8\n\t"
-      "v_cmp_le_u32 %[sE], 3, %[cnt]\n\t"
-      "s_and_b64 exec, exec, %[sE]\n\t"
-      "global_store_dword %[tmp], v125, %[tkb] offset:-12\n"
+      "global_store_dword %[voff], v124, %[tkb]\n\t"
+      "s_mov_b64 exec, %[sX2]\n\t"
+      "global_store_dword %[voff], v125, %[tkb] offset:4\n\t"
+      "s_mov_b64 exec, %[sX3]\n\t"
+      "global_store_dword %[voff], v126, %[tkb] offset:8\n"
       "L_fld%=:\n\t"
-      "s_mov_b64 exec, %[sv]\n\t"
-      "v_cndmask_b32_e64 %[badv], 0, 1, %[sBad]"
-      : [pos] "+v"(pos), [lo] "+v"(lo), [hi] "+v"(hi), [vt] "+v"(vt), [tselb] "+v"(tselb), [ntok] "+v"(ntok),
-        [acc] "+v"(acc), [ml] "+v"(ml), [voff] "+v"(voff), [badv] "+v"(badv), [cnt] "+v"(cnt), [e] "+v"(e),
-        [bits] "=&v"(bits),
+      "s_mov_b64 exec, %[sv]"
+      : [pos] "+v"(pos), [lo] "+v"(lo), [hi] "+v"(hi), [voff] "+v"(voff), [e] "=&v"(e), [bits] "=&v"(bits),
         [a] "=&v"(a), [nx] "=&v"(nx), [x] "=&v"(x), [ex] "=&v"(ex), [val] "=&v"(val), [np] "=&v"(np),
         [tmp] "=&v"(tmp), [r15] "=&v"(r15), [q] "=&v"(q), [p11] "=&v"(p11), [p12] "=&v"(p12), [p13] "=&v"(p13),
-        [p14] "=&v"(p14), [p15] "=&v"(p15), [d] "=&v"(d), [sh] "=&v"(sh), [vtok] "=&v"(vtok),
-        [vb] "=&v"(vb), [sA] "=&s"(sA), [sB] "=&s"(sB), [sC] "=&s"(sC), [sD] "=&s"(sD), [sE] "=&s"(sE),
-        [sL] "=&s"(sL), [sBad] "=&s"(sBad), [sv] "=&s"(sv)
-      : [stop] "v"(stop2), [tabb] "s"(tabb), [stb] "s"(stb), [pkb] "s"(pkb), [sentb] "s"(sentb),
-        [sentd] "s"(sentd), [bad_e] "v"(bad_e), [om1] "v"(om1), [tkb] "s"(tkb), [mlk] "s"(0x80010000u)
-      : "vcc", "scc", "memory"
-      , "v124", "v125", "v126", "v127"
-  );
-  bad |= badv;
+        [p14] "=&v"(p14), [p15] "=&v"(p15), [d] "=&v"(d), [sh] "=&v"(sh), [ml] "=&v"(ml), [sC] "=&s"(sC),
+        [sD] "=&s"(sD), [sS] "=&s"(sS), [sL] "=&s"(sL), [sM] "=&s"(sM), [sX1] "=&s"(sX1), [sX2] "=&s"(sX2),
+        [sX3] "=&s"(sX3), [sv] "=&s"(sv)
+      : [stop] "v"(stop2), [tabb] "s"(tabb), [tabd] "s"(tabd), [stb] "s"(stb), [pkl] "s"(pkl), [pkd] "s"(pkd),
+        [sentb] "s"(sentb), [sentd] "s"(sentd), [bad_e] "v"(bad_e), [tkb] "s"(tkb), [mlk] "s"(0x80010000u)
+      : "vcc", "scc", "memory", "v124", "v125", "v126", "v127");
 }
+#undef SBH_EMIT_ITER
+#undef SBH_EMIT_WINDOW
+#undef SBH_EMIT_VALUE
+#undef SBH_EMIT_LOOKUP
+#undef SBH_EMIT_SLOW
 
 // The code-length part of a dynamic block header (RFC 1951 3.2.7) by one wave: the
 // code-length code, then the nlen + ndist lengths into t.lens ([0, 288) lit/len, [288,
@@ -2040,7 +2070,7 @@ __device__ __forceinline__ uint32_t inflate_par(SM &sm, const uint8_t *__restric
     if (tid <= k) {
 #if SBH_ASM_EMIT
       if (LDS)
-        emit_asm(sm.t, sm.stage, A, stop, limit, tk + ntok, tpre, out_before + out + opre, bad);
+        emit_asm(sm.t, sm.stage, A, stop, limit, tk + ntok, tpre);
       else
 #endif
         lane_run<RUN_EMIT>(sm.t, src, A, stop, limit, ck, none, tk + ntok + tpre, out_before + out + opre, bad);
