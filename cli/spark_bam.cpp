@@ -37,6 +37,7 @@
 #include <unistd.h>
 
 #include "../include/sparkbam.h"
+#include "../spark-bam_amd/csrc/stats_core.h"  // stats' report (host functions only)
 #include "../spark-bam_amd/csrc/tally_core.h"  // flagstat's and idxstats' text (host functions only)
 #include "../spark-bam_amd/csrc/fastq_core.h"  // fastq's mode bits, the quality bound and the parts' order
 
@@ -275,6 +276,7 @@ struct Args {
   std::string out_part[3];
   bool suffix_never = false, suffix_always = false, has_level = false;
   int def_qual = 1;
+  long stat_cycles = 1024, stat_insert = 8000;  // stats: --cycles, -i
 };
 
 // decimal or 0x hex
@@ -296,7 +298,8 @@ Args parse(int argc, char **argv) {
     throw Error(SBH_E_ARG,
                 "usage: spark-bam <command> [options] <bam>\n"
                 "  commands: compute-splits count-reads check-bam full-check index-blocks index-records index-bai\n"
-                "            check-blocks htsjdk-rewrite view sort depth pileup consensus flagstat idxstats fastq fasta\n"
+                "            check-blocks htsjdk-rewrite view sort depth pileup consensus flagstat idxstats stats fastq\n"
+                "            fasta\n"
                 "  view [-h|--header] [-o FILE] <bam>: the records as SAM text (-h: the header text first)\n"
                 "  view -b -o OUT [-f INT] [-F INT] [-q INT] [-r ROWS] [--level N] [--index-bai] [--sort] <bam>: the records with\n"
                 "       (flag & f) == f, (flag & F) == 0, mapq >= q and an index in ROWS (a-b,c-d: htsjdk-rewrite's -r)\n"
@@ -317,6 +320,9 @@ Args parse(int argc, char **argv) {
                 "  flagstat [-f INT] [-F INT] [-q INT] [-o FILE] <bam>: samtools flagstat's sixteen lines of the records that pass\n"
                 "  idxstats [-f INT] [-F INT] [-q INT] [-o FILE] <bam>: NAME LENGTH MAPPED UNMAPPED per reference, then the `*` line\n"
                 "       (samtools idxstats), counted from the records: no index is read, any order will do\n"
+                "  stats [-f INT] [-F INT] [-q INT] [--cycles N] [-i MAX_INSERT] [-o FILE] <bam>: the read-level sections of samtools\n"
+                "       stats (SN, FFQ, LFQ, GCF, GCL, GCC, IS, RL, MAPQ) of the records that pass: read lengths, qualities and bases\n"
+                "       per cycle (N rows, 1024; longer reads share a last row), GC content, insert sizes (up to MAX_INSERT, 8000)\n"
                 "  view -c [-f INT] [-F INT] [-q INT] <bam>: how many records pass (samtools view -c)\n"
                 "  fastq [-o FILE] [-1 FILE] [-2 FILE] [-0 FILE] [-n|-N] [-f INT] [-F INT] [-q INT] [-v INT] [--level N] <bam>:\n"
                 "       the records as FASTQ (samtools fastq): @NAME[/1|/2], bases, +, qualities; reverse-strand reads\n"
@@ -354,6 +360,14 @@ Args parse(int argc, char **argv) {
     else if (tally && (t == "-q" || t == "--min-mapq")) a.min_mapq = (int)parse_int(next());
     else if (tally && (t == "-o" || t == "--output")) a.out = next();
     else if (tally && t.size() > 1 && t[0] == '-') throw Error(SBH_E_ARG, "usage: " + a.cmd + " [-f INT] [-F INT] [-q INT] [-o FILE] <bam> (unknown option " + t + ")");
+    else if (a.cmd == "stats" && (t == "-f" || t == "--require-flags")) a.flag_require = (uint32_t)parse_int(next());
+    else if (a.cmd == "stats" && (t == "-F" || t == "--exclude-flags")) a.flag_exclude = (uint32_t)parse_int(next());
+    else if (a.cmd == "stats" && (t == "-q" || t == "--min-mapq")) a.min_mapq = (int)parse_int(next());
+    else if (a.cmd == "stats" && t == "--cycles") a.stat_cycles = parse_int(next());
+    else if (a.cmd == "stats" && (t == "-i" || t == "--insert-size")) a.stat_insert = parse_int(next());
+    else if (a.cmd == "stats" && (t == "-o" || t == "--output")) a.out = next();
+    else if (a.cmd == "stats" && t.size() > 1 && t[0] == '-')
+      throw Error(SBH_E_ARG, "usage: stats [-f INT] [-F INT] [-q INT] [--cycles N] [-i MAX_INSERT] [-o FILE] <bam> (unknown option " + t + ")");
     else if (fq && (t == "-o" || t == "--output")) a.out = next();
     else if (fq && t == "-1") a.out_part[0] = next();
     else if (fq && t == "-2") a.out_part[1] = next();
@@ -413,7 +427,7 @@ Args parse(int argc, char **argv) {
         (pos[0].size() > 1 && pos[0][0] == '-'))
       throw Error(SBH_E_ARG, "usage: view -c [-f INT] [-F INT] [-q INT] <bam>");
   }
-  if (pos.size() > 1 && a.cmd != "depth" && !tally && !fq && !pile) a.out = pos[1];
+  if (pos.size() > 1 && a.cmd != "depth" && a.cmd != "stats" && !tally && !fq && !pile) a.out = pos[1];
   if (fq && !a.has_exclude) a.flag_exclude = 0x900;  // SECONDARY, SUPPLEMENTARY: samtools fastq's
   if (fq && a.suffix_never && a.suffix_always) throw Error(SBH_E_ARG, "usage: " + a.cmd + " takes -n or -N, not both");
   if ((a.cmd == "depth" || pile) && !a.has_exclude) a.flag_exclude = 1796;  // UNMAP, SECONDARY, QCFAIL, DUP: samtools depth's
@@ -1386,6 +1400,49 @@ int tally(const Args &a) {
   return 0;
 }
 
+// stats: one pass over the records that pass -f / -F / -q, whole file resident as depth holds it,
+// counted on the device (sbh_records_stats_add); the tables come back and stats_core.h's renderer
+// prints them.
+int stats(const Args &a) {
+  if (a.stat_cycles < 1 || a.stat_cycles > (long)sbh_stat::STAT_CYCLES_MAX || a.stat_insert < 1 || a.stat_insert > (long)sbh_stat::STAT_INSERT_MAX)
+    throw Error(SBH_E_ARG, "stats: --cycles takes 1.." + std::to_string(sbh_stat::STAT_CYCLES_MAX) + ", -i 1.." + std::to_string(sbh_stat::STAT_INSERT_MAX));
+  Loaded L(a.path);
+  uint64_t seg_end = L.flat;
+  for (const sbh_block &b : L.blocks)
+    if (b.flags & SBH_BLOCK_EMPTY) { seg_end = b.ustart; break; }
+  struct Acc {
+    sbh_stats *s = nullptr;
+    ~Acc() { sbh_stats_destroy(s); }
+  } acc;
+  const sbh_stats_params prm{(uint32_t)a.stat_cycles, (uint32_t)a.stat_insert};
+  chk(sbh_stats_create(g_ctx, &prm, &acc.s), "stats create");
+  if (seg_end > L.hdr.end) {
+    uint64_t n = 0;
+    chk(sbh_check_eager(L.sh, L.hdr.end, seg_end, a.reads_to_check, nullptr, &n), "eager");
+    sbh_records_sizes rs{};
+    chk(sbh_records_scan(L.sh, L.hdr.end, seg_end, &rs), "records scan");
+    sbh_record_filter f{};
+    f.flag_require = a.flag_require;
+    f.flag_exclude = a.flag_exclude;
+    f.min_mapq = a.min_mapq;
+    sbh_stats_add_result ar{};
+    chk(sbh_records_stats_add(L.sh, acc.s, &f, &ar), "stats add");
+  }
+  const sbh_stat::Params P{prm.cycles, prm.max_insert};
+  const sbh_stat::Layout lay = sbh_stat::layout_of(P);
+  std::vector<uint64_t> w(lay.words);
+  const sbh_stat::Tables T{w.data(), w.data() + lay.read_len, w.data() + lay.qual, w.data() + lay.base, w.data() + lay.gc,
+                           w.data() + lay.isize, w.data() + lay.mapq};
+  chk(sbh_stats_fetch(acc.s, T.sn, T.read_len, T.qual, T.base, T.gc, T.isize, T.mapq), "stats fetch");
+  const std::string text = sbh_stat::stats_text(P, T);
+  FILE *f = a.out.empty() ? stdout : fopen(a.out.c_str(), "wb");
+  if (!f) throw Error(SBH_E_ARG, "cannot write " + a.out);
+  const bool ok = fwrite(text.data(), 1, text.size(), f) == text.size() && fflush(f) == 0;
+  if (f != stdout) fclose(f);
+  if (!ok) throw Error(SBH_E_ARG, "short write to " + (a.out.empty() ? std::string("stdout") : a.out));
+  return 0;
+}
+
 // fastq, fasta: the records that pass -f / -F / -q as FASTQ or FASTA text, whole file resident as depth
 // holds it, rendered on the device (sbh_records_fastq_scan).  One sink (-o, or the terminal) takes the
 // text in file order; with any of -1 / -2 / -0 the text comes in three parts -- read 1, read 2, the
@@ -1685,6 +1742,7 @@ int main(int argc, char **argv) {
     else if (a.cmd == "depth") rc = depth(a);
     else if (a.cmd == "pileup" || a.cmd == "consensus") rc = pileup(a);
     else if (a.cmd == "flagstat" || a.cmd == "idxstats") rc = tally(a);
+    else if (a.cmd == "stats") rc = stats(a);
     else if (a.cmd == "fastq" || a.cmd == "fasta") rc = fastq(a);
     else throw Error(SBH_E_ARG, "unknown command " + a.cmd);
     sbh_ctx_destroy(g_ctx);

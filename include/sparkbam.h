@@ -174,7 +174,7 @@ int sbh_find_block_start(sbh_shard *sh, uint64_t start, int32_t bgzf_blocks_to_c
  *     which walks a range of its own, is not); a records scan that fails leaves no valid scan.
  *   a stage call refused for its arguments (SBH_E_ARG: a bad record filter) voids nothing: the
  *     stage's last good result is still there.
- * The accumulators (sbh_depth, sbh_pileup, sbh_tally) belong to the context, not to a shard: none
+ * The accumulators (sbh_depth, sbh_pileup, sbh_tally, sbh_stats) belong to the context, not to a shard: none
  * of these events touches what they hold, and an add that returns SBH_E_STATE adds nothing. */
 int sbh_index(sbh_shard *sh, uint64_t start, uint64_t *n_blocks, uint64_t *flat_size);
 int sbh_get_blocks(sbh_shard *sh, uint64_t first, uint64_t count, sbh_block *out);
@@ -925,6 +925,47 @@ int sbh_tally_fetch(sbh_tally *t, uint64_t *flag /* [16][2] or NULL */, uint64_t
 int sbh_tally_add_host(const uint8_t *flat, uint64_t flat_size, const uint64_t *starts, uint64_t n,
                        const sbh_record_filter *filter, int32_t n_ref, uint64_t *flag, uint64_t *ref,
                        sbh_tally_add_result *out, uint64_t *bad_row);
+
+/* ---- Read-level statistics ------------------------------------------------------------------
+ * The histograms of samtools stats -- read lengths, per-cycle qualities of first and last fragments,
+ * per-cycle base composition, GC content, insert sizes, mapping qualities and a table of summary
+ * numbers -- counted on the device over the rows of a record scan and summed over any number of
+ * scans and shards in an sbh_stats, which belongs to a context and outlives the shards added to it
+ * (csrc/stats_core.h holds the definition for device and host, table by table).
+ *
+ * params: cycles in [1, 65536] (reads longer than that share the last row of the per-cycle tables),
+ * max_insert in [1, 1 << 20] (larger insert sizes share the last bin); fixed at create.  A row the
+ * filter keeps (NULL: every row) is counted when it is neither secondary nor supplementary; the
+ * other kept rows add to sn's secondary / supplementary counters alone.  Every row, kept or not,
+ * must be a valid record; no reference id is validated.  The tables (uint64):
+ *   sn[SBH_STATS_SN]  read_len[cycles + 2]  qual[2][cycles + 1][SBH_STATS_QUALS]  base[cycles + 1][5]
+ *   gc[2][101]  isize[max_insert + 1][3]  mapq[256]
+ *
+ * sbh_records_stats_add uses the rows of the last valid scan on the shard, in their order, as
+ * sbh_records_tally_add does (decode == 0 is enough), leaves the scan alone and synchronises the
+ * shard's stream before it returns.  A failed add -- SBH_E_BAD_RECORD {row}, or SBH_E_NEED_HALO when
+ * the first bad row merely runs past an open shard end -- leaves the accumulator exactly as it was.
+ * There is no finish: sbh_stats_fetch may be called between adds, and copies out the tables asked for
+ * (any pointer may be NULL).  SBH_E_STATE without a valid scan; SBH_E_ARG for parameters out of
+ * range, a bad filter and a shard of another context.  One thread at a time per sbh_stats. */
+typedef struct sbh_stats sbh_stats;           /* owned by a context; outlives shards */
+typedef struct { uint32_t cycles, max_insert; } sbh_stats_params;
+typedef struct { uint64_t n, n_kept, n_counted; } sbh_stats_add_result;
+#define SBH_STATS_QUALS 94
+#define SBH_STATS_SN 23
+int sbh_stats_create(sbh_ctx *ctx, const sbh_stats_params *params, sbh_stats **out);
+int sbh_stats_destroy(sbh_stats *s);
+int sbh_stats_reset(sbh_stats *s);
+int sbh_records_stats_add(sbh_shard *sh, sbh_stats *s, const sbh_record_filter *filter /* NULL: all */,
+                          sbh_stats_add_result *out);
+int sbh_stats_fetch(sbh_stats *s, uint64_t *sn, uint64_t *read_len, uint64_t *qual, uint64_t *base, uint64_t *gc,
+                    uint64_t *isize, uint64_t *mapq);
+/* HOST ONLY, no context, no GPU: adds into the seven tables (the caller zeroes them first; none may
+ * be NULL); SBH_E_BAD_RECORD with *bad_row = the first bad row, the tables untouched. */
+int sbh_stats_add_host(const uint8_t *flat, uint64_t flat_size, const uint64_t *starts, uint64_t n,
+                       const sbh_record_filter *filter, const sbh_stats_params *params, uint64_t *sn,
+                       uint64_t *read_len, uint64_t *qual, uint64_t *base, uint64_t *gc, uint64_t *isize,
+                       uint64_t *mapq, sbh_stats_add_result *out, uint64_t *bad_row);
 
 /* ---- FASTQ / FASTA text -------------------------------------------------------------------
  * What samtools fastq and samtools fasta write, rendered on the device from the flat bytes and

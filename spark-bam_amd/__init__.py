@@ -16,17 +16,20 @@ Import name: ``spark_bam_amd`` (the directory name contains a hyphen, so load it
   depth:  depth (per-base coverage accumulated and scanned on the GPU), depth_host
   pileup: pileup (per-base allele counts, call bytes and consensus on the GPU), pileup_host
   counts: flagstat, idxstats (flag and per-reference read counts, one pass on the GPU), tally_host
+  stats:  stats (the read-level histograms of samtools stats, counted on the GPU), stats_host
   reads:  fastq (the records as FASTQ / FASTA text, rendered on the GPU), fastq_host
 """
 from ._lib import (BLOCK_EMPTY, BLOCK_TRUNCATED, FULL_FLAGS_MASK, FULL_N_SHIFT,  # noqa: F401
                    FULL_SUCCESS, FULL_UNKNOWN, HeaderParseException, HeaderSearchFailedException,
                    NoReadFoundException, SparkBamError, lib)
-from .device import Context, Depth, Pileup, PinnedBuffer, Shard, Tally  # noqa: F401
+from .device import Context, Depth, Pileup, PinnedBuffer, Shard, Stats, Tally  # noqa: F401
 from .api import (FLAG_NAMES, htsjdk_rewrite, Header, Metadata, Pos, Split, bam_header, check_bam, depth,  # noqa: F401
                   pileup,
                   file_splits, flagstat, full_check, idxstats, load_bam_count, load_reads, load_splits_and_reads,
                   parse_bam_header, sort_bam, view, view_bam)
 from .tally import TallyResult, flagstat_text, idxstats_text, tally_host  # noqa: F401
+from .stats import SN_ROWS, StatsResult, stats_host, stats_text  # noqa: F401
+from .api import stats  # noqa: F401,E402  (after the submodule of the same name: the function is what the package exports)
 from .fastq import FastqResult, fastq_host, fastq_mode  # noqa: F401
 from .api import fastq  # noqa: F401,E402  (after the submodule of the same name: the function is what the package exports)
 from .records import Reads, bam_gather_host, bam_header_set_so, bam_sort_host, sam_text_host  # noqa: F401
@@ -52,4 +55,5 @@ __all__ = [
     "pileup", "Pileup", "PileupResult", "pileup_host", "pileup_text", "consensus_fasta",
     "flagstat", "idxstats", "Tally", "TallyResult", "tally_host", "flagstat_text", "idxstats_text",
     "fastq", "fastq_host", "fastq_mode", "FastqResult",
+    "stats", "Stats", "StatsResult", "stats_host", "stats_text", "SN_ROWS",
 ]

@@ -56,6 +56,8 @@ EXPORTS = [
     "sbh_pileup_add_host", "sbh_pileup_finish_host",
     "sbh_tally_create", "sbh_tally_destroy", "sbh_tally_reset", "sbh_records_tally_add", "sbh_tally_fetch",
     "sbh_tally_add_host",
+    "sbh_stats_create", "sbh_stats_destroy", "sbh_stats_reset", "sbh_records_stats_add", "sbh_stats_fetch",
+    "sbh_stats_add_host",
     "sbh_records_fastq_scan", "sbh_records_fastq_device_ptr", "sbh_records_fastq_fetch", "sbh_fastq_render_host",
 ]
 ORDER_SCAN, ORDER_COORDINATE = 0, 1  # SBH_ORDER_*
@@ -170,6 +172,14 @@ class SbhDepthSizes(C.Structure):
 
 class SbhTallyAddResult(C.Structure):
     _fields_ = [("n", C.c_uint64), ("n_kept", C.c_uint64)]
+
+
+class SbhStatsParams(C.Structure):
+    _fields_ = [("cycles", C.c_uint32), ("max_insert", C.c_uint32)]
+
+
+class SbhStatsAddResult(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("n_kept", C.c_uint64), ("n_counted", C.c_uint64)]
 
 
 class SbhFastqSizes(C.Structure):
@@ -342,6 +352,13 @@ def lib():
         "sbh_records_tally_add": [P, P, C.POINTER(SbhRecordFilter), C.POINTER(SbhTallyAddResult)],
         "sbh_tally_fetch": [P, P, U64, U64, P],
         "sbh_tally_add_host": [P, U64, P, U64, C.POINTER(SbhRecordFilter), I32, P, P, C.POINTER(SbhTallyAddResult), PU64],
+        "sbh_stats_create": [P, C.POINTER(SbhStatsParams), C.POINTER(P)],
+        "sbh_stats_destroy": [P],
+        "sbh_stats_reset": [P],
+        "sbh_records_stats_add": [P, P, C.POINTER(SbhRecordFilter), C.POINTER(SbhStatsAddResult)],
+        "sbh_stats_fetch": [P, P, P, P, P, P, P, P],
+        "sbh_stats_add_host": [P, U64, P, U64, C.POINTER(SbhRecordFilter), C.POINTER(SbhStatsParams), P, P, P, P, P, P, P,
+                               C.POINTER(SbhStatsAddResult), PU64],
         "sbh_records_fastq_scan": [P, C.POINTER(SbhRecordFilter), U32, I32, C.POINTER(SbhFastqSizes)],
         "sbh_records_fastq_fetch": [P, P, P, P],
         "sbh_fastq_render_host": [P, U64, P, U64, C.POINTER(SbhRecordFilter), U32, I32, P, U64, P, P,

@@ -636,6 +636,54 @@ def idxstats(path_or_bytes, flag_require=0, flag_exclude=0, min_mapq=0, window=N
     return _tally(path_or_bytes, flag_require, flag_exclude, min_mapq, window, ctx, reads_to_check)
 
 
+def stats(path_or_bytes, flag_require=0, flag_exclude=0, min_mapq=0, cycles=1024, max_insert=8000, window=None, ctx=None,
+          reads_to_check=DEFAULT_READS_TO_CHECK):
+    """What `samtools stats` reports about the reads themselves, counted on the GPU: of the file's
+    records with (flag & flag_require) == flag_require, (flag & flag_exclude) == 0 and mapq >= min_mapq
+    (default: every record) that are neither secondary nor supplementary, the read lengths, the
+    qualities and the base composition per sequencing cycle (`cycles` rows; the bases of longer reads
+    share a last row), the GC content per read, the insert sizes (`max_insert` bins; larger ones share
+    a last bin) by pair orientation, the mapping qualities and a table of summary numbers
+    (csrc/stats_core.h defines each).  The file is walked `window` compressed bytes at a time
+    (iter_reads' walk) into one accumulator in HBM (Context.stats); the tables do not depend on
+    `window`.
+
+    Returns a stats.StatsResult: `.sn`, `.read_len`, `.qual`, `.base`, `.gc`, `.isize`, `.mapq`, `.n`,
+    `.n_kept`, `.n_counted` and `.text()` (the report under samtools stats' section tags)."""
+    from .stats import StatsResult
+    data = _file_array(path_or_bytes)
+    own_ctx = ctx is None
+    ctx = ctx or Context(0)
+    acc = None
+    try:
+        _, contig_len, _ = file_header(ctx, data)
+        acc = ctx.stats(cycles, max_insert)
+        f = {"flag_require": flag_require, "flag_exclude": flag_exclude, "min_mapq": min_mapq}
+        tot = {"n": 0, "n_kept": 0, "n_counted": 0}
+
+        def deliver(sh, first, E, _names):
+            # look at the chain's exit first, add after (_tally's delivery): a window that runs again
+            # with a larger halo must not count twice
+            _, x = sh.chain_from(first, E)
+            blocks = sh.blocks()
+            seg = next((b[3] for b in blocks if b[5] & 1 and b[3] >= first), None)
+            last = seg is not None and E == seg or sh.file_offset + sh.n == sh.file_size and E == sh.flat_size
+            if not last and x >= sh.flat_size:
+                raise SparkBamError(SBH_E_NEED_HALO, "the chain leaves the halo")
+            sh.records_scan(first, E)
+            return [acc.add(sh, f)]
+
+        for (got,) in _iter_windows(data, deliver, window, ctx=ctx, reads_to_check=reads_to_check):
+            for k in tot:
+                tot[k] += got[k]
+        return StatsResult(acc.counts(), acc.cycles, acc.max_insert, tot["n"], tot["n_kept"], tot["n_counted"])
+    finally:
+        if acc is not None:
+            acc.close()
+        if own_ctx:
+            ctx.close()
+
+
 def fastq(path_or_bytes, out=None, out1=None, out2=None, out0=None, fasta=False, suffix="auto", flag_require=0,
           flag_exclude=0x900, min_mapq=0, def_qual=1, level=None, window=None, ctx=None,
           reads_to_check=DEFAULT_READS_TO_CHECK):

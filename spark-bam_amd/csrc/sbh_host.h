@@ -5,7 +5,7 @@
 // declared in sbh_internal.h; nothing here is seen by device code.
 //
 // The stages that run over the rows of the last records scan under an sbh_record_filter
-// (bam_gather.hip, depth.hip, pileup.hip, tally.hip, fastq.hip) share one frame, declared at the end
+// (bam_gather.hip, depth.hip, pileup.hip, tally.hip, fastq.hip, stats.hip) share one frame, declared at the end
 // of this header and defined in bam_gather.hip: row_filter (the filter and its one message),
 // stage_row_ranges (the device copy of the row ranges, sbh_shard::row_ranges) and rows_verdict (bad
 // row, past row -> SBH_OK / SBH_E_NEED_HALO / SBH_E_BAD_RECORD); the accumulators share sbh::Accum.
@@ -320,11 +320,11 @@ struct sbh_shard {
 };
 
 namespace sbh {
-// What the accumulators (sbh_depth, sbh_pileup, sbh_tally) share: the owning context and a stream of
+// What the accumulators (sbh_depth, sbh_pileup, sbh_tally, sbh_stats) share: the owning context and a stream of
 // the accumulator's own.  The adds run on the adding shard's stream and synchronise it before they
 // return; reset, finish and the fetches run on `st` and synchronise that -- so no two of them ever
 // overlap on the device, and a shard may be destroyed right after its add.
-// drain() is the one destructor body of the three.  The derived destructors call it; it is not
+// drain() is the one destructor body of them all.  The derived destructors call it; it is not
 // ~Accum, because a base is destroyed after the derived struct's members and the DBufs must be freed
 // only once the stream is drained.
 struct Accum {
@@ -385,6 +385,17 @@ struct sbh_tally : sbh::Accum {
   // `words` counters of every add that succeeded (k_tally_commit)
   sbh::DBuf<unsigned long long> stage, totals;
   ~sbh_tally() { drain(); }
+};
+
+// A stats accumulator (sbh_stats_create): the tables of csrc/stats_core.h one behind another, owned
+// by a context, fed by any number of its shards.
+struct sbh_stats : sbh::Accum {
+  sbh_stats_params params{};
+  uint64_t words = 0;  // sbh_stat::layout_of(params).words
+  // stage: bad row, past row, kept rows, then `words` counters of the add under way (k_stats_rows,
+  // k_stats_bases); totals: `words` counters of every add that succeeded (k_stats_commit)
+  sbh::DBuf<unsigned long long> stage, totals;
+  ~sbh_stats() { drain(); }
 };
 
 struct StreamCache {

@@ -41,7 +41,8 @@ __device__ __forceinline__ void block_add(uint64_t v, uint64_t *s_red, unsigned 
   }
 }
 
-// The opening of a filtered row kernel (bam_gather.hip, depth.hip, pileup.hip, tally.hip, fastq.hip):
+// The opening of a filtered row kernel (bam_gather.hip, depth.hip, pileup.hip, tally.hip, fastq.hip,
+// stats.hip):
 // a lane's smallest bad row and its smallest row that is bad only because it runs past the stream,
 // kept over the lane's whole loop and sent out once behind it.  The host's rows_verdict reads the
 // two words: they are equal exactly when more resident bytes may cure the first bad row.
@@ -398,6 +399,10 @@ constexpr uint32_t FASTQ_END = H_FASTQ_SUMS + 6;
 constexpr uint32_t PILE_BAD = FASTQ_END, PILE_PAST = PILE_BAD + 1, PILE_KEPT = PILE_BAD + 2;
 constexpr uint32_t PILE_UNPLACED = PILE_BAD + 3, PILE_COUNTED = PILE_BAD + 4, PILE_TOTALS = PILE_BAD + 5;
 constexpr uint32_t PILE_END = PILE_TOTALS + 8;
+// stats add (sbh_records_stats_add), h_ctr only -- the device words are the accumulator's staging
+// words: first bad row, first row that only runs past the stream's end, kept rows, counted rows
+constexpr uint32_t H_STATS_BAD = PILE_END, H_STATS_PAST = H_STATS_BAD + 1, H_STATS_KEPT = H_STATS_BAD + 2;
+constexpr uint32_t H_STATS_COUNTED = H_STATS_BAD + 3, STATS_END = H_STATS_BAD + 4;
 // inflate status (launch_first_bad): the first block whose status is not INF_OK
 constexpr uint32_t FIRST_BAD = 100;
 // h_ctr only: that block's status (u32), fetched after the run's copy of [0, CTR_RUN_WORDS)
@@ -417,6 +422,7 @@ static_assert(ctr::DEPTH_END <= ctr::FIRST_BAD, "the depth counters end before t
 static_assert(ctr::TALLY_END <= ctr::FIRST_BAD, "the tally add's mirror words end before the first bad block");
 static_assert(ctr::FASTQ_END <= ctr::FIRST_BAD, "the FASTQ scan's words end before the first bad block");
 static_assert(ctr::PILE_END <= ctr::FIRST_BAD, "the pileup add's counters end before the first bad block");
+static_assert(ctr::STATS_END <= ctr::FIRST_BAD, "the stats add's mirror words end before the first bad block");
 // what the run template presets (the eager counters, FindRecordStart's best, the proof
 // counters, the first bad block) travels in the run's one copy each way ...
 static_assert(ctr::EAGER_END <= CTR_RUN_WORDS && ctr::FRS_BEST < CTR_RUN_WORDS &&

@@ -11,7 +11,7 @@ from .records import pack_ref_names, record_columns, record_filter
 from ._lib import (ORDER_COORDINATE, SBH_OK, SbhBaiSizes, SbhBamSizes, SbhBatchSplit, SbhBlock, SbhCheckOpts, SbhCheckResult, SbhDepthAddResult, SbhPileupAddResult, SbhPileupSizes,
                    SbhDepthSizes, SbhFastqSizes, SbhRecordsOut,
                    SbhRecordsSizes, SbhSamSizes, SbhShardResult, SbhSplitBatchResult, SbhSplitRecordsResult,
-                   SbhStreamOpts, SbhStreamResult, SbhTallyAddResult, SparkBamError, error_for, lib)
+                   SbhStatsAddResult, SbhStatsParams, SbhStreamOpts, SbhStreamResult, SbhTallyAddResult, SparkBamError, error_for, lib)
 
 
 # sbh_bai_run (include/sparkbam.h)
@@ -247,6 +247,65 @@ class Context:
         """A flag-count and per-reference-count accumulator for a file with n_ref references
         (sbh_tally_create): what samtools flagstat and idxstats report, counted on the GPU."""
         return Tally(self, n_ref)
+
+
+    def stats(self, cycles=1024, max_insert=8000):
+        """A read-level statistics accumulator (sbh_stats_create): the histograms of samtools stats --
+        read lengths, per-cycle qualities and base composition (`cycles` rows; longer reads share a
+        last row), GC content, insert sizes (`max_insert` bins; larger ones share a last bin),
+        mapping qualities and the summary numbers -- counted on the GPU."""
+        return Stats(self, cycles, max_insert)
+
+
+class Stats:
+    """sbh_stats: scans of any number of this context's shards counted into one set of tables
+    (`add`); `counts` may be read between adds."""
+
+    def __init__(self, ctx, cycles=1024, max_insert=8000):
+        from .stats import check_params
+        self.ctx = ctx
+        self.cycles, self.max_insert = check_params(cycles, max_insert)
+        h = C.c_void_p()
+        p = SbhStatsParams(self.cycles, self.max_insert)
+        _check(ctx.h, lib().sbh_stats_create(ctx.h, C.byref(p), C.byref(h)))
+        self.h = h
+        ctx._shards.add(self)  # (closed with the context, before it)
+
+    def close(self):
+        if self.h:
+            if self.ctx.h:
+                lib().sbh_stats_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, shard, filter=None):
+        """The rows of the last scan on `shard` that `filter` keeps (records.record_filter's dict,
+        None: all), counted (sbh_records_stats_add).  Returns {"n": rows, "n_kept": kept rows,
+        "n_counted": the kept rows that are neither secondary nor supplementary}.  A failed add leaves
+        the accumulator as it was."""
+        f, keep = record_filter(filter)
+        r = SbhStatsAddResult()
+        _check(self.ctx.h, lib().sbh_records_stats_add(shard.h, self.h, C.byref(f) if f is not None else None,
+                                                       C.byref(r)))
+        del keep
+        return {"n": int(r.n), "n_kept": int(r.n_kept), "n_counted": int(r.n_counted)}
+
+    def counts(self):
+        """The tables of every add so far (sbh_stats_fetch) as a dict of uint64 arrays: sn, read_len,
+        qual, base, gc, isize, mapq (stats.empty_tables' shapes)."""
+        from .stats import TABLES, empty_tables
+        t = empty_tables(self.cycles, self.max_insert)
+        _check(self.ctx.h, lib().sbh_stats_fetch(self.h, *[_ptr(t[k]) for k in TABLES]))
+        return t
+
+    def reset(self):
+        """Zero the totals (sbh_stats_reset)."""
+        _check(self.ctx.h, lib().sbh_stats_reset(self.h))
 
 
 class Tally:
