@@ -163,6 +163,11 @@ struct Loaded {
     if (nblocks) chk(sbh_get_blocks(sh, 0, nblocks, blocks.data()), "blocks");
   }
   ~Loaded() { sbh_shard_destroy(sh); }
+  uint64_t seg_end() const {  // the flat end of the stream's first segment: an empty block ends it
+    for (const sbh_block &b : blocks)
+      if (b.flags & SBH_BLOCK_EMPTY) return b.ustart;
+    return flat;
+  }
   Pos pos(uint64_t flat_pos) const {
     Pos p;
     chk(sbh_pos_of(sh, flat_pos, &p.block, &p.off), "pos");
@@ -292,6 +297,31 @@ long parse_int(const std::string &s) {
   return v;
 }
 
+// The record commands: which of the shared options each takes, whether it rejects a dash-option it does
+// not know, and the synopsis that the rejection shows.
+enum : unsigned { O_FILTER = 1, O_OUT = 2, O_REGION = 4, O_LEVEL = 8, O_BAI = 16 };  // -f -F -q | -o | -r REGION | --level | --index-bai
+struct Command {
+  const char *name;
+  unsigned opts;
+  bool strict;
+  const char *synopsis;
+};
+const char *const TALLY_SYNOPSIS = "[-f INT] [-F INT] [-q INT] [-o FILE] <bam>";
+const char *const FASTQ_SYNOPSIS = "[-o FILE] [-1 FILE] [-2 FILE] [-0 FILE] [-n|-N] [-f INT] [-F INT] [-q INT] [-v INT] [--level N] <bam>";
+const Command COMMANDS[] = {
+    {"view", O_FILTER | O_OUT | O_LEVEL | O_BAI, false, nullptr},
+    {"sort", O_OUT | O_LEVEL | O_BAI, false, nullptr},
+    {"htsjdk-rewrite", O_BAI, false, nullptr},
+    {"depth", O_FILTER | O_OUT | O_REGION, false, nullptr},
+    {"pileup", O_FILTER | O_OUT | O_REGION, true, "[-a] [-H] [-r REGION] [-f INT] [-F INT] [-q INT] [-Q INT] [-o FILE] <bam>"},
+    {"consensus", O_FILTER | O_OUT | O_REGION, true, "[-r REGION] [-f INT] [-F INT] [-q INT] [-Q INT] [-d MIN_DEPTH] [-c PCT] [-o FILE] <bam>"},
+    {"flagstat", O_FILTER | O_OUT, true, TALLY_SYNOPSIS},
+    {"idxstats", O_FILTER | O_OUT, true, TALLY_SYNOPSIS},
+    {"stats", O_FILTER | O_OUT, true, "[-f INT] [-F INT] [-q INT] [--cycles N] [-i MAX_INSERT] [-o FILE] <bam>"},
+    {"fastq", O_FILTER | O_OUT | O_LEVEL, true, FASTQ_SYNOPSIS},
+    {"fasta", O_FILTER | O_OUT | O_LEVEL, true, FASTQ_SYNOPSIS},
+};
+
 Args parse(int argc, char **argv) {
   Args a;
   if (argc < 2)
@@ -331,7 +361,11 @@ Args parse(int argc, char **argv) {
                 "       qualities (1); -F defaults to 0x900; --level N, or a FILE ending in .gz: BGZF-compressed on the GPU\n"
                 "  fasta: the same flags, >NAME and the bases only (samtools fasta)");
   a.cmd = argv[1];
-  const bool rewrite = a.cmd == "htsjdk-rewrite", tally = a.cmd == "flagstat" || a.cmd == "idxstats";
+  static const Command plain{"", 0, false, nullptr};
+  const Command *c = &plain;
+  for (const Command &k : COMMANDS)
+    if (a.cmd == k.name) c = &k;
+  const bool view = a.cmd == "view", rewrite = a.cmd == "htsjdk-rewrite", tally = a.cmd == "flagstat" || a.cmd == "idxstats";
   const bool fq = a.cmd == "fastq" || a.cmd == "fasta", pile = a.cmd == "pileup" || a.cmd == "consensus";
   std::vector<std::string> pos;
   for (int i = 2; i < argc; ++i) {
@@ -340,73 +374,42 @@ Args parse(int argc, char **argv) {
       if (i + 1 >= argc) throw Error(SBH_E_ARG, "missing value for " + t);
       return argv[++i];
     };
-    if (rewrite && (t == "-r" || t == "--read-ranges")) { a.read_ranges = parse_ranges(next()); a.has_read_ranges = true; }
+    auto is = [&](unsigned opt, const char *brief, const char *full) { return (c->opts & opt) && (t == brief || t == full); };
+    // the shared options, where the command's row has them
+    if (is(O_FILTER, "-f", "--require-flags")) a.flag_require = (uint32_t)parse_int(next());
+    else if (is(O_FILTER, "-F", "--exclude-flags")) { a.flag_exclude = (uint32_t)parse_int(next()); a.has_exclude = true; }
+    else if (is(O_FILTER, "-q", "--min-mapq")) a.min_mapq = (int)parse_int(next());
+    else if (is(O_OUT, "-o", "--output")) a.out = next();
+    else if (is(O_REGION, "-r", "--region")) a.region = next();
+    else if (is(O_LEVEL, "-l", "--level")) { a.level = (int)parse_int(next()); a.has_level = true; }
+    else if (is(O_BAI, "--index-bai", "--index-bai")) a.idx_bai = true;
+    // each command's own
+    else if ((rewrite || view) && (t == "-r" || t == "--read-ranges")) { a.read_ranges = parse_ranges(next()); a.has_read_ranges = true; }
     else if (rewrite && (t == "-b" || t == "--index-blocks")) a.idx_blocks = true;
     else if (rewrite && (t == "-i" || t == "--index-records")) a.idx_records = true;
-    else if (rewrite && t == "--index-bai") a.idx_bai = true;
-    else if (a.cmd == "view" && (t == "-h" || t == "--header")) a.sam_header = true;
-    else if (a.cmd == "view" && (t == "-o" || t == "--output")) a.out = next();
-    else if (a.cmd == "view" && (t == "-b" || t == "--bam")) a.bam_out = true;
-    else if (a.cmd == "view" && (t == "-f" || t == "--require-flags")) a.flag_require = (uint32_t)parse_int(next());
-    else if (a.cmd == "view" && (t == "-F" || t == "--exclude-flags")) a.flag_exclude = (uint32_t)parse_int(next());
-    else if (a.cmd == "view" && (t == "-q" || t == "--min-mapq")) a.min_mapq = (int)parse_int(next());
-    else if (a.cmd == "view" && (t == "-r" || t == "--read-ranges")) { a.read_ranges = parse_ranges(next()); a.has_read_ranges = true; }
-    else if (a.cmd == "view" && (t == "-l" || t == "--level")) a.level = (int)parse_int(next());
-    else if (a.cmd == "view" && t == "--index-bai") a.idx_bai = true;
-    else if (a.cmd == "view" && t == "--sort") a.sort = true;
-    else if (a.cmd == "view" && (t == "-c" || t == "--count")) a.count_only = true;
-    else if (tally && (t == "-f" || t == "--require-flags")) a.flag_require = (uint32_t)parse_int(next());
-    else if (tally && (t == "-F" || t == "--exclude-flags")) a.flag_exclude = (uint32_t)parse_int(next());
-    else if (tally && (t == "-q" || t == "--min-mapq")) a.min_mapq = (int)parse_int(next());
-    else if (tally && (t == "-o" || t == "--output")) a.out = next();
-    else if (tally && t.size() > 1 && t[0] == '-') throw Error(SBH_E_ARG, "usage: " + a.cmd + " [-f INT] [-F INT] [-q INT] [-o FILE] <bam> (unknown option " + t + ")");
-    else if (a.cmd == "stats" && (t == "-f" || t == "--require-flags")) a.flag_require = (uint32_t)parse_int(next());
-    else if (a.cmd == "stats" && (t == "-F" || t == "--exclude-flags")) a.flag_exclude = (uint32_t)parse_int(next());
-    else if (a.cmd == "stats" && (t == "-q" || t == "--min-mapq")) a.min_mapq = (int)parse_int(next());
+    else if (view && (t == "-h" || t == "--header")) a.sam_header = true;
+    else if (view && (t == "-b" || t == "--bam")) a.bam_out = true;
+    else if (view && t == "--sort") a.sort = true;
+    else if (view && (t == "-c" || t == "--count")) a.count_only = true;
     else if (a.cmd == "stats" && t == "--cycles") a.stat_cycles = parse_int(next());
     else if (a.cmd == "stats" && (t == "-i" || t == "--insert-size")) a.stat_insert = parse_int(next());
-    else if (a.cmd == "stats" && (t == "-o" || t == "--output")) a.out = next();
-    else if (a.cmd == "stats" && t.size() > 1 && t[0] == '-')
-      throw Error(SBH_E_ARG, "usage: stats [-f INT] [-F INT] [-q INT] [--cycles N] [-i MAX_INSERT] [-o FILE] <bam> (unknown option " + t + ")");
-    else if (fq && (t == "-o" || t == "--output")) a.out = next();
     else if (fq && t == "-1") a.out_part[0] = next();
     else if (fq && t == "-2") a.out_part[1] = next();
     else if (fq && t == "-0") a.out_part[2] = next();
     else if (fq && t == "-n") a.suffix_never = true;
     else if (fq && t == "-N") a.suffix_always = true;
-    else if (fq && (t == "-f" || t == "--require-flags")) a.flag_require = (uint32_t)parse_int(next());
-    else if (fq && (t == "-F" || t == "--exclude-flags")) { a.flag_exclude = (uint32_t)parse_int(next()); a.has_exclude = true; }
-    else if (fq && (t == "-q" || t == "--min-mapq")) a.min_mapq = (int)parse_int(next());
     else if (fq && t == "-v") a.def_qual = (int)parse_int(next());
-    else if (fq && (t == "-l" || t == "--level")) { a.level = (int)parse_int(next()); a.has_level = true; }
-    else if (fq && t.size() > 1 && t[0] == '-')
-      throw Error(SBH_E_ARG, "usage: " + a.cmd + " [-o FILE] [-1 FILE] [-2 FILE] [-0 FILE] [-n|-N] [-f INT] [-F INT] [-q INT] [-v INT] "
-                                                 "[--level N] <bam> (unknown option " + t + ")");
-    else if (a.cmd == "depth" && t == "-a") a.depth_all = true;
-    else if (a.cmd == "depth" && (t == "-r" || t == "--region")) a.region = next();
-    else if (a.cmd == "depth" && (t == "-f" || t == "--require-flags")) a.flag_require = (uint32_t)parse_int(next());
-    else if (a.cmd == "depth" && (t == "-F" || t == "--exclude-flags")) { a.flag_exclude = (uint32_t)parse_int(next()); a.has_exclude = true; }
-    else if (a.cmd == "depth" && (t == "-q" || t == "--min-mapq")) a.min_mapq = (int)parse_int(next());
+    else if ((a.cmd == "depth" || a.cmd == "pileup") && t == "-a") a.depth_all = true;
     else if (a.cmd == "depth" && t == "-J") a.count_del = true;
     else if (a.cmd == "depth" && t == "--bedgraph") a.bedgraph = true;
-    else if (a.cmd == "depth" && (t == "-o" || t == "--output")) a.out = next();
-    else if (pile && t == "-a" && a.cmd == "pileup") a.depth_all = true;
-    else if (pile && t == "-H" && a.cmd == "pileup") a.pile_header = true;
-    else if (pile && (t == "-r" || t == "--region")) a.region = next();
-    else if (pile && (t == "-f" || t == "--require-flags")) a.flag_require = (uint32_t)parse_int(next());
-    else if (pile && (t == "-F" || t == "--exclude-flags")) { a.flag_exclude = (uint32_t)parse_int(next()); a.has_exclude = true; }
-    else if (pile && (t == "-q" || t == "--min-mapq")) a.min_mapq = (int)parse_int(next());
+    else if (a.cmd == "pileup" && t == "-H") a.pile_header = true;
     else if (pile && (t == "-Q" || t == "--min-baseq")) a.min_baseq = (int)parse_int(next());
-    else if (pile && t == "-d" && a.cmd == "consensus") a.min_depth = (int)parse_int(next());
-    else if (pile && t == "-c" && a.cmd == "consensus") a.call_pct = (int)parse_int(next());
+    else if (a.cmd == "consensus" && t == "-d") a.min_depth = (int)parse_int(next());
+    else if (a.cmd == "consensus" && t == "-c") a.call_pct = (int)parse_int(next());
     else if (pile && t == "--max-positions") a.max_positions = parse_int(next());
-    else if (pile && (t == "-o" || t == "--output")) a.out = next();
-    else if (pile && t.size() > 1 && t[0] == '-')
-      throw Error(SBH_E_ARG, a.cmd == "pileup" ? "usage: pileup [-a] [-H] [-r REGION] [-f INT] [-F INT] [-q INT] [-Q INT] [-o FILE] <bam> (unknown option " + t + ")"
-                                               : "usage: consensus [-r REGION] [-f INT] [-F INT] [-q INT] [-Q INT] [-d MIN_DEPTH] [-c PCT] [-o FILE] <bam> (unknown option " + t + ")");
-    else if (a.cmd == "sort" && (t == "-o" || t == "--output")) a.out = next();
-    else if (a.cmd == "sort" && (t == "-l" || t == "--level")) a.level = (int)parse_int(next());
-    else if (a.cmd == "sort" && t == "--index-bai") a.idx_bai = true;
+    else if (c->strict && t.size() > 1 && t[0] == '-')
+      throw Error(SBH_E_ARG, "usage: " + a.cmd + " " + c->synopsis + " (unknown option " + t + ")");
+    // the reference's commands' options, wherever no row above claims the letter
     else if (t == "-m" || t == "--max-split-size") { a.split = parse_bytes(next()); a.has_split = true; }
     else if (t == "-s" || t == "--spark-bam") a.s = true;
     else if (t == "-u" || t == "--upstream" || t == "--hadoop-bam") a.u = true;
@@ -438,6 +441,77 @@ Args parse(int argc, char **argv) {
   if (a.cmd == "view" && a.bam_out && a.out.empty())
     throw Error(SBH_E_ARG, "usage: view -b needs -o OUT (a BAM is not written to the terminal)");
   return a;
+}
+
+// The frame of the record commands: the eager calls and the record scan over the records of the
+// stream's first segment, the -f / -F / -q filter, an accumulator's handle, and the sink.
+
+// The eager calls over the records; false: the file has none, and nothing ran.
+bool eager_calls(Loaded &L, const Args &a) {
+  const uint64_t end = L.seg_end();
+  if (end <= L.hdr.end) return false;
+  uint64_t n = 0;
+  chk(sbh_check_eager(L.sh, L.hdr.end, end, a.reads_to_check, nullptr, &n), "eager");
+  return true;
+}
+
+// eager_calls, then sbh_records_scan -- over no records too when `always` (view -b: its gather then
+// finds the scan of no rows); false: the file has no records.
+bool scan_records(Loaded &L, const Args &a, bool always = false) {
+  const bool any = eager_calls(L, a);
+  sbh_records_sizes rs{};
+  if (any || always) chk(sbh_records_scan(L.sh, L.hdr.end, L.seg_end(), &rs), "records scan");
+  return any;
+}
+
+sbh_record_filter filter_of(const Args &a) {
+  sbh_record_filter f{};
+  f.flag_require = a.flag_require;
+  f.flag_exclude = a.flag_exclude;
+  f.min_mapq = a.min_mapq;
+  return f;
+}
+
+template <class T, int (*Destroy)(T *)>
+struct Owned {  // a library handle, destroyed on the way out
+  T *p = nullptr;
+  ~Owned() { Destroy(p); }
+};
+
+// -o FILE, or the terminal.  Text gathers in `text` and goes out whenever 1 MiB of it has (spill) and
+// at the end (close), which throws when any write fell short.
+struct Sink {
+  std::string path, text;  // (path "": the terminal)
+  FILE *f;
+  bool ok = true;
+  explicit Sink(const std::string &p) : path(p), f(p.empty() ? stdout : fopen(p.c_str(), "wb")) {
+    if (!f) throw Error(SBH_E_ARG, "cannot write " + path);
+  }
+  Sink(const Sink &) = delete;
+  ~Sink() {
+    if (f && f != stdout) fclose(f);
+  }
+  void write(const void *p, size_t n) { ok = ok && fwrite(p, 1, n, f) == n; }
+  void spill(bool all = false) {
+    if (all || text.size() >= (1u << 20)) {
+      write(text.data(), text.size());
+      text.clear();
+    }
+  }
+  void close() {
+    spill(true);
+    ok = ok && fflush(f) == 0;
+    if (f != stdout) fclose(f);
+    f = nullptr;
+    if (!ok) throw Error(SBH_E_ARG, "short write to " + (path.empty() ? std::string("stdout") : path));
+  }
+};
+
+// a command's whole output at once
+void write_out(const std::string &path, const void *p, size_t n) {
+  Sink out(path);
+  out.write(p, n);
+  out.close();
 }
 
 void no_hadoop_bam() {
@@ -987,9 +1061,7 @@ int index_blocks(const Args &a) {
 
 int index_records(const Args &a) {
   Loaded L(a.path);
-  uint64_t seg_end = L.flat;
-  for (const sbh_block &b : L.blocks)
-    if (b.flags & SBH_BLOCK_EMPTY) { seg_end = b.ustart; break; }
+  const uint64_t seg_end = L.seg_end();
   std::vector<uint8_t> bits((seg_end - L.hdr.end + 7) / 8);
   uint64_t n = 0, chain = 0;
   chk(sbh_check_eager(L.sh, L.hdr.end, seg_end, a.reads_to_check, bits.data(), &n), "eager");
@@ -1011,15 +1083,9 @@ int index_records(const Args &a) {
 // equal (ref_id, bin) and linear-index minima on the device, sbh_bai_build finishes on the host.
 int index_bai(const Args &a) {
   Loaded L(a.path);
-  uint64_t seg_end = L.flat;
-  for (const sbh_block &b : L.blocks)
-    if (b.flags & SBH_BLOCK_EMPTY) { seg_end = b.ustart; break; }
-  if (seg_end > L.hdr.end) {
-    uint64_t n = 0;
-    chk(sbh_check_eager(L.sh, L.hdr.end, seg_end, a.reads_to_check, nullptr, &n), "eager");
-  }
+  eager_calls(L, a);
   sbh_bai_sizes sz{};
-  chk(sbh_bai_scan(L.sh, L.hdr.end, seg_end, &sz), "bai scan");
+  chk(sbh_bai_scan(L.sh, L.hdr.end, L.seg_end(), &sz), "bai scan");
   std::vector<sbh_bai_run> runs(sz.n_runs);
   std::vector<uint64_t> lin(sz.lin_size);
   chk(sbh_bai_fetch(L.sh, runs.data(), lin.data()), "bai fetch");
@@ -1029,12 +1095,7 @@ int index_bai(const Args &a) {
   const int rc = sbh_bai_build(runs.data(), runs.size(), lin.data(), L.hdr.lens.data(), n_ref, sz.n_no_coor, bai.data(),
                                bai.size(), &size);
   if (rc) throw Error(rc, "bai build failed (status " + std::to_string(rc) + ")");
-  std::string out = a.out.empty() ? a.path + ".bai" : a.out;
-  FILE *f = fopen(out.c_str(), "wb");
-  if (!f) throw Error(SBH_E_ARG, "cannot write " + out);
-  const bool ok = fwrite(bai.data(), 1, size, f) == size;
-  fclose(f);
-  if (!ok) throw Error(SBH_E_ARG, "short write to " + out);
+  write_out(a.out.empty() ? a.path + ".bai" : a.out, bai.data(), size);
   return 0;
 }
 
@@ -1052,9 +1113,6 @@ int view(const Args &a) {
   if (a.has_read_ranges || a.flag_require || a.flag_exclude || a.min_mapq || a.idx_bai || a.sort)
     throw Error(SBH_E_ARG, "view: -f / -F / -q / -r / --index-bai / --sort select records for BAM output: they need -b");
   Loaded L(a.path);
-  uint64_t seg_end = L.flat;
-  for (const sbh_block &b : L.blocks)
-    if (b.flags & SBH_BLOCK_EMPTY) { seg_end = b.ustart; break; }
   std::vector<char> text;
   uint64_t head = 0;
   if (a.sam_header) {
@@ -1066,11 +1124,7 @@ int view(const Args &a) {
     text.resize(head);
     if (head) chk(sbh_read_flat(L.sh, 8, head, (uint8_t *)text.data()), "read header text");
   }
-  if (seg_end > L.hdr.end) {
-    uint64_t n = 0;
-    chk(sbh_check_eager(L.sh, L.hdr.end, seg_end, a.reads_to_check, nullptr, &n), "eager");
-    sbh_records_sizes rs{};
-    chk(sbh_records_scan(L.sh, L.hdr.end, seg_end, &rs), "records scan");
+  if (scan_records(L, a)) {
     std::string names;
     std::vector<uint64_t> off(1, 0);
     for (const std::string &s : L.hdr.names) {
@@ -1082,11 +1136,7 @@ int view(const Args &a) {
     text.resize(head + sz.text_bytes);
     chk(sbh_records_sam_fetch(L.sh, text.data() + head, nullptr), "sam fetch");
   }
-  FILE *f = a.out.empty() ? stdout : fopen(a.out.c_str(), "wb");
-  if (!f) throw Error(SBH_E_ARG, "cannot write " + a.out);
-  const bool ok = fwrite(text.data(), 1, text.size(), f) == text.size() && fflush(f) == 0;
-  if (f != stdout) fclose(f);
-  if (!ok) throw Error(SBH_E_ARG, "short write to " + (a.out.empty() ? std::string("stdout") : a.out));
+  write_out(a.out, text.data(), text.size());
   return 0;
 }
 
@@ -1099,9 +1149,6 @@ int view_bam(const Args &a) {
   uint64_t size = 0, nb = 0;
   {
     Loaded L(a.path);
-    uint64_t seg_end = L.flat;
-    for (const sbh_block &b : L.blocks)
-      if (b.flags & SBH_BLOCK_EMPTY) { seg_end = b.ustart; break; }
     std::vector<uint8_t> head(L.hdr.end);
     if (L.hdr.end) chk(sbh_read_flat(L.sh, 0, L.hdr.end, head.data()), "read header");
     if (a.sort) {
@@ -1111,12 +1158,7 @@ int view_bam(const Args &a) {
       so.resize(so_n);
       head.swap(so);
     }
-    sbh_records_sizes rs{};
-    if (seg_end > L.hdr.end) {
-      uint64_t n = 0;
-      chk(sbh_check_eager(L.sh, L.hdr.end, seg_end, a.reads_to_check, nullptr, &n), "eager");
-    }
-    chk(sbh_records_scan(L.sh, L.hdr.end, seg_end, &rs), "records scan");
+    scan_records(L, a, true);
     // -r as given -> sorted, disjoint ranges
     std::vector<std::pair<uint64_t, uint64_t>> rr = a.read_ranges;
     std::sort(rr.begin(), rr.end());
@@ -1125,10 +1167,7 @@ int view_bam(const Args &a) {
       if (!re.empty() && r.first <= re.back()) re.back() = std::max(re.back(), r.second);
       else { rb.push_back(r.first); re.push_back(r.second); }
     }
-    sbh_record_filter f{};
-    f.flag_require = a.flag_require;
-    f.flag_exclude = a.flag_exclude;
-    f.min_mapq = a.min_mapq;
+    sbh_record_filter f = filter_of(a);
     f.row_begin = rb.data();
     f.row_end = re.data();
     f.n_row_ranges = rb.size();
@@ -1140,11 +1179,7 @@ int view_bam(const Args &a) {
                                 &nb, nullptr),
         "bgzf compress");
   }
-  FILE *f = fopen(a.out.c_str(), "wb");
-  if (!f) throw Error(SBH_E_ARG, "cannot write " + a.out);
-  const bool ok = fwrite(out.data(), 1, size, f) == size;
-  fclose(f);
-  if (!ok) throw Error(SBH_E_ARG, "short write to " + a.out);
+  write_out(a.out, out.data(), size);
   if (a.idx_bai) {
     Args ix = a;
     ix.path = a.out;
@@ -1194,37 +1229,22 @@ std::vector<sbh_depth_span> region_spans(const Header &hdr, const std::string &r
 // NAME:BEG-END with 1-based inclusive positions; none: every reference whole.
 int depth(const Args &a) {
   Loaded L(a.path);
-  uint64_t seg_end = L.flat;
-  for (const sbh_block &b : L.blocks)
-    if (b.flags & SBH_BLOCK_EMPTY) { seg_end = b.ustart; break; }
   const int32_t n_ref = (int32_t)L.hdr.lens.size();
   const std::vector<sbh_depth_span> spans = region_spans(L.hdr, a.region, "depth");
-  struct Acc {
-    sbh_depth *d = nullptr;
-    ~Acc() { sbh_depth_destroy(d); }
-  } acc;
-  chk(sbh_depth_create(g_ctx, spans.data(), (uint32_t)spans.size(), n_ref, a.count_del ? SBH_DEPTH_DEL : 0u, &acc.d),
+  Owned<sbh_depth, sbh_depth_destroy> acc;
+  chk(sbh_depth_create(g_ctx, spans.data(), (uint32_t)spans.size(), n_ref, a.count_del ? SBH_DEPTH_DEL : 0u, &acc.p),
       "depth create");
-  if (seg_end > L.hdr.end) {
-    uint64_t n = 0;
-    chk(sbh_check_eager(L.sh, L.hdr.end, seg_end, a.reads_to_check, nullptr, &n), "eager");
-    sbh_records_sizes rs{};
-    chk(sbh_records_scan(L.sh, L.hdr.end, seg_end, &rs), "records scan");
-    sbh_record_filter f{};
-    f.flag_require = a.flag_require;
-    f.flag_exclude = a.flag_exclude;
-    f.min_mapq = a.min_mapq;
+  if (scan_records(L, a)) {
+    const sbh_record_filter f = filter_of(a);
     sbh_depth_add_result ar{};
-    chk(sbh_records_depth_add(L.sh, acc.d, &f, &ar), "depth add");
+    chk(sbh_records_depth_add(L.sh, acc.p, &f, &ar), "depth add");
   }
   sbh_depth_sizes sz{};
-  chk(sbh_depth_finish(acc.d, &sz), "depth finish");
+  chk(sbh_depth_finish(acc.p, &sz), "depth finish");
   std::vector<sbh_depth_run> runs(sz.n_runs);
-  chk(sbh_depth_runs_fetch(acc.d, 0, sz.n_runs, runs.data()), "depth runs");
-  FILE *f = a.out.empty() ? stdout : fopen(a.out.c_str(), "wb");
-  if (!f) throw Error(SBH_E_ARG, "cannot write " + a.out);
-  bool ok = true;
-  std::string text;
+  chk(sbh_depth_runs_fetch(acc.p, 0, sz.n_runs, runs.data()), "depth runs");
+  Sink out(a.out);
+  std::string &text = out.text;
   for (const sbh_depth_run &r : runs) {
     if (!r.depth && !(a.depth_all && !a.bedgraph)) continue;
     const std::string &name = L.hdr.names[r.ref_id];
@@ -1237,16 +1257,11 @@ int depth(const Args &a) {
         text += '\t';
         text += std::to_string(p);
         text += tail;
-        if (text.size() >= (1u << 20)) {
-          ok = ok && fwrite(text.data(), 1, text.size(), f) == text.size();
-          text.clear();
-        }
+        out.spill();
       }
     }
   }
-  ok = ok && fwrite(text.data(), 1, text.size(), f) == text.size() && fflush(f) == 0;
-  if (f != stdout) fclose(f);
-  if (!ok) throw Error(SBH_E_ARG, "short write to " + (a.out.empty() ? std::string("stdout") : a.out));
+  out.close();
   return 0;
 }
 
@@ -1257,9 +1272,6 @@ int depth(const Args &a) {
 // the intervals' positions (-a: of every position), consensus the call bytes as FASTA.
 int pileup(const Args &a) {
   Loaded L(a.path);
-  uint64_t seg_end = L.flat;
-  for (const sbh_block &b : L.blocks)
-    if (b.flags & SBH_BLOCK_EMPTY) { seg_end = b.ustart; break; }
   const int32_t n_ref = (int32_t)L.hdr.lens.size();
   const std::vector<sbh_depth_span> spans = region_spans(L.hdr, a.region, a.cmd);
   uint64_t positions = 0, budget = 0;
@@ -1269,35 +1281,17 @@ int pileup(const Args &a) {
   if (positions > budget)
     throw Error(SBH_E_ARG, a.cmd + ": " + std::to_string(positions) + " positions at 33 bytes each do not fit the device memory budget of " +
                                std::to_string(budget) + " positions: give a region with -r");
-  struct Acc {
-    sbh_pileup *p = nullptr;
-    ~Acc() { sbh_pileup_destroy(p); }
-  } acc;
+  Owned<sbh_pileup, sbh_pileup_destroy> acc;
   chk(sbh_pileup_create(g_ctx, spans.data(), (uint32_t)spans.size(), n_ref, a.min_baseq, &acc.p), "pileup create");
-  if (seg_end > L.hdr.end) {
-    uint64_t n = 0;
-    chk(sbh_check_eager(L.sh, L.hdr.end, seg_end, a.reads_to_check, nullptr, &n), "eager");
-    sbh_records_sizes rs{};
-    chk(sbh_records_scan(L.sh, L.hdr.end, seg_end, &rs), "records scan");
-    sbh_record_filter f{};
-    f.flag_require = a.flag_require;
-    f.flag_exclude = a.flag_exclude;
-    f.min_mapq = a.min_mapq;
+  if (scan_records(L, a)) {
+    const sbh_record_filter f = filter_of(a);
     sbh_pileup_add_result ar{};
     chk(sbh_records_pileup_add(L.sh, acc.p, &f, &ar), "pileup add");
   }
   sbh_pileup_sizes sz{};
   chk(sbh_pileup_finish(acc.p, (uint32_t)std::max(a.min_depth, 0), (uint32_t)std::max(a.call_pct, 0), &sz), "pileup finish");
-  FILE *f = a.out.empty() ? stdout : fopen(a.out.c_str(), "wb");
-  if (!f) throw Error(SBH_E_ARG, "cannot write " + a.out);
-  bool ok = true;
-  std::string text;
-  auto flush = [&](bool all) {
-    if (all || text.size() >= (1u << 20)) {
-      ok = ok && fwrite(text.data(), 1, text.size(), f) == text.size();
-      text.clear();
-    }
-  };
+  Sink out(a.out);
+  std::string &text = out.text;
   constexpr uint64_t CHUNK = 1 << 16;  // positions fetched at a time
   if (a.cmd == "consensus") {
     std::vector<uint8_t> calls(CHUNK);
@@ -1316,7 +1310,7 @@ int pileup(const Args &a) {
           text += calls[i] ? (char)calls[i] : 'N';
           if (++col == 60) text += '\n', col = 0;
         }
-        flush(false);
+        out.spill();
       }
       if (col) text += '\n';
     }
@@ -1347,15 +1341,12 @@ int pileup(const Args &a) {
               text += std::to_string(counts[8 * i + ch]);
             }
             text += '\n';
-            flush(false);
+            out.spill();
           }
         }
     }
   }
-  flush(true);
-  ok = ok && fflush(f) == 0;
-  if (f != stdout) fclose(f);
-  if (!ok) throw Error(SBH_E_ARG, "short write to " + (a.out.empty() ? std::string("stdout") : a.out));
+  out.close();
   return 0;
 }
 
@@ -1365,38 +1356,21 @@ int pileup(const Args &a) {
 // reference and its `*` line, or (view -c) the number of records kept.
 int tally(const Args &a) {
   Loaded L(a.path);
-  uint64_t seg_end = L.flat;
-  for (const sbh_block &b : L.blocks)
-    if (b.flags & SBH_BLOCK_EMPTY) { seg_end = b.ustart; break; }
   const int32_t n_ref = (int32_t)L.hdr.lens.size();
-  struct Acc {
-    sbh_tally *t = nullptr;
-    ~Acc() { sbh_tally_destroy(t); }
-  } acc;
-  chk(sbh_tally_create(g_ctx, n_ref, &acc.t), "tally create");
+  Owned<sbh_tally, sbh_tally_destroy> acc;
+  chk(sbh_tally_create(g_ctx, n_ref, &acc.p), "tally create");
   sbh_tally_add_result ar{};
-  if (seg_end > L.hdr.end) {
-    uint64_t n = 0;
-    chk(sbh_check_eager(L.sh, L.hdr.end, seg_end, a.reads_to_check, nullptr, &n), "eager");
-    sbh_records_sizes rs{};
-    chk(sbh_records_scan(L.sh, L.hdr.end, seg_end, &rs), "records scan");
-    sbh_record_filter f{};
-    f.flag_require = a.flag_require;
-    f.flag_exclude = a.flag_exclude;
-    f.min_mapq = a.min_mapq;
-    chk(sbh_records_tally_add(L.sh, acc.t, &f, &ar), "tally add");
+  if (scan_records(L, a)) {
+    const sbh_record_filter f = filter_of(a);
+    chk(sbh_records_tally_add(L.sh, acc.p, &f, &ar), "tally add");
   }
   std::vector<uint64_t> flag(2 * SBH_TALLY_ROWS), ref(2 * ((size_t)n_ref + 1));
-  chk(sbh_tally_fetch(acc.t, flag.data(), 0, (uint64_t)n_ref + 1, ref.data()), "tally fetch");
+  chk(sbh_tally_fetch(acc.p, flag.data(), 0, (uint64_t)n_ref + 1, ref.data()), "tally fetch");
   std::string text;
   if (a.count_only) text = std::to_string(ar.n_kept) + "\n";
   else if (a.cmd == "flagstat") text = sbh_tal::flagstat_text(flag.data());
   else text = sbh_tal::idxstats_text(ref.data(), L.hdr.names.data(), L.hdr.lens.data(), n_ref);
-  FILE *f = a.out.empty() ? stdout : fopen(a.out.c_str(), "wb");
-  if (!f) throw Error(SBH_E_ARG, "cannot write " + a.out);
-  const bool ok = fwrite(text.data(), 1, text.size(), f) == text.size() && fflush(f) == 0;
-  if (f != stdout) fclose(f);
-  if (!ok) throw Error(SBH_E_ARG, "short write to " + (a.out.empty() ? std::string("stdout") : a.out));
+  write_out(a.out, text.data(), text.size());
   return 0;
 }
 
@@ -1407,39 +1381,22 @@ int stats(const Args &a) {
   if (a.stat_cycles < 1 || a.stat_cycles > (long)sbh_stat::STAT_CYCLES_MAX || a.stat_insert < 1 || a.stat_insert > (long)sbh_stat::STAT_INSERT_MAX)
     throw Error(SBH_E_ARG, "stats: --cycles takes 1.." + std::to_string(sbh_stat::STAT_CYCLES_MAX) + ", -i 1.." + std::to_string(sbh_stat::STAT_INSERT_MAX));
   Loaded L(a.path);
-  uint64_t seg_end = L.flat;
-  for (const sbh_block &b : L.blocks)
-    if (b.flags & SBH_BLOCK_EMPTY) { seg_end = b.ustart; break; }
-  struct Acc {
-    sbh_stats *s = nullptr;
-    ~Acc() { sbh_stats_destroy(s); }
-  } acc;
+  Owned<sbh_stats, sbh_stats_destroy> acc;
   const sbh_stats_params prm{(uint32_t)a.stat_cycles, (uint32_t)a.stat_insert};
-  chk(sbh_stats_create(g_ctx, &prm, &acc.s), "stats create");
-  if (seg_end > L.hdr.end) {
-    uint64_t n = 0;
-    chk(sbh_check_eager(L.sh, L.hdr.end, seg_end, a.reads_to_check, nullptr, &n), "eager");
-    sbh_records_sizes rs{};
-    chk(sbh_records_scan(L.sh, L.hdr.end, seg_end, &rs), "records scan");
-    sbh_record_filter f{};
-    f.flag_require = a.flag_require;
-    f.flag_exclude = a.flag_exclude;
-    f.min_mapq = a.min_mapq;
+  chk(sbh_stats_create(g_ctx, &prm, &acc.p), "stats create");
+  if (scan_records(L, a)) {
+    const sbh_record_filter f = filter_of(a);
     sbh_stats_add_result ar{};
-    chk(sbh_records_stats_add(L.sh, acc.s, &f, &ar), "stats add");
+    chk(sbh_records_stats_add(L.sh, acc.p, &f, &ar), "stats add");
   }
   const sbh_stat::Params P{prm.cycles, prm.max_insert};
   const sbh_stat::Layout lay = sbh_stat::layout_of(P);
   std::vector<uint64_t> w(lay.words);
   const sbh_stat::Tables T{w.data(), w.data() + lay.read_len, w.data() + lay.qual, w.data() + lay.base, w.data() + lay.gc,
                            w.data() + lay.isize, w.data() + lay.mapq};
-  chk(sbh_stats_fetch(acc.s, T.sn, T.read_len, T.qual, T.base, T.gc, T.isize, T.mapq), "stats fetch");
+  chk(sbh_stats_fetch(acc.p, T.sn, T.read_len, T.qual, T.base, T.gc, T.isize, T.mapq), "stats fetch");
   const std::string text = sbh_stat::stats_text(P, T);
-  FILE *f = a.out.empty() ? stdout : fopen(a.out.c_str(), "wb");
-  if (!f) throw Error(SBH_E_ARG, "cannot write " + a.out);
-  const bool ok = fwrite(text.data(), 1, text.size(), f) == text.size() && fflush(f) == 0;
-  if (f != stdout) fclose(f);
-  if (!ok) throw Error(SBH_E_ARG, "short write to " + (a.out.empty() ? std::string("stdout") : a.out));
+  write_out(a.out, text.data(), text.size());
   return 0;
 }
 
@@ -1455,33 +1412,23 @@ int fastq(const Args &a) {
   const uint32_t mode = (a.cmd == "fasta" ? SBH_FASTQ_FASTA : 0u) | (split ? SBH_FASTQ_SPLIT : 0u) |
                         (a.suffix_always ? SBH_FASTQ_SUFFIX_ALWAYS : a.suffix_never ? 0u : SBH_FASTQ_SUFFIX);
   Loaded L(a.path);
-  uint64_t seg_end = L.flat;
-  for (const sbh_block &b : L.blocks)
-    if (b.flags & SBH_BLOCK_EMPTY) { seg_end = b.ustart; break; }
   sbh_fastq_sizes sz{};
-  if (seg_end > L.hdr.end) {
-    uint64_t n = 0;
-    chk(sbh_check_eager(L.sh, L.hdr.end, seg_end, a.reads_to_check, nullptr, &n), "eager");
-    sbh_records_sizes rs{};
-    chk(sbh_records_scan(L.sh, L.hdr.end, seg_end, &rs), "records scan");
-    sbh_record_filter f{};
-    f.flag_require = a.flag_require;
-    f.flag_exclude = a.flag_exclude;
-    f.min_mapq = a.min_mapq;
+  if (scan_records(L, a)) {
+    const sbh_record_filter f = filter_of(a);
     chk(sbh_records_fastq_scan(L.sh, &f, mode, a.def_qual, &sz), "fastq scan");
   }
   // the sink of each part (a path; "": the terminal), a sink named twice opened once
-  struct Sink {
+  struct PartSink {
     std::string path;
     FILE *f = nullptr;
     bool gz = false;
   };
-  std::vector<Sink> sinks;
+  std::vector<PartSink> sinks;
   int of_part[sbh_fq::PARTS] = {-1, -1, -1};
   auto sink_of = [&](const std::string &path) {
     for (size_t k = 0; k < sinks.size(); ++k)
       if (sinks[k].path == path) return (int)k;
-    Sink s;
+    PartSink s;
     s.path = path;
     s.gz = a.has_level || (path.size() > 3 && path.compare(path.size() - 3, 3, ".gz") == 0);
     s.f = path.empty() ? stdout : fopen(path.c_str(), "wb");
@@ -1508,7 +1455,7 @@ int fastq(const Args &a) {
   for (uint32_t p = 0; p < sbh_fq::PARTS; ++p) {
     const uint64_t nb = sz.part_bytes[p];
     if (nb && of_part[p] >= 0) {
-      Sink &s = sinks[of_part[p]];
+      PartSink &s = sinks[of_part[p]];
       if (!s.gz) {
         ok = ok && fwrite(text.data() + at, 1, nb, s.f) == nb;
       } else {
@@ -1522,7 +1469,7 @@ int fastq(const Args &a) {
     at += nb;
   }
   static const uint8_t eof_member[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  for (Sink &s : sinks) {
+  for (PartSink &s : sinks) {
     if (s.gz) ok = ok && fwrite(eof_member, 1, 28, s.f) == 28;
     ok = ok && fflush(s.f) == 0;
     if (s.f != stdout) fclose(s.f);
@@ -1543,9 +1490,7 @@ int htsjdk_rewrite(const Args &a) {
   std::vector<uint8_t> payload;
   {
     Loaded L(a.path);
-    uint64_t seg_end = L.flat;
-    for (const sbh_block &b : L.blocks)
-      if (b.flags & SBH_BLOCK_EMPTY) { seg_end = b.ustart; break; }
+    const uint64_t seg_end = L.seg_end();
     std::vector<uint8_t> flat(seg_end);
     if (seg_end) chk(sbh_read_flat(L.sh, 0, seg_end, flat.data()), "read stream");
     if (!a.has_read_ranges) {
@@ -1572,11 +1517,7 @@ int htsjdk_rewrite(const Args &a) {
   uint64_t size = 0, nb = 0;
   chk(sbh_bgzf_compress(g_ctx, payload.data(), payload.size(), 0, out.data(), out.size(), &size, &nb, nullptr),
       "bgzf compress");
-  FILE *f = fopen(a.out.c_str(), "wb");
-  if (!f) throw Error(SBH_E_ARG, "cannot write " + a.out);
-  const bool ok = fwrite(out.data(), 1, size, f) == size;
-  fclose(f);
-  if (!ok) throw Error(SBH_E_ARG, "short write to " + a.out);
+  write_out(a.out, out.data(), size);
   Args ix = a;
   ix.path = a.out;
   ix.out.clear();

@@ -7,6 +7,7 @@ this module only moves small results around (splits, counts, histograms).
 import ctypes as C
 import os
 from collections import namedtuple
+from contextlib import ExitStack, closing, contextmanager
 
 import numpy as np
 
@@ -112,24 +113,47 @@ def _read(path_or_bytes):
         return np.frombuffer(f.read(), dtype=np.uint8)
 
 
-class _Loaded:
-    """A whole BGZF file resident on one device: indexed, inflated, header parsed."""
+@contextmanager
+def _context(ctx):
+    """The caller's context, or one of our own that is closed on the way out."""
+    own_ctx = ctx is None
+    ctx = ctx or Context(0)
+    try:
+        yield ctx
+    finally:
+        if own_ctx:
+            ctx.close()
+
+
+def _flag_filter(flag_require, flag_exclude, min_mapq):
+    """records.record_filter's dict of the entries' three filter arguments."""
+    return {"flag_require": flag_require, "flag_exclude": flag_exclude, "min_mapq": min_mapq}
+
+
+def _adding(acc, f):
+    """A delivery for _iter_windows: the window's records scanned, and the rows that the filter
+    dict f keeps added to the accumulator; the add's counts are what the walk yields."""
+    def deliver(sh, first, E, _names):
+        sh.records_scan(first, E)
+        return [acc.add(sh, f)]
+    return deliver
+
+
+class _Loaded(ExitStack):
+    """A whole BGZF file resident on one device: indexed, inflated, header parsed.  Leaving it
+    (`with`, or close()) closes the shard, then the context if it is our own."""
 
     def __init__(self, path_or_bytes, ctx=None, reads_to_check=DEFAULT_READS_TO_CHECK):
+        super().__init__()
         self.data = _read(path_or_bytes)
-        self.own_ctx = ctx is None
-        self.ctx = ctx or Context(0)
+        self.ctx = self.enter_context(_context(ctx))
         self.shard = self.ctx.shard(self.data)
+        self.callback(self.shard.close)
         self.shard.index(0)
         self.shard.inflate()
         self.names, self.contig_len, self.header_end = bam_header(self.shard)
         self.shard.set_contigs(self.contig_len)
         self.reads_to_check = reads_to_check
-
-    def close(self):
-        self.shard.close()
-        if self.own_ctx:
-            self.ctx.close()
 
 
 def load_splits_and_reads(path_or_bytes, split_size=DEFAULT_SPLIT_SIZE, ctx=None,
@@ -147,8 +171,7 @@ def load_splits_and_reads(path_or_bytes, split_size=DEFAULT_SPLIT_SIZE, ctx=None
             path_or_bytes, split_size, ctx=ctx, rank=0, world=1, bgzf_blocks_to_check=bgzf_blocks_to_check,
             reads_to_check=reads_to_check, max_read_size=max_read_size)
         return splits, counts
-    L = _Loaded(path_or_bytes, ctx, reads_to_check)
-    try:
+    with _Loaded(path_or_bytes, ctx, reads_to_check) as L:
         sh = L.shard
         # every split in one batch (FindBlockStart + FindRecordStart + counts on the device)
         status, v, n, _ = sh.split_starts(file_splits(L.data.size, split_size), bgzf_blocks_to_check,
@@ -160,8 +183,6 @@ def load_splits_and_reads(path_or_bytes, split_size=DEFAULT_SPLIT_SIZE, ctx=None
         firsts = [Pos.from_htsjdk(int(x)) for x, c in zip(v, n) if c > 0]
         ends = firsts[1:] + [Pos(L.data.size, 0)]
         return [Split(a, b) for a, b in zip(firsts, ends)], counts
-    finally:
-        L.close()
 
 
 def load_reads(path_or_bytes, ctx=None, reads_to_check=DEFAULT_READS_TO_CHECK, window=None):
@@ -176,18 +197,12 @@ def load_reads(path_or_bytes, ctx=None, reads_to_check=DEFAULT_READS_TO_CHECK, w
     from . import sharded
     size = os.path.getsize(path_or_bytes) if isinstance(path_or_bytes, (str, os.PathLike)) else len(path_or_bytes)
     if window is not None or size > sharded.RESIDENT_MAX:
-        own_ctx = ctx is None
-        ctx = ctx or Context(0)
-        try:
+        with _context(ctx) as ctx:
             batches = list(iter_reads(path_or_bytes, window=window or sharded.STREAM_WINDOW, ctx=ctx,
                                       reads_to_check=reads_to_check))
             names = file_header(ctx, _file_array(path_or_bytes))[0]
-        finally:
-            if own_ctx:
-                ctx.close()
         return Reads.concat(batches, names)
-    L = _Loaded(path_or_bytes, ctx, reads_to_check)
-    try:
+    with _Loaded(path_or_bytes, ctx, reads_to_check) as L:
         sh = L.shard
         end = sh.flat_size
         for b in sh.blocks():
@@ -197,8 +212,6 @@ def load_reads(path_or_bytes, ctx=None, reads_to_check=DEFAULT_READS_TO_CHECK, w
         sh.check_eager(L.header_end, end, reads_to_check, want_bits=False)
         cols = sh.records(L.header_end, end)
         return Reads(cols, L.names)
-    finally:
-        L.close()
 
 
 def _vpos_of(flat, blocks):
@@ -225,13 +238,15 @@ def iter_reads(path_or_bytes, window=None, halo=4 << 20, ctx=None, reads_to_chec
 
 def _iter_windows(path_or_bytes, deliver, window=None, halo=4 << 20, ctx=None, reads_to_check=DEFAULT_READS_TO_CHECK):
     """iter_reads' walk through the file; deliver(shard, first_flat, end_flat, names) turns a
-    window's records into what is yielded (anything with a len(): empty ones are dropped)."""
+    window's records into what is yielded (anything with a len(): empty ones are dropped).
+
+    Look first, deliver after: a window whose chain leaves the resident bytes runs again with a
+    larger halo, so the chain's exit is looked at before deliver is called.  deliver is then called
+    once per window and may commit as it goes (add to an accumulator, write to a sink)."""
     window = int(window or STREAM_WINDOW)
     data = _file_array(path_or_bytes)
     size = int(data.size)
-    own_ctx = ctx is None
-    ctx = ctx or Context(0)
-    try:
+    with _context(ctx) as ctx:
         names, contig_len, header_end = file_header(ctx, data)
         lo, start = 0, None  # window start (a block) and the record to start from (vpos; None: after the header)
         while lo < size:
@@ -253,10 +268,10 @@ def _iter_windows(path_or_bytes, deliver, window=None, halo=4 << 20, ctx=None, r
                     if seg is not None:
                         E = min(E, seg)
                     sh.check_eager(f, E, reads_to_check, want_bits=False)
-                    batch = deliver(sh, f, E, names) if E > f else None
-                    n, x = sh.chain_from(f, E) if E > f else (0, f)
+                    x = sh.chain_from(f, E)[1] if E > f else f
                     if not last and x >= sh.flat_size:
                         raise SparkBamError(SBH_E_NEED_HALO, "the chain leaves the halo")
+                    batch = deliver(sh, f, E, names) if E > f else None
                     nxt = None if last else int(Pos(*sh.pos_of(x)).to_htsjdk())
                     break
                 except SparkBamError as err:
@@ -270,9 +285,6 @@ def _iter_windows(path_or_bytes, deliver, window=None, halo=4 << 20, ctx=None, r
             if last:
                 return
             start, lo = nxt, nxt >> 16
-    finally:
-        if own_ctx:
-            ctx.close()
 
 
 def view(path_or_bytes, header=False, out=None, window=None, ctx=None, reads_to_check=DEFAULT_READS_TO_CHECK):
@@ -282,8 +294,6 @@ def view(path_or_bytes, header=False, out=None, window=None, ctx=None, reads_to_
     header text first, verbatim.  out: a binary file object the text is written to as it is
     produced (returns the byte count); None: returns the text as bytes."""
     data = _file_array(path_or_bytes)
-    own_ctx = ctx is None
-    ctx = ctx or Context(0)
     parts, total = [], 0
 
     def put(b):
@@ -298,14 +308,11 @@ def view(path_or_bytes, header=False, out=None, window=None, ctx=None, reads_to_
         sh.records_scan(f, E)
         return sh.records_sam(names)[0]
 
-    try:
+    with _context(ctx) as ctx:
         if header:
             put(header_text(ctx, data))
         for text in _iter_windows(data, deliver, window, ctx=ctx, reads_to_check=reads_to_check):
             put(text.data)
-    finally:
-        if own_ctx:
-            ctx.close()
     return b"".join(parts) if out is None else total
 
 
@@ -348,8 +355,6 @@ def view_bam(path_or_bytes, out=None, flag_require=0, flag_exclude=0, min_mapq=0
     if sort and intervals is not None:
         raise SparkBamError(SBH_E_ARG, "view_bam: sort needs the whole file in one window, not `intervals`")
     data = _file_array(path_or_bytes)
-    own_ctx = ctx is None
-    ctx = ctx or Context(0)
     from .records import bam_header_set_so, row_ranges
     want = None if rows is None else row_ranges(rows)
     pieces = []
@@ -357,9 +362,9 @@ def view_bam(path_or_bytes, out=None, flag_require=0, flag_exclude=0, min_mapq=0
 
     def gather(sh):
         """The scan on sh -> (compressed whole members, the new tail, rows scanned); nothing is
-        committed here: a window that has to run again with a larger halo calls this again."""
+        committed here: an interval group that has to run again with a larger halo calls this again."""
         base = state["row_base"]
-        f = {"flag_require": flag_require, "flag_exclude": flag_exclude, "min_mapq": min_mapq}
+        f = _flag_filter(flag_require, flag_exclude, min_mapq)
         if want is not None:
             f["rows"] = [(max(a - base, 0), b - base) for a, b in want if b > base]
         sh.records_bam(state["tail"], f, want_bytes=False, order=sort or "scan")
@@ -375,7 +380,7 @@ def view_bam(path_or_bytes, out=None, flag_require=0, flag_exclude=0, min_mapq=0
         state["tail"] = tail
         state["row_base"] += n
 
-    try:
+    with _context(ctx) as ctx:
         state["tail"] = _header_flat(ctx, data)
         if sort:
             state["tail"] = bam_header_set_so(state["tail"], sort)
@@ -405,9 +410,6 @@ def view_bam(path_or_bytes, out=None, flag_require=0, flag_exclude=0, min_mapq=0
         if index:
             from .bai import build_bai
             bai_bytes = build_bai(result, ctx=ctx)
-    finally:
-        if own_ctx:
-            ctx.close()
     if out is None:
         return (result, bai_bytes) if index else result
     if isinstance(out, (str, os.PathLike)):
@@ -448,31 +450,16 @@ def depth(path_or_bytes, region=None, flag_require=0, flag_exclude=0x704, min_ma
     (samtools depth's lines) and `.bedgraph()` (genomecov -bg's)."""
     from .coverage import DEPTH_RUN_DTYPE, DepthResult, region_spans
     data = _file_array(path_or_bytes)
-    own_ctx = ctx is None
-    ctx = ctx or Context(0)
-    acc = None
-    try:
+    with ExitStack() as stack:
+        ctx = stack.enter_context(_context(ctx))
         names, contig_len, _ = file_header(ctx, data)
         try:
             spans = region_spans(region, names, contig_len)
         except ValueError as err:
             raise SparkBamError(SBH_E_ARG, str(err))
-        acc = ctx.depth(spans, len(contig_len), count_del)
-        f = {"flag_require": flag_require, "flag_exclude": flag_exclude, "min_mapq": min_mapq}
+        acc = stack.enter_context(closing(ctx.depth(spans, len(contig_len), count_del)))
+        deliver = _adding(acc, _flag_filter(flag_require, flag_exclude, min_mapq))
         totals = {}
-
-        def deliver(sh, first, E, _names):
-            # the walk looks at the chain's exit only after this returns, and runs the window again
-            # with a larger halo when the chain leaves the resident bytes: look first, add after
-            _, x = sh.chain_from(first, E)
-            blocks = sh.blocks()
-            seg = next((b[3] for b in blocks if b[5] & 1 and b[3] >= first), None)
-            last = seg is not None and E == seg or sh.file_offset + sh.n == sh.file_size and E == sh.flat_size
-            if not last and x >= sh.flat_size:
-                raise SparkBamError(SBH_E_NEED_HALO, "the chain leaves the halo")
-            sh.records_scan(first, E)
-            return [acc.add(sh, f)]
-
         for (got,) in _iter_windows(data, deliver, window, ctx=ctx, reads_to_check=reads_to_check):
             for k, v in got.items():
                 totals[k] = totals.get(k, 0) + v
@@ -480,7 +467,7 @@ def depth(path_or_bytes, region=None, flag_require=0, flag_exclude=0x704, min_ma
         for k in ("n", "n_kept", "n_counted", "n_unplaced", "cov_bases"):
             stats[k] = totals.get(k, 0)
         runs = acc.runs() if stats["n_runs"] else np.zeros(0, dtype=DEPTH_RUN_DTYPE)
-        # the accumulator is closed below: a span's per-base depth is expanded from its runs on request
+        # the accumulator is closed on the way out: a span's per-base depth is expanded from its runs on request
         spans_l = list(spans)
 
         def depths(k, runs=runs, spans=spans_l):
@@ -489,11 +476,6 @@ def depth(path_or_bytes, region=None, flag_require=0, flag_exclude=0x704, min_ma
             return np.repeat(r["depth"], (r["end"] - r["beg"]).astype(np.int64)).astype(np.uint32)
 
         return DepthResult(runs, stats, spans_l, names, depths)
-    finally:
-        if acc is not None:
-            acc.close()
-        if own_ctx:
-            ctx.close()
 
 
 def pileup(path_or_bytes, region=None, flag_require=0, flag_exclude=0x704, min_mapq=0, min_baseq=0, min_depth=1,
@@ -519,60 +501,37 @@ def pileup(path_or_bytes, region=None, flag_require=0, flag_exclude=0x704, min_m
     from .coverage import DEPTH_SPAN_DTYPE, region_spans
     from .pileup import PileupResult, span_passes
     data = _file_array(path_or_bytes)
-    own_ctx = ctx is None
-    ctx = ctx or Context(0)
-    acc = None
-    try:
+    with _context(ctx) as ctx:
         names, contig_len, _ = file_header(ctx, data)
         try:
             spans = region_spans(region, names, contig_len)
         except ValueError as err:
             raise SparkBamError(SBH_E_ARG, str(err).replace("depth:", "pileup:"))
         budget = ctx.pileup_budget() if max_positions is None else int(max_positions)
-        f = {"flag_require": flag_require, "flag_exclude": flag_exclude, "min_mapq": min_mapq}
+        f = _flag_filter(flag_require, flag_exclude, min_mapq)
         stats, ivs, counts, calls = {"totals": [0] * 8}, [], [], []
         for group in span_passes(spans, budget):
-            acc = ctx.pileup(group, len(contig_len), min_baseq)
-            totals = {}
-
-            def deliver(sh, first, E, _names):
-                # as depth's: the chain is looked at before the add, so that a window run again with
-                # a larger halo has added nothing yet
-                _, x = sh.chain_from(first, E)
-                blocks = sh.blocks()
-                seg = next((b[3] for b in blocks if b[5] & 1 and b[3] >= first), None)
-                last = seg is not None and E == seg or sh.file_offset + sh.n == sh.file_size and E == sh.flat_size
-                if not last and x >= sh.flat_size:
-                    raise SparkBamError(SBH_E_NEED_HALO, "the chain leaves the halo")
-                sh.records_scan(first, E)
-                return [acc.add(sh, f)]
-
-            for (got,) in _iter_windows(data, deliver, window, ctx=ctx, reads_to_check=reads_to_check):
-                for k in ("n", "n_kept", "n_counted", "n_unplaced"):
-                    totals[k] = totals.get(k, 0) + got[k]
-            sz = acc.finish(min_depth, call_pct)
-            for k in ("positions", "n_intervals", "nonzero", "n_called", "covered"):
-                stats[k] = stats.get(k, 0) + sz[k]
-            stats["max_depth"] = max(stats.get("max_depth", 0), sz["max_depth"])
-            stats["totals"] = [a + b for a, b in zip(stats["totals"], sz["totals"])]
-            # every pass walks every record: the rows are the file's; a row is counted in the pass
-            # that holds its reference's span
-            for k in ("n", "n_kept", "n_unplaced"):
-                stats[k] = totals.get(k, 0)
-            stats["n_counted"] = stats.get("n_counted", 0) + totals.get("n_counted", 0)
-            ivs.append(acc.intervals() if sz["n_intervals"] else np.zeros(0, dtype=DEPTH_SPAN_DTYPE))
-            for k in range(len(group)):
-                counts.append(acc.counts(k))
-                calls.append(acc.calls(k))
-            acc.close()
-            acc = None
+            with closing(ctx.pileup(group, len(contig_len), min_baseq)) as acc:
+                totals = {}
+                for (got,) in _iter_windows(data, _adding(acc, f), window, ctx=ctx, reads_to_check=reads_to_check):
+                    for k in ("n", "n_kept", "n_counted", "n_unplaced"):
+                        totals[k] = totals.get(k, 0) + got[k]
+                sz = acc.finish(min_depth, call_pct)
+                for k in ("positions", "n_intervals", "nonzero", "n_called", "covered"):
+                    stats[k] = stats.get(k, 0) + sz[k]
+                stats["max_depth"] = max(stats.get("max_depth", 0), sz["max_depth"])
+                stats["totals"] = [a + b for a, b in zip(stats["totals"], sz["totals"])]
+                # every pass walks every record: the rows are the file's; a row is counted in the pass
+                # that holds its reference's span
+                for k in ("n", "n_kept", "n_unplaced"):
+                    stats[k] = totals.get(k, 0)
+                stats["n_counted"] = stats.get("n_counted", 0) + totals.get("n_counted", 0)
+                ivs.append(acc.intervals() if sz["n_intervals"] else np.zeros(0, dtype=DEPTH_SPAN_DTYPE))
+                for k in range(len(group)):
+                    counts.append(acc.counts(k))
+                    calls.append(acc.calls(k))
         return PileupResult(np.concatenate(ivs) if ivs else np.zeros(0, dtype=DEPTH_SPAN_DTYPE), stats, spans, names,
                             counts, calls, contig_len)
-    finally:
-        if acc is not None:
-            acc.close()
-        if own_ctx:
-            ctx.close()
 
 
 def _tally(path_or_bytes, flag_require, flag_exclude, min_mapq, window, ctx, reads_to_check):
@@ -580,37 +539,16 @@ def _tally(path_or_bytes, flag_require, flag_exclude, min_mapq, window, ctx, rea
     and counted into one accumulator in HBM (Context.tally)."""
     from .tally import TallyResult
     data = _file_array(path_or_bytes)
-    own_ctx = ctx is None
-    ctx = ctx or Context(0)
-    acc = None
-    try:
+    with ExitStack() as stack:
+        ctx = stack.enter_context(_context(ctx))
         names, contig_len, _ = file_header(ctx, data)
-        acc = ctx.tally(len(contig_len))
-        f = {"flag_require": flag_require, "flag_exclude": flag_exclude, "min_mapq": min_mapq}
+        acc = stack.enter_context(closing(ctx.tally(len(contig_len))))
+        deliver = _adding(acc, _flag_filter(flag_require, flag_exclude, min_mapq))
         n = n_kept = 0
-
-        def deliver(sh, first, E, _names):
-            # the walk looks at the chain's exit only after this returns, and runs the window again
-            # with a larger halo when the chain leaves the resident bytes: look first, add after
-            # (api.depth's delivery), or a window that runs again would count twice
-            _, x = sh.chain_from(first, E)
-            blocks = sh.blocks()
-            seg = next((b[3] for b in blocks if b[5] & 1 and b[3] >= first), None)
-            last = seg is not None and E == seg or sh.file_offset + sh.n == sh.file_size and E == sh.flat_size
-            if not last and x >= sh.flat_size:
-                raise SparkBamError(SBH_E_NEED_HALO, "the chain leaves the halo")
-            sh.records_scan(first, E)
-            return [acc.add(sh, f)]
-
         for (got,) in _iter_windows(data, deliver, window, ctx=ctx, reads_to_check=reads_to_check):
             n, n_kept = n + got["n"], n_kept + got["n_kept"]
         flag, ref = acc.counts()
         return TallyResult(flag, ref, names, contig_len, n, n_kept)
-    finally:
-        if acc is not None:
-            acc.close()
-        if own_ctx:
-            ctx.close()
 
 
 def flagstat(path_or_bytes, flag_require=0, flag_exclude=0, min_mapq=0, window=None, ctx=None,
@@ -652,36 +590,16 @@ def stats(path_or_bytes, flag_require=0, flag_exclude=0, min_mapq=0, cycles=1024
     `.n_kept`, `.n_counted` and `.text()` (the report under samtools stats' section tags)."""
     from .stats import StatsResult
     data = _file_array(path_or_bytes)
-    own_ctx = ctx is None
-    ctx = ctx or Context(0)
-    acc = None
-    try:
+    with ExitStack() as stack:
+        ctx = stack.enter_context(_context(ctx))
         _, contig_len, _ = file_header(ctx, data)
-        acc = ctx.stats(cycles, max_insert)
-        f = {"flag_require": flag_require, "flag_exclude": flag_exclude, "min_mapq": min_mapq}
+        acc = stack.enter_context(closing(ctx.stats(cycles, max_insert)))
+        deliver = _adding(acc, _flag_filter(flag_require, flag_exclude, min_mapq))
         tot = {"n": 0, "n_kept": 0, "n_counted": 0}
-
-        def deliver(sh, first, E, _names):
-            # look at the chain's exit first, add after (_tally's delivery): a window that runs again
-            # with a larger halo must not count twice
-            _, x = sh.chain_from(first, E)
-            blocks = sh.blocks()
-            seg = next((b[3] for b in blocks if b[5] & 1 and b[3] >= first), None)
-            last = seg is not None and E == seg or sh.file_offset + sh.n == sh.file_size and E == sh.flat_size
-            if not last and x >= sh.flat_size:
-                raise SparkBamError(SBH_E_NEED_HALO, "the chain leaves the halo")
-            sh.records_scan(first, E)
-            return [acc.add(sh, f)]
-
         for (got,) in _iter_windows(data, deliver, window, ctx=ctx, reads_to_check=reads_to_check):
             for k in tot:
                 tot[k] += got[k]
         return StatsResult(acc.counts(), acc.cycles, acc.max_insert, tot["n"], tot["n_kept"], tot["n_counted"])
-    finally:
-        if acc is not None:
-            acc.close()
-        if own_ctx:
-            ctx.close()
 
 
 def fastq(path_or_bytes, out=None, out1=None, out2=None, out0=None, fasta=False, suffix="auto", flag_require=0,
@@ -709,13 +627,12 @@ def fastq(path_or_bytes, out=None, out1=None, out2=None, out0=None, fasta=False,
     split = any(s is not None for s in (out1, out2, out0))
     mode = fastq_mode(fasta, suffix, split)
     data = _file_array(path_or_bytes)
-    own_ctx = ctx is None
-    ctx = ctx or Context(0)
-    f = {"flag_require": flag_require, "flag_exclude": flag_exclude, "min_mapq": min_mapq}
+    f = _flag_filter(flag_require, flag_exclude, min_mapq)
     wanted = [s if s is not None else out for s in (out1, out2, out0)] if split else [out, None, None]
     collect = not split and out is None
     opened, sinks = {}, []  # a sink given twice is opened once: (file object, compression level or None)
-    try:
+    with ExitStack() as stack:  # (the files we open are closed first, then the context if it is ours)
+        ctx = stack.enter_context(_context(ctx))
         for s in wanted:
             if s is None:
                 sinks.append(None)
@@ -725,22 +642,13 @@ def fastq(path_or_bytes, out=None, out1=None, out2=None, out0=None, fasta=False,
                 is_path = isinstance(s, (str, os.PathLike))
                 name = str(key) if is_path else str(getattr(s, "name", ""))
                 lv = level if level is not None else (5 if name.endswith(".gz") else None)
-                opened[key] = (open(s, "wb") if is_path else s, lv, is_path)
+                opened[key] = (stack.enter_context(open(s, "wb")) if is_path else s, lv)
             sinks.append(opened[key])
         parts = []
         totals = {"n": 0, "n_kept": 0, "part_bytes": [0, 0, 0], "part_rows": [0, 0, 0]}
-        plain = collect or any(lv is None for _, lv, _ in opened.values())  # some text comes to the host as it is
+        plain = collect or any(lv is None for _, lv in opened.values())  # some text comes to the host as it is
 
         def deliver(sh, first, E, _names):
-            # the walk looks at the chain's exit only after this returns, and runs the window again
-            # with a larger halo when the chain leaves the resident bytes: look first, render after
-            # (api.depth's delivery), or a window that runs again would be written twice
-            _, x = sh.chain_from(first, E)
-            blocks = sh.blocks()
-            seg = next((b[3] for b in blocks if b[5] & 1 and b[3] >= first), None)
-            last = seg is not None and E == seg or sh.file_offset + sh.n == sh.file_size and E == sh.flat_size
-            if not last and x >= sh.flat_size:
-                raise SparkBamError(SBH_E_NEED_HALO, "the chain leaves the halo")
             sh.records_scan(first, E)
             got = sh.records_fastq(f, mode=mode, def_qual=def_qual, want_text=plain)
             text = got[0] if plain else None
@@ -749,7 +657,7 @@ def fastq(path_or_bytes, out=None, out1=None, out2=None, out0=None, fasta=False,
             for k in range(3):
                 nb = sz["part_bytes"][k]
                 if nb and sinks[k] is not None:
-                    fh, lv, _ = sinks[k]
+                    fh, lv = sinks[k]
                     if lv is None:
                         fh.write(text[at:at + nb].data)
                     else:
@@ -765,17 +673,11 @@ def fastq(path_or_bytes, out=None, out1=None, out2=None, out0=None, fasta=False,
             for k in range(3):
                 totals["part_bytes"][k] += sz["part_bytes"][k]
                 totals["part_rows"][k] += sz["part_rows"][k]
-        for fh, lv, _ in opened.values():
+        for fh, lv in opened.values():
             if lv is not None:
                 fh.write(BGZF_EOF)
         return FastqResult(totals["n"], totals["n_kept"], totals["part_bytes"], totals["part_rows"],
                            b"".join(parts) if collect else None)
-    finally:
-        for fh, _, is_path in opened.values():
-            if is_path:
-                fh.close()
-        if own_ctx:
-            ctx.close()
 
 
 def _header_flat(ctx, data):
@@ -912,13 +814,8 @@ def blocks(path_or_bytes, split_size=None, ranges=None, blocks_path=None, ctx=No
     size = int(data.size)
     idxs = [i for i in range(-(-size // split))
             if ranges is None or any(a < (i + 1) * split and b > i * split and a < b for a, b in ranges)]
-    own_ctx = ctx is None
-    ctx = ctx or Context(0)
-    try:
+    with _context(ctx) as ctx:
         found = ctx.find_blocks(data, [(i * split, min(size, (i + 1) * split)) for i in idxs], bgzf_blocks_to_check)
-    finally:
-        if own_ctx:
-            ctx.close()
     out = [[] for _ in idxs]
     for k, start, cs, us in found:
         if _in_ranges(ranges, start):
@@ -930,18 +827,13 @@ def _all_positions(path_or_bytes, ranges, ctx, reads_to_check, split_size, block
     """Blocks.apply, then every position of those blocks through sbh_check_stream (HBM windows
     of `window` compressed bytes, whatever the file size)."""
     data = _file_array(path_or_bytes)
-    own_ctx = ctx is None
-    ctx = ctx or Context(0)
-    try:
+    with _context(ctx) as ctx:
         parts, _ = blocks(path_or_bytes if not isinstance(path_or_bytes, (bytes, bytearray, memoryview))
                           else data, split_size, ranges, blocks_path, ctx)
         starts = [m.start for p in parts for m in p]
         _, contig_len, _ = file_header(ctx, data)
         return ctx.check_stream(data, contig_len, starts, window=window or STREAM_WINDOW,
                                 reads_to_check=reads_to_check, **kw)
-    finally:
-        if own_ctx:
-            ctx.close()
 
 
 def check_bam(path_or_bytes, records=None, ranges=None, ctx=None, reads_to_check=DEFAULT_READS_TO_CHECK,
@@ -1009,8 +901,7 @@ def htsjdk_rewrite(path_or_bytes, out_path=None, read_ranges=None, ctx=None, lev
     deflated as java.util.zip.Deflater(5, nowrap) = zlib 1.2.11 deflate_slow does (zdeflate.hip),
     so the file, `.blocks` and `.records` equal HTSJDKRewriteTest's fixtures.  `level` picks
     another zlib level (4..9, 0 = stored) or -1 for this library's faster, non-zlib coder."""
-    L = _Loaded(path_or_bytes, ctx)
-    try:
+    with _Loaded(path_or_bytes, ctx) as L:
         sh = L.shard
         if read_ranges is None:
             out, _, _ = L.ctx.bgzf_compress(sh.flat_ptr(), sh.flat_size, level=level)
@@ -1024,8 +915,6 @@ def htsjdk_rewrite(path_or_bytes, out_path=None, read_ranges=None, ctx=None, lev
             keep = idx[np.isin(idx, sel)]
             parts = [flat[:L.header_end]] + [flat[starts[i]:ends[i]] for i in keep]
             out, _, _ = L.ctx.bgzf_compress(np.concatenate(parts), level=level)
-    finally:
-        L.close()
     if out_path is not None:
         with open(out_path, "wb") as f:
             f.write(out.tobytes())

@@ -257,24 +257,20 @@ class Context:
         return Stats(self, cycles, max_insert)
 
 
-class Stats:
-    """sbh_stats: scans of any number of this context's shards counted into one set of tables
-    (`add`); `counts` may be read between adds."""
+class _Owned:
+    """A C-ABI handle that lives in a context: `_own` registers it there, so that it is closed with
+    the context, before it; `close` destroys it (the library's `_destroy`) only while the context
+    lives -- the context's own destroy has freed it otherwise."""
+    _destroy = None
 
-    def __init__(self, ctx, cycles=1024, max_insert=8000):
-        from .stats import check_params
-        self.ctx = ctx
-        self.cycles, self.max_insert = check_params(cycles, max_insert)
-        h = C.c_void_p()
-        p = SbhStatsParams(self.cycles, self.max_insert)
-        _check(ctx.h, lib().sbh_stats_create(ctx.h, C.byref(p), C.byref(h)))
-        self.h = h
-        ctx._shards.add(self)  # (closed with the context, before it)
+    def _own(self, ctx, h):
+        self.ctx, self.h = ctx, h
+        ctx._shards.add(self)
 
     def close(self):
         if self.h:
             if self.ctx.h:
-                lib().sbh_stats_destroy(self.h)
+                getattr(lib(), self._destroy)(self.h)
             self.h = None
 
     def __del__(self):
@@ -283,17 +279,48 @@ class Stats:
         except Exception:
             pass
 
+
+class _Accumulator(_Owned):
+    """What Stats, Tally, Depth and Pileup share: the bodies of `add` and `reset` (the methods stay
+    with the classes, with their descriptions).  A subclass names the library's functions
+    (_destroy, _add, _reset) and the add's result struct (_AddResult), whose fields are the dict
+    that add returns unless _added says otherwise."""
+    _add = _reset = _AddResult = None
+
+    def _added(self, r):
+        return {k: int(getattr(r, k)) for k, _ in r._fields_}
+
+    def _add_rows(self, shard, filter):
+        f, keep = record_filter(filter)
+        r = self._AddResult()
+        _check(self.ctx.h, getattr(lib(), self._add)(shard.h, self.h, C.byref(f) if f is not None else None,
+                                                     C.byref(r)))
+        del keep
+        return self._added(r)
+
+    def _zero(self):
+        _check(self.ctx.h, getattr(lib(), self._reset)(self.h))
+
+
+class Stats(_Accumulator):
+    """sbh_stats: scans of any number of this context's shards counted into one set of tables
+    (`add`); `counts` may be read between adds."""
+    _destroy, _add, _reset, _AddResult = "sbh_stats_destroy", "sbh_records_stats_add", "sbh_stats_reset", SbhStatsAddResult
+
+    def __init__(self, ctx, cycles=1024, max_insert=8000):
+        from .stats import check_params
+        self.cycles, self.max_insert = check_params(cycles, max_insert)
+        h = C.c_void_p()
+        p = SbhStatsParams(self.cycles, self.max_insert)
+        _check(ctx.h, lib().sbh_stats_create(ctx.h, C.byref(p), C.byref(h)))
+        self._own(ctx, h)
+
     def add(self, shard, filter=None):
         """The rows of the last scan on `shard` that `filter` keeps (records.record_filter's dict,
         None: all), counted (sbh_records_stats_add).  Returns {"n": rows, "n_kept": kept rows,
         "n_counted": the kept rows that are neither secondary nor supplementary}.  A failed add leaves
         the accumulator as it was."""
-        f, keep = record_filter(filter)
-        r = SbhStatsAddResult()
-        _check(self.ctx.h, lib().sbh_records_stats_add(shard.h, self.h, C.byref(f) if f is not None else None,
-                                                       C.byref(r)))
-        del keep
-        return {"n": int(r.n), "n_kept": int(r.n_kept), "n_counted": int(r.n_counted)}
+        return self._add_rows(shard, filter)
 
     def counts(self):
         """The tables of every add so far (sbh_stats_fetch) as a dict of uint64 arrays: sn, read_len,
@@ -305,43 +332,25 @@ class Stats:
 
     def reset(self):
         """Zero the totals (sbh_stats_reset)."""
-        _check(self.ctx.h, lib().sbh_stats_reset(self.h))
+        self._zero()
 
 
-class Tally:
+class Tally(_Accumulator):
     """sbh_tally: scans of any number of this context's shards counted into one set of totals
     (`add`); `counts` may be read between adds."""
+    _destroy, _add, _reset, _AddResult = "sbh_tally_destroy", "sbh_records_tally_add", "sbh_tally_reset", SbhTallyAddResult
 
     def __init__(self, ctx, n_ref):
-        self.ctx = ctx
         self.n_ref = int(n_ref)
         h = C.c_void_p()
         _check(ctx.h, lib().sbh_tally_create(ctx.h, self.n_ref, C.byref(h)))
-        self.h = h
-        ctx._shards.add(self)  # (closed with the context, before it)
-
-    def close(self):
-        if self.h:
-            if self.ctx.h:
-                lib().sbh_tally_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._own(ctx, h)
 
     def add(self, shard, filter=None):
         """The rows of the last scan on `shard` that `filter` keeps (records.record_filter's dict,
         None: all), counted (sbh_records_tally_add).  Returns {"n": rows, "n_kept": kept rows}.  A
         failed add leaves the accumulator as it was."""
-        f, keep = record_filter(filter)
-        r = SbhTallyAddResult()
-        _check(self.ctx.h, lib().sbh_records_tally_add(shard.h, self.h, C.byref(f) if f is not None else None,
-                                                       C.byref(r)))
-        del keep
-        return {"n": int(r.n), "n_kept": int(r.n_kept)}
+        return self._add_rows(shard, filter)
 
     def counts(self):
         """(flag uint64[16, 2], ref uint64[n_ref + 1, 2]) of every add so far (sbh_tally_fetch)."""
@@ -351,46 +360,28 @@ class Tally:
 
     def reset(self):
         """Zero the totals (sbh_tally_reset)."""
-        _check(self.ctx.h, lib().sbh_tally_reset(self.h))
+        self._zero()
 
 
-class Depth:
+class Depth(_Accumulator):
     """sbh_depth: scans of any number of this context's shards added into one array of slots
     (`add`), then turned into per-base depth and runs of equal depth on the GPU (`finish`)."""
+    _destroy, _add, _reset, _AddResult = "sbh_depth_destroy", "sbh_records_depth_add", "sbh_depth_reset", SbhDepthAddResult
 
     def __init__(self, ctx, spans, n_ref, count_del=False):
-        self.ctx = ctx
         self.spans = [(int(r), int(b), int(e)) for r, b, e in spans]
         sp = span_array(self.spans)
         h = C.c_void_p()
         _check(ctx.h, lib().sbh_depth_create(ctx.h, _ptr(sp) if sp.size else None, int(sp.size), int(n_ref),
                                              DEPTH_DEL if count_del else 0, C.byref(h)))
-        self.h = h
         self.sizes = None
-        ctx._shards.add(self)  # (closed with the context, before it)
-
-    def close(self):
-        if self.h:
-            if self.ctx.h:
-                lib().sbh_depth_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._own(ctx, h)
 
     def add(self, shard, filter=None):
         """The rows of the last scan on `shard` that `filter` keeps (records.record_filter's dict,
         None: all), added (sbh_records_depth_add).  Returns the add's counts as a dict: n, n_kept,
         n_counted, n_unplaced, cov_bases.  A failed add leaves the accumulator as it was."""
-        f, keep = record_filter(filter)
-        r = SbhDepthAddResult()
-        _check(self.ctx.h, lib().sbh_records_depth_add(shard.h, self.h, C.byref(f) if f is not None else None,
-                                                       C.byref(r)))
-        del keep
-        return {k: int(getattr(r, k)) for k, _ in SbhDepthAddResult._fields_}
+        return self._add_rows(shard, filter)
 
     def finish(self):
         """Slots -> depth, runs and stats on the GPU (sbh_depth_finish): a dict slots, n_runs,
@@ -424,48 +415,33 @@ class Depth:
 
     def reset(self):
         """Zero the slots and open the accumulator for adds again (sbh_depth_reset)."""
-        _check(self.ctx.h, lib().sbh_depth_reset(self.h))
+        self._zero()
         self.sizes = None
 
 
-class Pileup:
+class Pileup(_Accumulator):
     """sbh_pileup: scans of any number of this context's shards added into one table of per-base
     allele counts (`add`), then turned into call bytes and intervals on the GPU (`finish`)."""
+    _destroy, _add, _reset, _AddResult = "sbh_pileup_destroy", "sbh_records_pileup_add", "sbh_pileup_reset", SbhPileupAddResult
 
     def __init__(self, ctx, spans, n_ref, min_baseq=0):
-        self.ctx = ctx
         self.spans = [(int(r), int(b), int(e)) for r, b, e in spans]
         sp = span_array(self.spans)
         h = C.c_void_p()
         _check(ctx.h, lib().sbh_pileup_create(ctx.h, _ptr(sp) if sp.size else None, int(sp.size), int(n_ref),
                                               int(min_baseq), C.byref(h)))
-        self.h = h
         self.sizes = None
-        ctx._shards.add(self)  # (closed with the context, before it)
-
-    def close(self):
-        if self.h:
-            if self.ctx.h:
-                lib().sbh_pileup_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._own(ctx, h)
 
     def add(self, shard, filter=None):
         """The rows of the last scan on `shard` that `filter` keeps (records.record_filter's dict,
         None: all), added (sbh_records_pileup_add).  Returns the add's counts as a dict: n, n_kept,
         n_counted, n_unplaced, totals (what went into each channel).  A failed add leaves the
         accumulator as it was."""
+        return self._add_rows(shard, filter)
+
+    def _added(self, r):
         from .pileup import add_dict
-        f, keep = record_filter(filter)
-        r = SbhPileupAddResult()
-        _check(self.ctx.h, lib().sbh_records_pileup_add(shard.h, self.h, C.byref(f) if f is not None else None,
-                                                        C.byref(r)))
-        del keep
         return add_dict(r)
 
     def finish(self, min_depth=1, call_pct=75):
@@ -513,15 +489,15 @@ class Pileup:
 
     def reset(self):
         """Zero the counts and open the accumulator for adds again (sbh_pileup_reset)."""
-        _check(self.ctx.h, lib().sbh_pileup_reset(self.h))
+        self._zero()
         self.sizes = None
 
 
-class Shard:
+class Shard(_Owned):
     """Compressed bytes [file_offset, file_offset + n) of a BGZF file, resident in HBM."""
+    _destroy = "sbh_shard_destroy"
 
     def __init__(self, ctx, comp, file_offset=0, file_size=None, on_device=False, nbytes=None):
-        self.ctx = ctx
         if on_device:
             ptr, n = int(comp), int(nbytes)
             src = C.c_void_p(ptr)
@@ -537,26 +513,13 @@ class Shard:
         h = C.c_void_p()
         _check(ctx.h, lib().sbh_shard_create(ctx.h, src, n, self.file_offset, self.file_size,
                                              1 if on_device else 0, C.byref(h)))
-        self.h = h
+        self._own(ctx, h)
         self._keep = None
-        ctx._shards.add(self)
         self.n_blocks = 0
         self.flat_size = 0
 
     def _c(self, rc):
         _check(self.ctx.h, rc)
-
-    def close(self):
-        if self.h:
-            if self.ctx.h:
-                lib().sbh_shard_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def load(self, comp, file_offset, on_device=False, nbytes=None):
         """Replace the resident bytes with file bytes [file_offset, file_offset + n) of the same

@@ -2,8 +2,8 @@
 sbh_depth_finish: k_depth_tile_sums, k_depth_apply, k_depth_runs) against the numpy restatement of
 depth_corpus.py: the add's counts, the stats, the runs and the fetched depth on every corpus; a
 failed add leaving the accumulator as it was; two shards into one accumulator; the state rules; the
-bundled files with literal expected numbers; api.depth over the whole genome and in several windows.
-Every comparison is exact equality."""
+bundled files with literal expected numbers; api.depth over the whole genome, in several windows and
+with a window that runs twice.  Every comparison is exact equality."""
 import ctypes as C
 import functools
 
@@ -15,6 +15,7 @@ from pkg import sb
 import depth_corpus as dc
 import record_corpus as rc
 from test_record_conformance_gpu import call
+from walk_spy import walked
 
 pytestmark = pytest.mark.gpu
 
@@ -421,3 +422,15 @@ def test_api_depth_in_windows_and_renderers(ctx):
     with pytest.raises(sb.SparkBamError) as e:
         sb.depth(golden_bam("2.bam"), region="no_such_reference", ctx=ctx)
     assert e.value.code == SBH_E_ARG
+
+
+def test_api_depth_halo_rerun_adds_once(ctx):
+    """A first halo of 16 bytes: windows run again (x 4 each time) until the block behind the window
+    and the chain's exit are resident.  A window that runs twice is added once: the one-window answer."""
+    _, _, _, names, _, _ = fixture("2.bam")
+    _, _, (lo, hi) = fixture_want("2.bam")
+    region = "%s:%d-%d" % (names[0], lo + 1, hi)
+    one = call(sb.depth, golden_bam("2.bam"), region=region, ctx=ctx)
+    rerun, w_rerun = walked(sb.depth, golden_bam("2.bam"), ctx, halo=16, window=150000, region=region)
+    assert len(w_rerun) > len(set(o for o, _ in w_rerun)) >= 3
+    assert np.array_equal(rerun.runs, one.runs) and rerun.stats == one.stats

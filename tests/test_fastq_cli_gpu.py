@@ -11,6 +11,7 @@ import pytest
 from conftest import ROOT, golden_bam
 from pkg import sb
 import fastq_corpus as fc
+import walk_spy
 from test_record_conformance_gpu import call
 from test_tally_cpu import bundled
 
@@ -35,24 +36,9 @@ def run(*args):
 
 
 def walked(path, ctx, halo=None, **kw):
-    """sb.fastq(path, ctx=ctx, **kw), and the walk it made: (file offset, resident bytes) of every
-    window attempt -- a window that ran again with a larger halo shows as its offset twice
-    (test_tally_gpu.py's spy; halo: the walk's first halo)."""
-    attempts = []
-    index, walk = sb.device.Shard.index, sb.api._iter_windows
-
-    def spy(self, *a, **k):
-        attempts.append((self.file_offset, self.n))
-        return index(self, *a, **k)
-
-    sb.device.Shard.index = spy
-    if halo is not None:
-        sb.api._iter_windows = lambda data, deliver, window=None, **k: walk(data, deliver, window, halo=halo, **k)
-    try:
-        r = call(sb.fastq, path, ctx=ctx, **kw)
-    finally:
-        sb.device.Shard.index, sb.api._iter_windows = index, walk
-    return r, attempts[1:]  # (the first shard reads the header)
+    """sb.fastq(path, ctx=ctx, **kw) and the walk it made (walk_spy.walked; fastq reads no header of
+    its own, so one shard comes before the first window)."""
+    return walk_spy.walked(sb.fastq, path, ctx, halo=halo, header_shards=1, **kw)
 
 
 def want_of(name, **kw):

@@ -3,7 +3,8 @@ sbh_pileup_finish: k_pile_calls, k_pile_fold, k_pile_intervals) against the nump
 pileup_corpus.py: the add's counts, the table, the calls, the intervals and the stats on every
 corpus; the hand-worked table; the existing depth code as an independent check on every corpus and
 bundled file; a failed add leaving the table as it was; two shards into one accumulator; the state
-rules; the bundled files with literal expected numbers; api.pileup in several windows and passes.
+rules; the bundled files with literal expected numbers; api.pileup in several windows and passes, and with a
+window that runs twice.
 Every comparison is exact equality."""
 import ctypes as C
 import functools
@@ -16,6 +17,7 @@ from pkg import sb
 import pileup_corpus as pc
 import record_corpus as rc
 from test_depth_gpu import call, fixture, scanned
+from walk_spy import walked
 
 pytestmark = pytest.mark.gpu
 
@@ -373,6 +375,20 @@ def test_api_pileup_in_windows_and_passes(ctx):
     with pytest.raises(ValueError) as e:
         sb.pileup(golden_bam("2.bam"), region=region, ctx=ctx, max_positions=hi - lo - 1)
     assert "(ref 0, %d, %d)" % (lo, hi) in str(e.value)
+
+
+def test_api_pileup_halo_rerun_adds_once(ctx):
+    """A first halo of 16 bytes: windows run again (x 4 each time) until the block behind the window
+    and the chain's exit are resident.  A window that runs twice is added once: the one-window answer."""
+    _, _, _, names, _, _ = fixture("2.bam")
+    _, (lo, hi) = fixture_want("2.bam")
+    region = "%s:%d-%d" % (names[0], lo + 1, hi)
+    one = call(sb.pileup, golden_bam("2.bam"), region=region, ctx=ctx)
+    rerun, w_rerun = walked(sb.pileup, golden_bam("2.bam"), ctx, halo=16, window=150000, region=region)
+    assert len(w_rerun) > len(set(o for o, _ in w_rerun)) >= 3
+    assert np.array_equal(rerun.intervals, one.intervals) and rerun.stats == one.stats
+    assert np.array_equal(rerun.counts(names[0]), one.counts(names[0]))
+    assert np.array_equal(rerun.calls(names[0]), one.calls(names[0]))
 
 
 def test_api_pileup_three_passes_are_one(ctx):

@@ -15,7 +15,7 @@ import stats_corpus as sc
 from test_depth_gpu import scanned
 from test_record_conformance_gpu import call
 from test_tally_cpu import bundled
-from test_tally_gpu import walked
+from walk_spy import walked
 
 pytestmark = pytest.mark.gpu
 

@@ -16,6 +16,7 @@ import tally_corpus as tc
 from test_depth_gpu import scanned
 from test_record_conformance_gpu import call
 from test_tally_cpu import BUNDLED, FLAGSTAT_1BAM, FLAGSTAT_2BAM, bundled, bundled_flag, bundled_ref
+from walk_spy import walked
 
 pytestmark = pytest.mark.gpu
 
@@ -261,27 +262,6 @@ def test_per_reference_counts_are_the_bai_s(ctx, name):
     ours = [tuple(int(x) for x in row) for row in r.ref[:-1]]
     assert ours == committed == built and ours[0] == BUNDLED[name][1]
     assert no_coor == no_coor_built == 0 and r.ref[-1].tolist() == [0, 0]
-
-
-def walked(fn, path, ctx, halo=None, **kw):
-    """fn(path, ctx=ctx, **kw), and the walk it made: (file offset, resident bytes) of every window
-    attempt -- a window that ran again with a larger halo shows as its offset twice.  halo: the walk's
-    first halo (the entries take none of their own; default 4 MiB, more than these files hold)."""
-    attempts = []
-    index, walk = sb.device.Shard.index, sb.api._iter_windows
-
-    def spy(self, *a, **k):
-        attempts.append((self.file_offset, self.n))
-        return index(self, *a, **k)
-
-    sb.device.Shard.index = spy
-    if halo is not None:
-        sb.api._iter_windows = lambda data, deliver, window=None, **k: walk(data, deliver, window, halo=halo, **k)
-    try:
-        r = call(fn, path, ctx=ctx, **kw)
-    finally:
-        sb.device.Shard.index, sb.api._iter_windows = index, walk
-    return r, attempts[2:]  # (the first two shards read the header: the entry's own and the walk's)
 
 
 def test_api_in_one_window_and_in_several(ctx):
