@@ -40,12 +40,6 @@ static int need_checkable(sbh_shard *sh, uint64_t begin, uint64_t end, int32_t r
 
 }  // extern "C"
 
-// SBH_XQ=0 turns the long-record queue off (every exact check inline; for A/B timing)
-uint64_t sbh::xq_cap() {
-  const char *e = std::getenv("SBH_XQ");
-  return e && e[0] == '0' ? 0 : XQ_CAP_MAX;
-}
-
 int sbh::eager_range(sbh_shard *sh, uint64_t begin, uint64_t end, int32_t rtc, uint64_t *n_true) {
   sbh_ctx *ctx = sh->ctx;
   hipStream_t st = sh->st;
@@ -59,10 +53,9 @@ int sbh::eager_range(sbh_shard *sh, uint64_t begin, uint64_t end, int32_t rtc, u
   mark(sh, 4);
   HIPCHK(ctx, launch_eager(sh->U.p, sh->utotal + sh->pad, begin, end, sh->d_seg.p, (uint32_t)sh->seg_end.size(),
                            sh->open_last ? 1 : 0, sh->ctg.p, sh->nctg, rtc, sh->bits.p, c, st, ~0ull, nullptr, 0,
-                           sh->xq.p, xq_cap(),
-                           sh->sieve_nref1 && sh->sieve_nref1 == (uint32_t)sh->nctg + 1 ? sh->sieve.p : nullptr));
+                           sh->xq.p, XQ_CAP_MAX));
   HIPCHK(ctx, launch_eager_xq(sh->U.p, begin, sh->d_seg.p, (uint32_t)sh->seg_end.size(), sh->open_last ? 1 : 0,
-                              sh->ctg.p, sh->nctg, rtc, sh->bits.p, c, sh->xq.p, xq_cap(), st));
+                              sh->ctg.p, sh->nctg, rtc, sh->bits.p, c, sh->xq.p, XQ_CAP_MAX, st));
   mark(sh, 5);
   // (the true count and the two need-halo words)
   HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::EAGER_TRUE, c + ctr::EAGER_TRUE, (ctr::EAGER_HALO_FIRST + 1) * 8,
@@ -337,7 +330,7 @@ int sbh::count_records_impl(sbh_shard *sh, uint64_t first, uint64_t E, uint64_t 
       uint32_t *code = reinterpret_cast<uint32_t *>(sh->h_ctr + ctr::H_MARK_CODE);
       HIPCHK(ctx, launch_chain_mark(sh->U.p, sh->bits.p, sh->bits_begin, first, E, total, sh->cm_pos.p,
                                     sh->cm_wpre.p, n, sh->cm_j.p, sh->cm_j2.p, sh->cm_j0.p, sh->cm_mark.p,
-                                    c + ctr::MARK_EXIT, code, st));
+                                    c + ctr::MARK_EXIT, code, env_flag("SBH_CM_DOUBLING"), st));
       HIPCHK(ctx, hipMemsetAsync(sh->cm_mark.p + n, 0, 8, st));
       HIPCHK(ctx, scan_exclusive_u64(sh->cm_mark.p, sh->cm_mpre.p, n + 1, sh->tmp.p, st));
       HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::H_MARK_COUNT, sh->cm_mpre.p + n, 8, hipMemcpyDeviceToHost, st));
@@ -441,10 +434,7 @@ int sbh_split_starts(sbh_shard *sh, const uint64_t *starts, const uint64_t *ends
 }  // extern "C"
 
 // SBH_SPLIT_CC=0: split counts by a popcount of each split's whole bitmap range (A/B)
-static bool split_cc_on() {
-  const char *e = std::getenv("SBH_SPLIT_CC");
-  return !(e && e[0] == '0');
-}
+static bool split_cc_on() { return env_flag("SBH_SPLIT_CC", true); }
 
 int sbh::split_starts_impl(sbh_shard *sh, const uint64_t *starts, const uint64_t *ends, uint64_t n, int32_t k,
                            int32_t rtc, int32_t mrs, uint64_t *first_vpos, uint64_t *counts, int32_t *status,
@@ -623,7 +613,7 @@ int sbh::split_starts_impl(sbh_shard *sh, const uint64_t *starts, const uint64_t
     }
     ++nh;
     if (hostf) hostf[i] = 1;
-    if (std::getenv("SBH_SPLIT_DEBUG"))
+    if (env_flag("SBH_SPLIT_DEBUG"))
       fprintf(stderr, "[sbh] split %llu [%llu, %llu) host path: shard [%llu, +%llu) first %llu E %llu dense %d marked %d code %#x\n",
               (unsigned long long)i, (unsigned long long)starts[i], (unsigned long long)ends[i],
               (unsigned long long)sh->file_off, (unsigned long long)sh->n, (unsigned long long)first[i],

@@ -356,7 +356,6 @@ struct EagerOut {
   unsigned long long *xq_n;
   uint64_t xq_cap;                // 0: every exact check runs inline
   unsigned long long *true_spread;  // k_eager: per-wave true counts, folded into n_true by k_fold_true
-  const uint32_t *sieve = nullptr;  // k_lz's first-filter bitmap, bit p = flat position p (nullptr: sweep here)
 };
 
 // k_eager's true count goes to TRUE_SLOTS counters TRUE_STRIDE u64 apart (one atomic per
@@ -710,43 +709,26 @@ __global__ __launch_bounds__(T) void k_eager(const uint8_t *__restrict__ U, uint
                         upto(4 * (int32_t)EG - 32 * (int32_t)w);
     return (m | ~upto((int32_t)fast_end - i0)) & in;
   };
-  if (o.sieve) {
-    // k_lz evaluated this filter (and the next refID / pos signs) on the bytes in its LDS ring:
-    // the thread's bits are the sieve's bits [s0 + 4 g0, + 4 EG), masked to the window, plus every
-    // position from fast_end on (near a segment end, decided below)
-    const uint64_t A = s0 + 4ull * g0;
-    const uint32_t *sw = o.sieve + (A >> 5);
-    const uint32_t sft = (uint32_t)(A & 31);
-    uint32_t lo_w = sw[0];
+  // each word's 32 refID tests shifted into it last position first (m = 2 m + test: one
+  // add-with-carry per position, no per-position range logic); the word's range after
+  static_assert(EMW * 8 >= EG, "the words cover the thread's groups");
 #pragma unroll
-    for (uint32_t w = 0; w < EMW; ++w) {
-      const uint32_t hi_w = sw[w + 1];
-      const uint32_t m = sft ? (lo_w >> sft) | (hi_w << (32 - sft)) : lo_w;
-      lo_w = hi_w;
-      msk[w] = word_keep(w, m);
-    }
-  } else {
-    // each word's 32 refID tests shifted into it last position first (m = 2 m + test: one
-    // add-with-carry per position, no per-position range logic); the word's range after
-    static_assert(EMW * 8 >= EG, "the words cover the thread's groups");
+  for (uint32_t w = 0; w < EMW; ++w) {
+    constexpr uint32_t GW = 8;  // groups (of 4 positions) per word
+    uint32_t d[GW + 1];         // staged dwords g0 + 8 w + 1 .. + 9: bytes 4..7 of every position's record
 #pragma unroll
-    for (uint32_t w = 0; w < EMW; ++w) {
-      constexpr uint32_t GW = 8;  // groups (of 4 positions) per word
-      uint32_t d[GW + 1];         // staged dwords g0 + 8 w + 1 .. + 9: bytes 4..7 of every position's record
+    for (uint32_t j = 0; j <= GW; ++j) d[j] = 8 * w + j <= EG ? lds32[g0 + 8 * w + j + 1] : 0u;
+    uint32_t m = 0;
 #pragma unroll
-      for (uint32_t j = 0; j <= GW; ++j) d[j] = 8 * w + j <= EG ? lds32[g0 + 8 * w + j + 1] : 0u;
-      uint32_t m = 0;
+    for (int32_t j = GW - 1; j >= 0; --j) {
+      if (8 * w + (uint32_t)j >= EG) continue;
 #pragma unroll
-      for (int32_t j = GW - 1; j >= 0; --j) {
-        if (8 * w + (uint32_t)j >= EG) continue;
-#pragma unroll
-        for (int32_t k = 3; k >= 0; --k) {
-          const uint32_t ref = __builtin_amdgcn_alignbyte(d[j + 1], d[j], (uint32_t)k);
-          m = m + m + (ref + 1u < nref1 ? 1u : 0u);
-        }
+      for (int32_t k = 3; k >= 0; --k) {
+        const uint32_t ref = __builtin_amdgcn_alignbyte(d[j + 1], d[j], (uint32_t)k);
+        m = m + m + (ref + 1u < nref1 ? 1u : 0u);
       }
-      msk[w] = word_keep(w, m);
     }
+    msk[w] = word_keep(w, m);
   }
 #ifdef SBH_EPROBE
   const uint64_t c1x = __builtin_readcyclecounter();
@@ -1968,15 +1950,14 @@ static inline uint32_t ngrid(uint64_t n, uint32_t t) { return (uint32_t)((n + t 
 hipError_t launch_eager(const uint8_t *U, uint64_t u_pad, uint64_t begin, uint64_t end, const uint64_t *seg_end,
                         uint32_t nseg, uint32_t open_last, const int32_t *ctg, int32_t nctg, int32_t rtc,
                         uint32_t *bits, unsigned long long *counters, hipStream_t st, uint64_t front,
-                        uint64_t *defer_pos, uint64_t defer_cap, uint64_t *xq_pos, uint64_t xq_cap,
-                        const uint32_t *sieve) {
+                        uint64_t *defer_pos, uint64_t defer_cap, uint64_t *xq_pos, uint64_t xq_cap) {
   if (end <= begin) return hipSuccess;
   Segs sg{seg_end, nseg, open_last};
   Ctg c{ctg, nctg};
   EagerOut o{bits, counters + ctr::EAGER_TRUE, counters + ctr::EAGER_HALO_N, counters + ctr::EAGER_HALO_FIRST, front,
              defer_pos, counters + ctr::EAGER_DEFER_N, defer_cap,
              xq_pos, counters + ctr::EAGER_XQ_N, xq_cap,
-             counters + TRUE_SPREAD_OFF, sieve};
+             counters + TRUE_SPREAD_OFF};
   hipLaunchKernelGGL(k_eager, dim3(ngrid(end - begin, ETILE)), dim3(T), 0, st, U, u_pad, begin, end, sg, c,
                      rtc, o);
   hipLaunchKernelGGL(k_fold_true, dim3(1), dim3(WAVE), 0, st, counters + TRUE_SPREAD_OFF,
@@ -2071,14 +2052,14 @@ hipError_t launch_chain_walk(const uint8_t *U, uint64_t first, uint64_t E, uint6
 
 // pos, wpre: from launch_rec_positions_bits over [from, E); J, J2, J0: n + 1 u32; mark: n + 1 u64.
 // *final_code = the chain's terminal code after doubling (n: ended validly, n + 1: broken).
+// doubling: mark by pointer doubling instead of peeling (SBH_CM_DOUBLING=1: A/B, tests).
 hipError_t launch_chain_mark(const uint8_t *U, const uint32_t *bits, uint64_t begin, uint64_t from, uint64_t E,
                              uint64_t total, const uint64_t *pos, const uint64_t *wpre, uint64_t n, uint32_t *J,
                              uint32_t *J2, uint32_t *J0, uint64_t *mark, unsigned long long *exit_pos,
-                             uint32_t *final_code, hipStream_t st) {
+                             uint32_t *final_code, bool doubling, hipStream_t st) {
   if (!n) return hipSuccess;
   const uint32_t g = ngrid(n, 256);
-  const char *dbl = std::getenv("SBH_CM_DOUBLING");  // 1: the pointer-doubling marking (A/B, tests)
-  if (dbl && dbl[0] == '1') {
+  if (doubling) {
     hipLaunchKernelGGL(k_cm_succ, dim3(g), dim3(256), 0, st, U, bits, begin, from, E, total, pos, wpre, n, J, J0,
                        mark, nullptr);
     uint32_t *a = J, *b = J2;

@@ -2620,10 +2620,9 @@ __device__ __forceinline__ void chase8_asm(uint32_t (&c)[8], uint32_t pend, uint
 // pos in range at each of a granule's 16 positions -- as a bitmap in `sieve`, a word per granule
 // once the ring had the granule's 48 bytes: k_eager -0.55 ms, k_lz +0.95 ms on
 // config B -- the filter's ~180 vector instructions per 16-byte granule are issue time k_lz does
-// not have spare.  The `sieve` / `nref1` arguments stay in the kernel's signature, unused.)
+// not have spare.)
 __global__ __launch_bounds__(LZ_THREADS, SBH_LZ_WAVES_PER_EU) void k_lz(const uint8_t *__restrict__ comp, DevBlocks bl, uint64_t nblocks,
-                                                    const uint32_t *__restrict__ tok, uint8_t *__restrict__ U,
-                                                    uint32_t *__restrict__ sieve, uint32_t nref1) {
+                                                    const uint32_t *__restrict__ tok, uint8_t *__restrict__ U) {
   __shared__ LzSmem sm;
   uint32_t *wsum = sm.pp.wsum;
   const uint64_t b = blockIdx.x;
@@ -3083,12 +3082,10 @@ hipError_t launch_huff(const uint8_t *comp, DevBlocks blocks, uint64_t nblocks, 
 }
 
 hipError_t launch_lz(const uint8_t *comp, DevBlocks blocks, uint64_t nblocks, const uint32_t *tok_buf,
-                     uint64_t tok_base, uint8_t *U, hipStream_t stream, uint32_t *sieve, uint32_t nref1) {
+                     uint64_t tok_base, uint8_t *U, hipStream_t stream) {
   if (nblocks == 0) return hipSuccess;
   const uint32_t *tok = reinterpret_cast<const uint32_t *>(reinterpret_cast<uintptr_t>(tok_buf) - tok_base * 4);
-  sieve = nullptr;  // (k_lz writes no sieve: see the note above k_lz)
-  hipLaunchKernelGGL(k_lz, dim3((uint32_t)nblocks), dim3(LZ_THREADS), 0, stream, comp, blocks, nblocks, tok, U, sieve,
-                     nref1);
+  hipLaunchKernelGGL(k_lz, dim3((uint32_t)nblocks), dim3(LZ_THREADS), 0, stream, comp, blocks, nblocks, tok, U);
   return hipGetLastError();
 }
 

@@ -87,7 +87,6 @@ void sbh::resident_changed(sbh_shard *sh, uint64_t file_off, uint64_t n) {
   sh->file_off = file_off;
   sh->n = n;
   sh->at_eof = file_off + n == sh->file_size;
-  sh->sieve_nref1 = 0;
   sh->indexed = sh->inflated = sh->bits_valid = sh->chain_ok = sh->cm_valid = false;
   sh->rec.valid = false;
   sh->bai.valid = false;
@@ -118,7 +117,7 @@ int sbh_ctx_create(int device, sbh_ctx **out) {
   // SBH_SCHED=spin|yield|block: how a host thread waits in hipStreamSynchronize (the path's
   // host round trips -- index sizes, block table, statuses -- each leave the GPU idle until the
   // host thread wakes); unset: the runtime's default
-  if (const char *e = std::getenv("SBH_SCHED")) {
+  if (const char *e = env_str("SBH_SCHED")) {
     const unsigned f = !std::strcmp(e, "spin")    ? hipDeviceScheduleSpin
                        : !std::strcmp(e, "yield") ? hipDeviceScheduleYield
                        : !std::strcmp(e, "block") ? hipDeviceScheduleBlockingSync
@@ -252,6 +251,18 @@ int sbh_shard_destroy(sbh_shard *sh) {
   return SBH_OK;
 }
 
+// A copy stream at another priority than the compute streams: its hardware queue then comes from
+// another pool, so no compute stream shares it (a copy in flight on a shared queue held the next
+// window's kernels behind it: e2e 130 -> 84 GB/s depending on stream creation order).  A device
+// with a single priority gets a plain stream.
+static hipError_t copy_stream_create(hipStream_t *cs) {
+  int least = 0, greatest = 0;
+  const hipError_t e = hipDeviceGetStreamPriorityRange(&least, &greatest);
+  if (e != hipSuccess) return e;
+  return greatest != least ? hipStreamCreateWithPriority(cs, hipStreamNonBlocking, greatest)
+                           : hipStreamCreateWithFlags(cs, hipStreamNonBlocking);
+}
+
 int sbh_shard_load(sbh_shard *sh, const void *src, uint64_t n, uint64_t file_offset, int comp_on_device) {
   if (!sh || (!src && n) || file_offset + n > sh->file_size) return SBH_E_ARG;
   sbh_ctx *ctx = sh->ctx;
@@ -259,21 +270,13 @@ int sbh_shard_load(sbh_shard *sh, const void *src, uint64_t n, uint64_t file_off
   if (rc) return rc;
   HIPCHK(ctx, hipStreamSynchronize(sh->st));  // (no kernel may still read the old bytes)
   HIPCHK(ctx, sh->comp.ensure(n + sh->pad));
-  // the copy on the shard's copy stream, at another priority than every compute stream: its
-  // hardware queue is then never one another task's kernels wait behind (see sbh_run_stream2)
-  hipStream_t cs = sh->st;
-  if (!std::getenv("SBH_LOAD_ON_SHARD_STREAM")) {
-    if (!sh->cs) {
-      int least = 0, greatest = 0;
-      if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && greatest != least)
-        HIPCHK(ctx, hipStreamCreateWithPriority(&sh->cs, hipStreamNonBlocking, greatest));
-    }
-    if (sh->cs) cs = sh->cs;
-  }
+  // the copy on the shard's copy stream: its hardware queue is never one another task's kernels
+  // wait behind
+  if (!sh->cs) HIPCHK(ctx, copy_stream_create(&sh->cs));
   if (n)
     HIPCHK(ctx, hipMemcpyAsync(sh->comp.p, src, n, comp_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
-                               cs));
-  if (cs != sh->st) HIPCHK(ctx, hipStreamSynchronize(cs));
+                               sh->cs));
+  HIPCHK(ctx, hipStreamSynchronize(sh->cs));
   HIPCHK(ctx, hipMemsetAsync(sh->comp.p + n, 0, sh->pad, sh->st));
   HIPCHK(ctx, hipStreamSynchronize(sh->st));
   resident_changed(sh, file_offset, n);
@@ -285,24 +288,10 @@ int sbh_shard_load(sbh_shard *sh, const void *src, uint64_t n, uint64_t file_off
 namespace sbh {
 
 // copy threads per prefetch (SBH_PREFETCH_THREADS, default 4), each hipMemcpyAsync-ing its
-// part on its own stream.  SBH_PREFETCH_STAGE=1: host memory that is not page-locked (a mapped
-// file, a numpy array) goes through page-locked staging chunks instead -- each thread memcpys a
-// chunk into its slot and DMAs it while it fills the next (2 slots of 8 MiB per thread).  Measured
-// on configs[2]'s 100.9 GiB file (pageable numpy): direct 2.34 s of copies (r05f, ~46 GB/s, the
-// same with 1 or 4 threads), staged 2.32 s (r05h) and slower on a 5 GiB file (136 vs 118 ms):
-// the host's memory bandwidth share, not the runtime's staging, is the limit, so staging is off
-// by default.  Page-locked host memory is DMAed directly (~56 GB/s).
-static uint32_t prefetch_threads() {
-  const char *e = std::getenv("SBH_PREFETCH_THREADS");
-  const long v = e ? std::atol(e) : 4;
-  return (uint32_t)std::min<long>(std::max<long>(v, 1), 16);
-}
-static bool prefetch_stage() {
-  const char *e = std::getenv("SBH_PREFETCH_STAGE");
-  return e && std::atol(e) == 1;
-}
-static constexpr uint32_t PF_SLOTS = 2;
-static constexpr uint64_t PF_CHUNK = 8ull << 20;
+// part on its own stream, pageable host memory (a mapped file, a numpy array) included.  (Measured
+// and removed: staging pageable memory through page-locked chunks of the threads' own, 2.32 s
+// against 2.34 s on a 100.9 GiB file and slower on a 5 GiB one -- DESIGN_HISTORY.md.)
+static uint32_t prefetch_threads() { return (uint32_t)env_uint("SBH_PREFETCH_THREADS", 4, 1, 16); }
 
 int shard_prefetch(sbh_shard *sh, const void *src, uint64_t n, uint64_t file_offset, const uint64_t *aux,
                    uint64_t n_aux) {
@@ -319,20 +308,6 @@ int shard_prefetch(sbh_shard *sh, const void *src, uint64_t n, uint64_t file_off
     HIPCHK(ctx, hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
     sh->pf_stream.push_back(st);
   }
-  hipPointerAttribute_t pa{};
-  const bool pinned = n && hipPointerGetAttributes(&pa, src) == hipSuccess && pa.type == hipMemoryTypeHost;
-  (void)hipGetLastError();
-  const bool stage = !pinned && prefetch_stage();
-  if (stage) {
-    while (sh->pf_pin.size() < (size_t)nt * PF_SLOTS) {
-      void *p = nullptr;
-      HIPCHK(ctx, hipHostMalloc(&p, PF_CHUNK, hipHostMallocDefault));
-      sh->pf_pin.push_back(static_cast<uint8_t *>(p));
-      hipEvent_t ev = nullptr;
-      HIPCHK(ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-      sh->pf_ev.push_back(ev);
-    }
-  }
   sh->pf_active = true;
   sh->pf_off = file_offset, sh->pf_n = n, sh->pf_naux = n_aux;
   sh->pf_err.assign(nt, hipSuccess);
@@ -348,32 +323,15 @@ int shard_prefetch(sbh_shard *sh, const void *src, uint64_t n, uint64_t file_off
     hipStream_t cs = sh->pf_stream[k];
     hipError_t *err = &sh->pf_err[k];
     double *ms = &sh->pf_ms[k];
-    uint8_t *const *pin = stage ? sh->pf_pin.data() + (size_t)k * PF_SLOTS : nullptr;
-    hipEvent_t *ev = stage ? sh->pf_ev.data() + (size_t)k * PF_SLOTS : nullptr;
     sh->pf.emplace_back([=]() {
-      uint32_t used = 0;  // staging chunks issued by this thread
       // [from, from + len) of host memory to device memory at to
-      auto copy = [&](uint8_t *to, const uint8_t *from, uint64_t len) -> hipError_t {
-        if (!stage) return len ? hipMemcpyAsync(to, from, len, hipMemcpyHostToDevice, cs) : hipSuccess;
-        for (uint64_t o = 0; o < len; o += PF_CHUNK, ++used) {
-          const uint32_t slot = used % PF_SLOTS;
-          const uint64_t m = std::min(PF_CHUNK, len - o);
-          if (used >= PF_SLOTS) {  // the slot's previous DMA must be done before it is refilled
-            const hipError_t e = hipEventSynchronize(ev[slot]);
-            if (e != hipSuccess) return e;
-          }
-          std::memcpy(pin[slot], from + o, m);
-          hipError_t e = hipMemcpyAsync(to + o, pin[slot], m, hipMemcpyHostToDevice, cs);
-          if (e == hipSuccess) e = hipEventRecord(ev[slot], cs);
-          if (e != hipSuccess) return e;
-        }
-        return hipSuccess;
+      auto copy = [&](void *to, const void *from, uint64_t len) {
+        return len ? hipMemcpyAsync(to, from, len, hipMemcpyHostToDevice, cs) : hipSuccess;
       };
       hipError_t e = hipSetDevice(dev);
       if (e == hipSuccess) e = copy(dst + lo, static_cast<const uint8_t *>(src) + lo, hi - lo);
       if (e == hipSuccess && k == 0) e = hipMemsetAsync(dst + n, 0, pad, cs);
-      if (e == hipSuccess && k == 0 && n_aux)
-        e = copy(reinterpret_cast<uint8_t *>(adst), reinterpret_cast<const uint8_t *>(aux), 8 * n_aux);
+      if (e == hipSuccess && k == 0 && n_aux) e = copy(adst, aux, 8 * n_aux);
       if (e == hipSuccess) e = hipStreamSynchronize(cs);
       *err = e;
       *ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -443,10 +401,7 @@ int sbh_find_block_start(sbh_shard *sh, uint64_t start, int32_t k, uint64_t *out
 
 // SBH_CHAIN_JUMP=1: the index always builds the block chain by pointer jumping (the path a
 // chain with false-positive candidates takes), for tests and A/B.
-static bool chain_jump_only() {
-  const char *e = std::getenv("SBH_CHAIN_JUMP");
-  return e && e[0] == '1';
-}
+static bool chain_jump_only() { return env_flag("SBH_CHAIN_JUMP"); }
 
 // MetadataStream from `start` (bgzf/.../block/MetadataStream.scala:16-58)
 int sbh_index(sbh_shard *sh, uint64_t start, uint64_t *n_blocks, uint64_t *flat_size) {
@@ -455,7 +410,6 @@ int sbh_index(sbh_shard *sh, uint64_t start, uint64_t *n_blocks, uint64_t *flat_
   hipStream_t st = sh->st;
   int rc = set_device(ctx);
   if (rc) return rc;
-  sh->sieve_nref1 = 0;
   sh->indexed = sh->inflated = sh->bits_valid = sh->chain_ok = sh->cm_valid = false;
   // a new index rebases every flat offset: the last scan's positions, and what was rendered from
   // them, describe a stream that is no longer there (what resident_changed voids of them)
@@ -642,22 +596,6 @@ static int inflate_status(sbh_shard *sh, hipStream_t st, uint64_t *bad_block, co
                    (unsigned long long)b.start);
 }
 
-// SBH_SIEVE=1: k_eager reads its first filter from a bitmap k_lz left (measured slower, DESIGN.md
-// §10: k_lz's writer is removed, so nothing fills the bitmap; off by default, k_eager sweeps
-// refIDs itself)
-static bool sieve_on() {
-  const char *e = std::getenv("SBH_SIEVE");
-  return e && e[0] == '1';
-}
-// The sieve k_lz fills for k_eager (launch_lz): one bit per flat position of the shard, plus the
-// look-ahead an eager window past the last tile reads (masked there); nullptr when off or when the
-// contig count is not known yet.
-static uint32_t *sieve_for(sbh_shard *sh) {
-  if (!sieve_on() || sh->nctg < 0) return nullptr;
-  if (sh->sieve.ensure((sh->utotal + sh->pad + 65536) / 32 + 2) != hipSuccess) return nullptr;
-  return sh->sieve.p;
-}
-
 static hipError_t zero_u_pad(sbh_shard *sh, hipStream_t st) {
   if (sh->u_pad_clean == sh->utotal && sh->u_pad_cap == sh->U.cap) return hipSuccess;
   const hipError_t e = hipMemsetAsync(sh->U.p + sh->utotal, 0, sh->pad, st);
@@ -676,11 +614,7 @@ static DevBlocks blocks_from(DevBlocks d, uint64_t b) {
 // shard whose flat bytes exceed the budget (SBH_TOK_BUDGET bytes, default 16 GiB) is inflated in
 // consecutive batches of blocks that reuse one buffer, so HBM holds the compressed and flat
 // bytes plus a bounded token buffer whatever the shard size.
-static uint64_t tok_cap_flat() {
-  const char *e = std::getenv("SBH_TOK_BUDGET");
-  const long long v = e ? std::atoll(e) : 0;
-  return (v > 0 ? (uint64_t)v : (16ull << 30)) / 4;
-}
+static uint64_t tok_cap_flat() { return env_uint("SBH_TOK_BUDGET", 16ull << 30) / 4; }
 
 struct TokPlan {
   std::vector<std::pair<uint64_t, uint64_t>> batches;  // blocks [b0, b1)
@@ -725,20 +659,17 @@ int sbh_inflate(sbh_shard *sh, uint64_t *bad_block) {
   const TokPlan P = tok_plan(sh, ~0ull);
   HIPCHK(ctx, sh->tok.ensure(P.tok_len));
   HIPCHK(ctx, zero_u_pad(sh, st));
-  uint32_t *sv = sieve_for(sh);
-  const uint32_t nref1 = (uint32_t)sh->nctg + 1;
   mark(sh, 2);
   for (const auto &bt : P.batches) {  // (one stream: a batch's k_lz finishes before the next k_huff)
     const DevBlocks d = blocks_from(sh->dev_blocks(), bt.first);
     const uint64_t base = P.reuse ? sh->hb[bt.first].ustart : 0;
     HIPCHK(ctx, launch_huff(sh->comp.p, d, bt.second - bt.first, sh->tok.p, base, st));
-    HIPCHK(ctx, launch_lz(sh->comp.p, d, bt.second - bt.first, sh->tok.p, base, sh->U.p, st, sv, nref1));
+    HIPCHK(ctx, launch_lz(sh->comp.p, d, bt.second - bt.first, sh->tok.p, base, sh->U.p, st));
   }
   mark(sh, 3);
   rc = inflate_status(sh, st, bad_block);
   if (rc) return rc;
   sh->inflated = true;
-  sh->sieve_nref1 = sv ? nref1 : 0;
   sh->bits_valid = sh->chain_ok = sh->cm_valid = false;
   return SBH_OK;
 }
@@ -882,11 +813,7 @@ static constexpr uint64_t DEFER_CAP = 1 << 20;
 // this design): 1 batch 34.7 ms/step, 3 batches 35.2, 16 batches 38.2 -- side by side
 // the three kernels contend for the same LDS and issue slots, and k_lz (two 80 KiB
 // workgroups per CU) loses the most; the pipeline stays for inputs where it pays.
-static uint64_t pipe_min_blocks() {
-  const char *e = std::getenv("SBH_PIPE_MIN_BLOCKS");
-  const long long v = e ? std::atoll(e) : 0;
-  return v > 0 ? (uint64_t)v : ~0ull;
-}
+static uint64_t pipe_min_blocks() { return env_uint("SBH_PIPE_MIN_BLOCKS", ~0ull); }
 
 static hipEvent_t pev(sbh_shard *sh, size_t i) {
   while (sh->pev.size() <= i) {
@@ -914,9 +841,7 @@ static int run_pipelined(sbh_shard *sh, uint64_t E, int32_t rtc, uint64_t *n_tru
   // one batch (the default) of a resident shard: every launch on the shard's stream, no
   // cross-stream event waits (each cost the step ~15 us of idle device between the stages)
   hipStream_t sl = sa, se = sa;
-  static const char *ps = std::getenv("SBH_PIPE_STREAMS");  // (A/B: 3 = three streams for every shard)
-  static const bool three = ps && std::atoi(ps) == 3;
-  if (P.batches.size() > 1 || three) {
+  if (P.batches.size() > 1) {
     if (!sh->s_lz) HIPCHK(ctx, hipStreamCreateWithFlags(&sh->s_lz, hipStreamNonBlocking));
     if (!sh->s_eg) HIPCHK(ctx, hipStreamCreateWithFlags(&sh->s_eg, hipStreamNonBlocking));
     sl = sh->s_lz;
@@ -941,9 +866,6 @@ static int run_pipelined(sbh_shard *sh, uint64_t E, int32_t rtc, uint64_t *n_tru
     HIPCHK(ctx, set_words(reinterpret_cast<uint64_t *>(c), reinterpret_cast<const uint64_t *>(tpl), CTR_RUN_WORDS, sa));
   }
   sh->inflated = sh->bits_valid = sh->chain_ok = sh->cm_valid = false;
-  sh->sieve_nref1 = 0;
-  uint32_t *sv = sieve_for(sh);
-  const uint32_t nref1 = (uint32_t)sh->nctg + 1;
   sh->pipe_fallback = false;
   const uint64_t nbat = P.batches.size();
   // events: per batch [huff start, huff end, lz start, lz end, eager start, eager end]
@@ -968,7 +890,7 @@ static int run_pipelined(sbh_shard *sh, uint64_t E, int32_t rtc, uint64_t *n_tru
     HIPCHK(ctx, hipEventRecord(e[1], sa));
     HIPCHK(ctx, wait(sl, e[1], sa));
     HIPCHK(ctx, hipEventRecord(e[2], sl));
-    HIPCHK(ctx, launch_lz(sh->comp.p, d, b1 - b0, sh->tok.p, base, sh->U.p, sl, sv, nref1));
+    HIPCHK(ctx, launch_lz(sh->comp.p, d, b1 - b0, sh->tok.p, base, sh->U.p, sl));
     HIPCHK(ctx, hipEventRecord(e[3], sl));
     // eager tiles whose staged windows lie below the inflated frontier
     const bool last = i + 1 == nbat;
@@ -983,7 +905,7 @@ static int run_pipelined(sbh_shard *sh, uint64_t E, int32_t rtc, uint64_t *n_tru
       HIPCHK(ctx, hipEventRecord(e[4], se));
       HIPCHK(ctx, launch_eager(sh->U.p, sh->utotal + sh->pad, e_done, hi, sh->d_seg.p, (uint32_t)sh->seg_end.size(),
                                sh->open_last ? 1 : 0, sh->ctg.p, sh->nctg, rtc, sh->bits.p + e_done / 32, c, se,
-                               front, sh->defer.p, DEFER_CAP, sh->xq.p, xq_cap(), sv));
+                               front, sh->defer.p, DEFER_CAP, sh->xq.p, XQ_CAP_MAX));
       HIPCHK(ctx, hipEventRecord(e[5], se));
       eager_launched[i] = 1;
       e_done = hi;
@@ -994,7 +916,7 @@ static int run_pipelined(sbh_shard *sh, uint64_t E, int32_t rtc, uint64_t *n_tru
                                  sh->ctg.p, sh->nctg, rtc, sh->bits.p, c, sh->defer.p, DEFER_CAP, se));
   HIPCHK(ctx, hipEventRecord(ev[6 * nbat + 2], se));
   HIPCHK(ctx, launch_eager_xq(sh->U.p, 0, sh->d_seg.p, (uint32_t)sh->seg_end.size(), sh->open_last ? 1 : 0,
-                              sh->ctg.p, sh->nctg, rtc, sh->bits.p, c, sh->xq.p, xq_cap(), se));
+                              sh->ctg.p, sh->nctg, rtc, sh->bits.p, c, sh->xq.p, XQ_CAP_MAX, se));
   HIPCHK(ctx, hipEventRecord(ev[6 * nbat + 3], se));
   HIPCHK(ctx, hipEventRecord(ev[6 * nbat + 1], se));
   HIPCHK(ctx, wait(sa, ev[6 * nbat + 1], se));
@@ -1004,7 +926,6 @@ static int run_pipelined(sbh_shard *sh, uint64_t E, int32_t rtc, uint64_t *n_tru
     if (rs) return rs;
   }
   sh->inflated = true;
-  sh->sieve_nref1 = sv ? nref1 : 0;
   if (sh->timing) {
     double hs = 0, ls = 0, es = 0;
     for (uint64_t i = 0; i < nbat; ++i) {
@@ -1019,7 +940,7 @@ static int run_pipelined(sbh_shard *sh, uint64_t E, int32_t rtc, uint64_t *n_tru
     if (hipEventElapsedTime(&xs, ev[6 * nbat + 2], ev[6 * nbat + 3]) == hipSuccess) es += xs;  // k_eager_xq
     sh->pipe_ms[2] = es;
   }
-  if (std::getenv("SBH_XQ_DEBUG"))
+  if (env_flag("SBH_XQ_DEBUG"))
     fprintf(stderr, "[sbh] eager: deferred %llu, long-record queue %llu (%llu past the pre-test)\n",
             sh->h_ctr[ctr::EAGER_DEFER_N], sh->h_ctr[ctr::EAGER_XQ_N], sh->h_ctr[ctr::EAGER_XQ_LIVE]);
   if (sh->h_ctr[ctr::EAGER_DEFER_N] > DEFER_CAP) {  // deferral overflow: plain pass
@@ -1261,15 +1182,7 @@ int sbh_run_stream2(sbh_ctx *ctx, const void *host, uint64_t n, uint64_t file_of
       return res->status = rc;
     }
     scp->sh->comp.release();
-    // the copy stream at another priority than the compute streams: its hardware queue then comes
-    // from another pool, so no compute stream shares it (a copy in flight on a shared queue held
-    // the next window's kernels behind it: e2e 130 -> 84 GB/s depending on stream creation order)
-    int least = 0, greatest = 0;
-    hipError_t e = hipDeviceGetStreamPriorityRange(&least, &greatest);
-    if (e == hipSuccess)
-      e = greatest != least && !std::getenv("SBH_CS_SAME_PRIORITY")
-              ? hipStreamCreateWithPriority(&scp->cs, hipStreamNonBlocking, greatest)
-              : hipStreamCreateWithFlags(&scp->cs, hipStreamNonBlocking);
+    hipError_t e = copy_stream_create(&scp->cs);
     for (int i = 0; i < 2 && e == hipSuccess; ++i) {
       e = hipEventCreate(&scp->done[i]);
       if (e == hipSuccess) e = hipEventCreate(&scp->c0[i]);

@@ -91,6 +91,27 @@ struct DBuf {  // grow-only device buffer, freed with its owner (movable, not co
   void forget() { p = nullptr, cap = 0, lent = false; }
 };
 
+// ---- run-time knobs ----------------------------------------------------------------------------
+// The environment is read through these three and nowhere else under csrc/; INTEGRATION.md
+// ("Run-time knobs") lists every name they are given.  A knob is read again at each call, never
+// cached: tests change them between calls in one process.
+// The value, or nullptr when the variable is unset or empty.
+inline const char *env_str(const char *name) {
+  const char *e = std::getenv(name);
+  return e && *e ? e : nullptr;
+}
+// 0 / 1: off / on; unset: dflt.
+inline bool env_flag(const char *name, bool dflt = false) {
+  const char *e = env_str(name);
+  return e ? e[0] != '0' : dflt;
+}
+// A positive integer clamped to [lo, hi]; unset or not positive: dflt.
+inline uint64_t env_uint(const char *name, uint64_t dflt, uint64_t lo = 1, uint64_t hi = ~0ull) {
+  const char *e = env_str(name);
+  const long long v = e ? std::atoll(e) : 0;
+  return v > 0 ? std::min(std::max<uint64_t>((uint64_t)v, lo), hi) : dflt;
+}
+
 }  // namespace sbh
 
 struct StreamCache;  // sbh_run_stream's window shard, buffers and copy stream (kept between calls)
@@ -150,10 +171,6 @@ struct sbh_shard {
   sbh::DBuf<int32_t> ctg;
   int32_t nctg = -1;
   sbh::DBuf<uint32_t> bits;
-  // k_lz's first-filter bitmap for k_eager (launch_lz's sieve), valid for the inflated bytes and
-  // the contig count it was computed with (sieve_nref1 = contigs + 1; 0: none)
-  sbh::DBuf<uint32_t> sieve;
-  uint32_t sieve_nref1 = 0;
   bool pipe_fallback = false;  // run_pipelined redid the eager pass (a deferral overflow)
   // chain marking (pointer doubling) over the set bits of [cm_first, cm_E) when the bitmap
   // is not the chain: node positions, per-word prefix counts, jumps, marks and their prefix
@@ -281,8 +298,6 @@ struct sbh_shard {
   bool pf_active = false;
   uint64_t pf_off = 0, pf_n = 0, pf_naux = 0;
   std::vector<double> pf_ms;  // each copy thread's wall time
-  std::vector<uint8_t *> pf_pin;  // page-locked staging, PF_SLOTS chunks per copy thread
-  std::vector<hipEvent_t> pf_ev;  // (one per staging chunk: its DMA is done)
   hipEvent_t ev[9] = {};
   bool ev_ok = false, timing = false;
   double stage_ms[6] = {0, 0, 0, 0, 0, 0};
@@ -301,7 +316,6 @@ struct sbh_shard {
     if (pf_active) (void)sbh::shard_prefetch_finish(this, false);  // (joins the copy threads)
     if (ctx) (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(st);
-    for (hipEvent_t e : pf_ev) (void)hipEventDestroy(e);
     for (hipEvent_t e : ev)
       if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : pev)
@@ -312,7 +326,6 @@ struct sbh_shard {
         (void)hipStreamSynchronize(s);
         (void)hipStreamDestroy(s);
       }
-    for (uint8_t *q : pf_pin) (void)hipHostFree(q);
     if (sp_pin) (void)hipHostFree(sp_pin);
     if (h_ctr) (void)hipHostFree(h_ctr);
     if (own_st && st) (void)hipStreamDestroy(st);
@@ -442,10 +455,9 @@ void resident_changed(sbh_shard *sh, uint64_t file_off, uint64_t n);
 int64_t block_index_of(const sbh_shard *sh, uint64_t file_pos);
 
 // ---- checkers, chain, splits (api_check.hip) ---------------------------------------------------
-// Capacity of the long-record eager queue (sbh_shard::xq holds 2 XQ_CAP_MAX entries); xq_cap() is
-// what a launch is given: 0 with SBH_XQ=0 (every exact check inline), else XQ_CAP_MAX.
+// Capacity of the long-record eager queue (sbh_shard::xq holds 2 XQ_CAP_MAX entries), which every
+// launch is given.
 constexpr uint64_t XQ_CAP_MAX = 1 << 22;  // queued long-record eager candidates (2 x 32 MiB)
-uint64_t xq_cap();
 // The eager bitmap of flat [begin, end) into sh->bits (then bits_valid, bits_begin, bits_end,
 // bits_rtc); *n_true (optional) = its set bits.  SBH_E_NEED_HALO when a position needs bytes past
 // the shard.  The caller has checked the arguments and set the device.

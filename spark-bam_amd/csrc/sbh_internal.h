@@ -172,13 +172,8 @@ hipError_t build_chain(const uint8_t *comp, uint64_t n, const uint64_t *cand, ui
 constexpr uint32_t HUFF_FAST = 1u, HUFF_SERIAL = 2u;
 hipError_t launch_huff(const uint8_t *comp, DevBlocks blocks, uint64_t nblocks, uint32_t *tok_buf, uint64_t tok_base,
                        hipStream_t stream, uint32_t stages = HUFF_FAST | HUFF_SERIAL);
-// sieve (optional): bit p of the flat bitmap = position p may pass eager.Checker's refID / next
-// refID range and pos / next pos sign tests (k_eager's first filter, evaluated by k_lz on the bytes
-// still in its LDS ring; 1 wherever the block's WG cannot decide: seams, stored blocks).  nref1 =
-// contigs + 1.
 hipError_t launch_lz(const uint8_t *comp, DevBlocks blocks, uint64_t nblocks, const uint32_t *tok_buf,
-                     uint64_t tok_base, uint8_t *U, hipStream_t stream, uint32_t *sieve = nullptr,
-                     uint32_t nref1 = 0);
+                     uint64_t tok_base, uint8_t *U, hipStream_t stream);
 // *first = the first block of [0, n) whose status is not INF_OK (~0 if none).
 // (init: set *first to ~0 first; false when the caller already did)
 hipError_t launch_first_bad(const uint32_t *status, uint64_t n, unsigned long long *first, hipStream_t stream,
@@ -189,8 +184,7 @@ hipError_t launch_first_bad(const uint32_t *status, uint64_t n, unsigned long lo
 hipError_t launch_eager(const uint8_t *U, uint64_t u_pad, uint64_t begin, uint64_t end, const uint64_t *seg_end,
                         uint32_t nseg, uint32_t open_last, const int32_t *ctg, int32_t nctg, int32_t rtc,
                         uint32_t *bits, unsigned long long *counters, hipStream_t st, uint64_t front,
-                        uint64_t *defer_pos, uint64_t defer_cap, uint64_t *xq_pos, uint64_t xq_cap,
-                        const uint32_t *sieve = nullptr);
+                        uint64_t *defer_pos, uint64_t defer_cap, uint64_t *xq_pos, uint64_t xq_cap);
 hipError_t launch_eager_xq(const uint8_t *U, uint64_t begin, const uint64_t *seg_end, uint32_t nseg,
                            uint32_t open_last, const int32_t *ctg, int32_t nctg, int32_t rtc, uint32_t *bits,
                            unsigned long long *counters, uint64_t *xq_pos, uint64_t cap, hipStream_t st);
@@ -214,7 +208,7 @@ hipError_t launch_chain_walk(const uint8_t *U, uint64_t first, uint64_t E, uint6
 hipError_t launch_chain_mark(const uint8_t *U, const uint32_t *bits, uint64_t begin, uint64_t from, uint64_t E,
                              uint64_t total, const uint64_t *pos, const uint64_t *wpre, uint64_t n, uint32_t *J,
                              uint32_t *J2, uint32_t *J0, uint64_t *mark, unsigned long long *exit_pos,
-                             uint32_t *final_code, hipStream_t st);
+                             uint32_t *final_code, bool doubling, hipStream_t st);
 
 // Record field extraction (records.hip): device columns of a decoded batch (the host
 // view is sbh_records_out in sparkbam.h).

@@ -589,9 +589,7 @@ int sbh_bgzf_compress_level(sbh_ctx *ctx, const void *src, uint64_t n, int src_o
   float kms = 0.f;
   if (nb) {
     // members in batches: scratch bounded by the batch, not the input
-    uint64_t bmax = fast ? DEFLATE_BATCH : ZDEFLATE_BATCH;
-    if (const char *e = std::getenv("SBH_ZDEFLATE_BATCH"))
-      if (!fast && std::strtoull(e, nullptr, 10) > 0) bmax = std::strtoull(e, nullptr, 10);
+    uint64_t bmax = fast ? DEFLATE_BATCH : env_uint("SBH_ZDEFLATE_BATCH", ZDEFLATE_BATCH);
     const uint64_t stride = fast ? 65536ull : ZDEFLATE_SLOT;
     // scratch per member; the batch shrinks to half of the free HBM (a resident shard may hold
     // the rest), never below 256 members

@@ -4,14 +4,11 @@ table (bgzf_index.hip: k_cand_count, k_cand_write, k_cand_link, k_chain_emit, th
 on both chain paths, the inflate over those tables, k_block_crc in both directions (every size and
 alignment it branches on passes; every corrupted member is counted, and no other), the in-run CRC
 of the windowed path, and k_find_block_start against the probe literals, whole and cut."""
-import contextlib
-import os
-
 import numpy as np
 import pytest
 
 import bgzf_corpus as bc
-from pkg import sb
+from pkg import knob, sb
 from test_index_chain_gpu import both, index_run
 
 pytestmark = pytest.mark.gpu
@@ -75,17 +72,8 @@ def test_index_gives_the_builders_table(ctx, f):
         assert (nb, fs) == (len(f.table), total)
 
 
-@contextlib.contextmanager
 def chain_jump(on):
-    old = os.environ.get("SBH_CHAIN_JUMP")
-    os.environ["SBH_CHAIN_JUMP"] = "1" if on else "0"
-    try:
-        yield
-    finally:
-        if old is None:
-            os.environ.pop("SBH_CHAIN_JUMP", None)
-        else:
-            os.environ["SBH_CHAIN_JUMP"] = old
+    return knob("SBH_CHAIN_JUMP", "1" if on else "0")
 
 
 @pytest.mark.parametrize("residue,count", [(1, 20), (7, 30), (13, 2)])

@@ -373,7 +373,7 @@ def test_shard_with_halo_matches_whole_file(ctx, synth_files):
 
 
 @pytest.mark.parametrize("name,batch_blocks", [("short_l6", 4), ("long", 2), ("adversarial", 3)])
-def test_pipelined_run_matches_separate_calls(ctx, synth_files, name, batch_blocks):
+def test_pipelined_run_matches_separate_calls(ctx, synth_files, name, batch_blocks, monkeypatch):
     """run() inflates and checks in a pipeline over block batches (eager tiles launched
     behind the inflate frontier, positions whose exact check crosses it deferred).  With
     tiny batches (many frontiers; long reads cross them) it must equal inflate() +
@@ -382,20 +382,13 @@ def test_pipelined_run_matches_separate_calls(ctx, synth_files, name, batch_bloc
     of = OracleFile(data)
     sh = ctx.shard(data)
     sh.set_contigs(of.contig_len)
-    old = os.environ.get("SBH_PIPE_MIN_BLOCKS")
-    os.environ["SBH_PIPE_MIN_BLOCKS"] = str(batch_blocks)
-    try:
-        r = sh.run(0, data.size)
-        got = sh.read_flat(0, of.flat_size)
-        i = first_diff(got, of.uncompressed())
-        assert i < 0, f"inflate differs at flat {i}"
-        E = r["flat_bytes"]
-        bits_pipe = sh.eager_bits(0, E)
-    finally:
-        if old is None:
-            del os.environ["SBH_PIPE_MIN_BLOCKS"]
-        else:
-            os.environ["SBH_PIPE_MIN_BLOCKS"] = old
+    monkeypatch.setenv("SBH_PIPE_MIN_BLOCKS", str(batch_blocks))
+    r = sh.run(0, data.size)
+    got = sh.read_flat(0, of.flat_size)
+    i = first_diff(got, of.uncompressed())
+    assert i < 0, f"inflate differs at flat {i}"
+    E = r["flat_bytes"]
+    bits_pipe = sh.eager_bits(0, E)
     assert r["status"] == 0
     # the same shard, unpipelined, over the same range
     sh.index(0)
@@ -409,6 +402,81 @@ def test_pipelined_run_matches_separate_calls(ctx, synth_files, name, batch_bloc
     k = of.flat_size
     assert np.array_equal(np.unpackbits(bits_pipe, bitorder="little")[:k], np.unpackbits(bits_ref, bitorder="little")[:k])
     sh.close()
+
+
+TOK_BUDGET = 4 * 3 * 65536  # bytes: the tokens of three BGZF blocks of flat bytes
+
+
+def tok_batches(blocks, max_blocks=None):
+    """The block batches [b0, b1) that share one token buffer of TOK_BUDGET bytes, from the block
+    table alone: 4 B of tokens per flat byte, each batch the longest run of blocks (max_blocks at
+    most) whose flat bytes fit, one block at least."""
+    cap = TOK_BUDGET // 4
+    flat = blocks[-1][3] + blocks[-1][2]
+    assert flat + 64 > cap, "the budget does not bind: nothing would reuse the buffer"
+    out, b0 = [], 0
+    while b0 < len(blocks):
+        b1 = b0 + 1
+        while (b1 < len(blocks) and (max_blocks is None or b1 - b0 < max_blocks)
+               and blocks[b1][3] + blocks[b1][2] - blocks[b0][3] <= cap):
+            b1 += 1
+        out.append((b0, b1))
+        b0 = b1
+    return out
+
+
+@pytest.mark.parametrize("name", ["long", "short_l6"])
+def test_token_budget_inflate_in_batches(ctx, synth_files, name, monkeypatch):
+    """SBH_TOK_BUDGET below the shard's tokens: sbh_inflate runs batch after batch of blocks through
+    one reused token buffer, and the flat bytes are the oracle's."""
+    monkeypatch.setenv("SBH_TOK_BUDGET", str(TOK_BUDGET))
+    data = synth_files[name]
+    of = OracleFile(data)
+    sh = ctx.shard(data)
+    try:
+        sh.index(0)
+        assert len(tok_batches(sh.blocks())) >= 3
+        sh.inflate()
+        i = first_diff(sh.read_flat(0, of.flat_size), of.uncompressed())
+        assert i < 0, f"inflate differs at flat {i}"
+    finally:
+        sh.close()
+
+
+@pytest.mark.parametrize("name,batch_blocks", [("long", 2), ("adversarial", 3)])
+def test_token_budget_pipelined_run(ctx, synth_files, name, batch_blocks, monkeypatch):
+    """run() under SBH_TOK_BUDGET and small pipeline batches: each batch's k_huff waits for the k_lz
+    that still reads the shared token buffer.  Same n_true, record count and eager bitmap as
+    inflate() + check_eager() + count_records() without the budget."""
+    data = synth_files[name]
+    of = OracleFile(data)
+    monkeypatch.setenv("SBH_TOK_BUDGET", str(TOK_BUDGET))
+    monkeypatch.setenv("SBH_PIPE_MIN_BLOCKS", str(batch_blocks))
+    sh = ctx.shard(data)
+    try:
+        sh.set_contigs(of.contig_len)
+        sh.index(0)
+        blocks = sh.blocks()  # (run() indexes again from the same start: the same table)
+        r = sh.run(0, data.size)
+        assert r["status"] == 0 and r["n_blocks"] == len(blocks)
+        E = r["flat_bytes"]
+        bits_run = sh.eager_bits(0, E)
+        npipe = max(1, min(16, len(blocks) // batch_blocks))  # the pipeline's batches without a budget
+        assert len(tok_batches(blocks, -(-len(blocks) // npipe))) >= 3
+    finally:
+        sh.close()
+    monkeypatch.delenv("SBH_TOK_BUDGET")
+    monkeypatch.delenv("SBH_PIPE_MIN_BLOCKS")
+    ref = load(ctx, data, of.contig_len)
+    try:
+        n, bits = ref.check_eager(0, E)
+        assert r["n_true"] == n
+        i = first_diff(np.unpackbits(bits_run, bitorder="little"), np.unpackbits(bits, bitorder="little"))
+        assert i < 0, f"eager under the budget differs at {i}"
+        first = ref.flat_of(r["first_vpos"] >> 16, r["first_vpos"] & 0xFFFF)
+        assert r["count"] == ref.count_records(first, E)
+    finally:
+        ref.close()
 
 
 @pytest.mark.parametrize("marking", ["peel", "doubling"])

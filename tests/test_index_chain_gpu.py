@@ -5,13 +5,11 @@ marks and ranks are direct and no pointer-jumping rounds run -- against the poin
 reference's .blocks files, on streams where the linear assumption holds and where it does not: a
 header planted inside a block's compressed bytes (a candidate off the chain), a link broken by a
 wrong BSIZE, a start past earlier candidates, a shard cut inside a block."""
-import os
-
 import numpy as np
 import pytest
 
 from conftest import golden_bam, read_blocks
-from pkg import sb
+from pkg import knob, sb
 
 pytestmark = pytest.mark.gpu
 
@@ -27,20 +25,15 @@ def ctx():
 
 def index_run(ctx, data, start=0, jump=False):
     """(n_blocks, flat_size, blocks) of one index call, or the exception it raised."""
-    old = os.environ.get("SBH_CHAIN_JUMP")
-    os.environ["SBH_CHAIN_JUMP"] = "1" if jump else "0"
     sh = ctx.shard(np.ascontiguousarray(data))
     try:
-        nb, fs = sh.index(start)
+        with knob("SBH_CHAIN_JUMP", "1" if jump else "0"):
+            nb, fs = sh.index(start)
         return nb, fs, sh.blocks()
     except Exception as e:  # (compared by type and message)
         return type(e).__name__, str(e)
     finally:
         sh.close()
-        if old is None:
-            os.environ.pop("SBH_CHAIN_JUMP", None)
-        else:
-            os.environ["SBH_CHAIN_JUMP"] = old
 
 
 def both(ctx, data, start=0):

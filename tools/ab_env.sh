@@ -1,5 +1,5 @@
 # A/B of one environment toggle on bench.py, ABAB order: tools/ab_env.sh TAG "ENV_A" "ENV_B" ARGS...
-# (e.g. "SBH_SIEVE=1" "SBH_SIEVE=0" --config B); each line lands in gpurun_out/TAG_ab.jsonl with its env
+# (e.g. "SBH_SPLIT_CC=1" "SBH_SPLIT_CC=0" --config B); each line lands in TAG_ab.jsonl of the output directory below, with its env
 set -o pipefail
 T=$1; A=$2; B=$3; shift 3
 mkdir -p gpurun_out
