@@ -23,7 +23,8 @@
  *    caller).  sbh_last_error / sbh_last_error_detail report the calling THREAD's last failed
  *    call on that context, so a task always reads back its own failure.  sbh_ctx_set_stream
  *    and sbh_ctx_destroy are setup/teardown calls: no other call may run on the context then
- *    (shards created after sbh_ctx_set_stream enqueue on the caller's stream instead of their own).
+ *    (shards created after sbh_ctx_set_stream enqueue on the caller's stream instead of their own;
+ *    which stream that may be, and the ordering the caller gets, are written at sbh_ctx_set_stream).
  *  - Offsets: "file offsets" are byte offsets in the compressed BGZF file; "flat"
  *    offsets index the shard's concatenated uncompressed bytes (the reference's
  *    UncompressedBytes view, bgzf/.../block/UncompressedBytes.scala:13-87).  A
@@ -115,7 +116,22 @@ const char *sbh_last_error(const sbh_ctx *ctx);
  *                              sbh_records_bam_scan only)
  *   anything else              no fields */
 int32_t sbh_last_error_detail(const sbh_ctx *ctx, int32_t *code, int64_t *fields, int32_t cap);
-/* Use a caller-owned hipStream_t (e.g. torch.cuda.current_stream().cuda_stream). */
+/* Use a caller-owned hipStream_t.  Every shard created afterwards -- those the context-level calls
+ * build for themselves included; idle window caches of sbh_run_stream2 are let go -- enqueues on it,
+ * and so does sbh_bgzf_compress*.  Shards created before the call keep their own streams.
+ *  - The stream must belong to the HIP runtime instance this library links (libamdhip64): create it
+ *    with that runtime's hipStreamCreate*.  A handle of another instance loaded into the process
+ *    means nothing here -- a torch build that ships its own libamdhip64.so has one, and then
+ *    torch.cuda.current_stream().cuda_stream must not be passed; it may be when torch and this
+ *    library resolve to the same libamdhip64.so.  NULL is legal and means the null stream.
+ *  - Ordering.  What the caller enqueued on the stream before a call is complete before the call
+ *    reads its inputs: a device-resident `comp` or `src` written on the stream (sbh_shard_create,
+ *    sbh_shard_load, sbh_bgzf_compress*), page-locked host bytes a copy on the stream was filling
+ *    (sbh_run_stream2).  Every call that enqueues device work returns with the stream drained
+ *    (hipStreamQuery is hipSuccess), so its device results (sbh_flat_device_ptr, ...) can be used by
+ *    work enqueued on the stream afterwards, or on any other stream.
+ *  - The library never destroys the stream.  It must outlive every shard of the context; tasks that
+ *    share the context then share the one stream, and one task's wait covers the others' work. */
 int sbh_ctx_set_stream(sbh_ctx *ctx, void *hip_stream);
 int sbh_ctx_synchronize(sbh_ctx *ctx);
 const char *sbh_version(void);

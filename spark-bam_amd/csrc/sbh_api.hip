@@ -178,8 +178,16 @@ int sbh_host_free(void *p) { return p && hipHostFree(p) != hipSuccess ? SBH_E_HI
 
 int sbh_ctx_set_stream(sbh_ctx *ctx, void *hip_stream) {
   if (!ctx) return SBH_E_ARG;
+  (void)hipSetDevice(ctx->device);
+  {
+    // the idle window caches hold shards with streams of their own: let them go, so that every
+    // shard built from here on -- sbh_run_stream2's window shard included -- is on the caller's stream
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    for (StreamCache *sc : ctx->sc_free) delete sc;
+    ctx->sc_free.clear();
+  }
   if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
-  ctx->stream = reinterpret_cast<hipStream_t>(hip_stream);
+  ctx->stream = reinterpret_cast<hipStream_t>(hip_stream);  // (null: the null stream)
   ctx->own_stream = false;
   return SBH_OK;
 }
@@ -188,7 +196,8 @@ int sbh_ctx_synchronize(sbh_ctx *ctx) {
   if (!ctx) return SBH_E_ARG;
   int rc = set_device(ctx);
   if (rc) return rc;
-  // the context's work is on its own stream and on its shards' streams: wait for the device
+  // the context's work is on its stream (its own or the caller's) and on the streams of its shards
+  // and accumulators: wait for the stream, then for the device
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   HIPCHK(ctx, hipDeviceSynchronize());
   return SBH_OK;
@@ -219,10 +228,7 @@ int sbh_shard_create(sbh_ctx *ctx, const void *src, uint64_t n, uint64_t file_of
     }
     sh->own_st = true;
   } else {
-    // The caller gave the context a stream (sbh_ctx_set_stream), and sparkbam.h says the shard
-    // then enqueues on it.  It does not: the shard runs on the null stream (the line here used
-    // to read `sh->st = sh->st`).  Kept as it behaves; DESIGN.md lists it as an open item.
-    sh->st = nullptr;
+    sh->st = ctx->stream;  // the caller's (sbh_ctx_set_stream): never destroyed here
   }
   sh->file_off = file_offset;
   sh->n = n;
@@ -268,7 +274,10 @@ int sbh_shard_load(sbh_shard *sh, const void *src, uint64_t n, uint64_t file_off
   sbh_ctx *ctx = sh->ctx;
   int rc = set_device(ctx);
   if (rc) return rc;
-  HIPCHK(ctx, hipStreamSynchronize(sh->st));  // (no kernel may still read the old bytes)
+  // No kernel may still read the old bytes.  On the caller's stream (sbh_ctx_set_stream) this wait
+  // is also what orders the copy below, which runs on another stream, behind the work that wrote
+  // `src`: nothing else ties the copy stream to the shard's stream before the copy.
+  HIPCHK(ctx, hipStreamSynchronize(sh->st));
   HIPCHK(ctx, sh->comp.ensure(n + sh->pad));
   // the copy on the shard's copy stream: its hardware queue is never one another task's kernels
   // wait behind
@@ -547,6 +556,9 @@ int sbh_index(sbh_shard *sh, uint64_t start, uint64_t *n_blocks, uint64_t *flat_
   sh->seg_end.push_back(total);
   HIPCHK(ctx, sh->d_seg.ensure(sh->seg_end.size()));
   HIPCHK(ctx, set_words(sh->d_seg.p, sh->seg_end.data(), sh->seg_end.size(), st));
+  // (a stream of the shard's own carries that last write to the shard's next call, with no host
+  // round trip here; the caller's stream is handed back drained, as after every call)
+  if (!sh->own_st) HIPCHK(ctx, hipStreamSynchronize(st));
   sh->nblocks = nchain;
   sh->utotal = total;
   sh->index_start = start;
@@ -1210,6 +1222,10 @@ int sbh_run_stream2(sbh_ctx *ctx, const void *host, uint64_t n, uint64_t file_of
   } detach{R};
   sbh_shard *sh = R.sh;
   sh->file_size = file_size;
+  // (sbh_set_contigs synchronises the shard's stream.  The window copies below run on the cache's
+  // copy stream, which no event orders behind the shard's: when that is the caller's stream
+  // (sbh_ctx_set_stream) and work on it was still writing `host`, this wait is what puts the first
+  // copy behind it -- a reused cache creates no shard, so nothing else would)
   rc = sbh_set_contigs(sh, contigs, n_contigs);
   if (rc) return res->status = rc;
   const uint64_t data_end = file_offset + n, pad = sh->pad;

@@ -122,6 +122,9 @@ struct StreamCache;  // sbh_run_stream's window shard, buffers and copy stream (
 // calls) or guarded by `mu` (the pool of streaming-window caches).  Each shard has its own HIP
 // stream (sbh_shard_create), so two tasks' shards run concurrently on the device and a task's
 // hipStreamSynchronize waits for its own work only; a shard itself belongs to one thread at a time.
+// A context that was given the caller's stream (sbh_ctx_set_stream, before any other thread uses the
+// context) puts every later shard on that one stream: the tasks then share it, each call still
+// drains it before it returns, and no shard ever destroys it.
 // The last error (message, status, the reference exception's fields) is kept per thread and per
 // context (t_err in sbh_api.hip), so one task's failure never overwrites what another task reads back.
 struct sbh_ctx {

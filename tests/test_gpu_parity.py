@@ -661,12 +661,9 @@ def test_split_parameters(golden, z, rtc):
 def _hbm_free():
     """Free device memory now, as the HIP runtime libsparkbam_hip.so itself links reports it
     (torch, when imported earlier in the run, brings its own libamdhip64.so: a second runtime
-    instance with no device state of ours)."""
-    import ctypes as C
-    hip = C.CDLL("libamdhip64.so.7")
-    free, total = C.c_size_t(), C.c_size_t()
-    assert hip.hipMemGetInfo(C.byref(free), C.byref(total)) == 0
-    return free.value
+    instance with no device state of ours; hip_rt finds ours)."""
+    import hip_rt
+    return hip_rt.mem_get_info()[0]
 
 
 @pytest.fixture(scope="module")
