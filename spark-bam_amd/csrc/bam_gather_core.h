@@ -88,6 +88,20 @@ inline bool filter_ok(const Filter &F) {
   return true;
 }
 
+// The opening of the four accumulators' add_host (depth_core.h, pileup_core.h, tally_core.h,
+// stats_core.h): every row is validated, kept or not, as gather_host below validates them, and
+// a kept row must also pass pred(r) -- the stage's own test, r the row's first byte.  Returns the first
+// row that fails, or NO_ROW.
+template <class Pred>
+inline uint64_t first_bad_row(const uint8_t *flat, uint64_t flat_size, const uint64_t *starts, uint64_t n, const Filter &F,
+                              Pred pred) {
+  uint64_t len = 0;
+  for (uint64_t i = 0; i < n; ++i)
+    if (row_check(flat, flat_size, starts[i], &len) != ROW_OK || (row_keep(flat + starts[i], i, F) && !pred(flat + starts[i])))
+      return i;
+  return NO_ROW;
+}
+
 // head, then the kept rows' bytes, in row order.  rec_off (n + 1 slots, n_kept + 1 written) and
 // rows (n slots, n_kept written) may be NULL; out == NULL: sizes only.  Returns 0, 1 (a malformed
 // row: *bad_row), 2 (out_cap too small) -- *n_kept and *bytes are set for 0 and 2.

@@ -147,8 +147,7 @@ __global__ __launch_bounds__(256) void k_depth_events(const uint8_t *__restrict_
         const uint32_t j = b0 + lane;
         const uint32_t w = j < wnc ? sbh_bam::ld32(c + 4 * (uint64_t)j) : 0u, op = w & 15u;
         const uint32_t l = w >> 4, adv = sbh_dep::op_advances(op) ? l : 0u;
-        // 64 lengths below 2^28: the low 16 bits sum below 2^22, the high 12 below 2^18
-        const uint64_t incl = (uint64_t)wave_incl_scan(adv & 0xffffu) + ((uint64_t)wave_incl_scan(adv >> 16) << 16);
+        const uint64_t incl = wave_incl_scan64(adv);  // (64 lengths below 2^28)
         if (j < wnc && sbh_dep::op_covers(op, flags))
           cov += emit(slots, S, wo, wbeg, wend, wx + (int64_t)(incl - adv), (int64_t)l);
         wx += (int64_t)__shfl((unsigned long long)incl, 63);
@@ -223,22 +222,8 @@ __global__ __launch_bounds__(TILE_T) void k_depth_tile_sums(const int32_t *slots
   if (threadIdx.x == 0) sums[blockIdx.x] = s_red[0] + s_red[1] + s_red[2] + s_red[3];
 }
 
-// What a lane needs about the spans of its 4 slots: slot s is a span's first when s == off[k], its
-// extra slot when s + 1 == off[k + 1].  off has n_spans + 1 entries and s < S == off[n_spans], so
-// span_of_slot's k is below n_spans and off[k + 1] exists.
-struct SlotSpan {
-  uint32_t k;
-  uint64_t first, next;  // off[k], off[k + 1]
-};
-__device__ __forceinline__ SlotSpan slot_span(const uint64_t *off, uint32_t n_spans, uint64_t s) {
-  const uint32_t k = sbh_dep::span_of_slot(off, n_spans, s);
-  return SlotSpan{k, off[k], off[k + 1]};
-}
-// the span of slot s, from the span of a slot before it (spans may be 2 slots short: a loop)
-__device__ __forceinline__ void slot_span_to(SlotSpan &q, const uint64_t *off, uint32_t n_spans, uint64_t s) {
-  while (s >= q.next && q.k + 1 < n_spans) ++q.k, q.first = q.next, q.next = off[q.k + 1];
-}
-
+// What a lane needs about the spans of its 4 slots is a SpanCursor (sbh_internal.h): a span's last slot
+// (s + 1 == next) is its extra slot, and a span may be 2 slots short.
 // base: the exclusive scan of the tile sums.  Depth in place; heads[tile]; tstat: 3 n_tiles words,
 // the tile's max depth, covered positions and sum of depth at [tile], [n_tiles + tile], [2 n_tiles +
 // tile] (k_depth_stats folds them: no workgroup of this kernel touches a word another one does).
@@ -267,7 +252,7 @@ __global__ __launch_bounds__(TILE_T) void k_depth_apply(int32_t *slots, uint64_t
     const uint32_t first = tile_slot(wave, r, lane);
     if (first >= count) continue;
     const uint64_t s0 = t0 + first;
-    SlotSpan q = slot_span(off, n_spans, s0);
+    SpanCursor q = SpanCursor::span_at(off, n_spans, s0);
     uint32_t d = tb + x[r], out[4];
     if (first + 4 <= count && q.first < s0 && s0 + 4 < q.next) {
       // the four slots lie inside one span, none of them its first or its extra slot
@@ -287,7 +272,7 @@ __global__ __launch_bounds__(TILE_T) void k_depth_apply(int32_t *slots, uint64_t
         d += v[r][e];
         out[e] = d;
         if (first + e >= count) continue;
-        slot_span_to(q, off, n_spans, s);
+        q.span_to(off, n_spans, s);
         if (s + 1 == q.next) continue;  // the extra slot
         n_heads += s == q.first || v[r][e] != 0;
         mx = d > mx ? d : mx;
@@ -368,7 +353,7 @@ __global__ __launch_bounds__(TILE_T) void k_depth_runs(const int32_t *depth, uin
     if (lane == 0) prev[r] = t0 + first && first < count ? (uint32_t)depth[t0 + first - 1] : 0u;
     hd[r] = 0;
     if (first < count) {
-      SlotSpan q = slot_span(off, n_spans, t0 + first);
+      SpanCursor q = SpanCursor::span_at(off, n_spans, t0 + first);
       uint32_t p = prev[r];
       if (first + 4 <= count && q.first < t0 + first && t0 + first + 4 < q.next) {
         // inside one span, none of the four its first or its extra slot: a head is a change of depth
@@ -382,7 +367,7 @@ __global__ __launch_bounds__(TILE_T) void k_depth_runs(const int32_t *depth, uin
         for (uint32_t e = 0; e < 4; ++e) {
           const uint64_t s = t0 + first + e;
           if (first + e < count) {
-            slot_span_to(q, off, n_spans, s);
+            q.span_to(off, n_spans, s);
             if (s + 1 != q.next && (s == q.first || v[r][e] != p)) hd[r] |= 1u << e;
           }
           p = v[r][e];
@@ -398,13 +383,13 @@ __global__ __launch_bounds__(TILE_T) void k_depth_runs(const int32_t *depth, uin
   for (uint32_t r = 0; r < TILE_ROUNDS; ++r) {
     const uint32_t first = tile_slot(wave, r, lane);
     if (first >= count) continue;
-    SlotSpan q = slot_span(off, n_spans, t0 + first);
+    SpanCursor q = SpanCursor::span_at(off, n_spans, t0 + first);
     uint64_t rank = hb + x[r];  // heads before the slot
 #pragma unroll
     for (uint32_t e = 0; e < 4; ++e) {
       const uint64_t s = t0 + first + e;
       if (first + e >= count) continue;
-      slot_span_to(q, off, n_spans, s);
+      q.span_to(off, n_spans, s);
       const int64_t at = sp[q.k].beg + (int64_t)(s - q.first);
       if (s + 1 == q.next) {  // the extra slot: at == the span's end
         if (rank && rank - 1 < n_runs) runs[rank - 1].end = at;
@@ -424,13 +409,13 @@ __global__ __launch_bounds__(TILE_T) void k_depth_runs(const int32_t *depth, uin
 }  // namespace
 
 // The launchers, in the order the entry points below use them.  launch_depth_events: off has
-// n_spans + 1 entries, off[n_spans] == S.  The finish: tile sums (depth_tiles(S) words), their
-// exclusive scan as base, launch_depth_apply (heads: depth_tiles(S) + 1 words, the caller zeroes
-// the last), the scan of heads as hbase, launch_depth_runs.
+// n_spans + 1 entries, off[n_spans] == S (a SpanTable's d_off, sbh_host.h).  The finish: tile sums
+// (depth_tiles(S) words), their exclusive scan as base, launch_depth_apply (heads: depth_tiles(S) + 1
+// words, the caller zeroes the last), the scan of heads as hbase, launch_depth_runs.
 static uint64_t depth_tiles(uint64_t S) { return (S + DEPTH_TILE - 1) / DEPTH_TILE; }
 
-// keep: ceil(n / 64) words; acc: ctr::DEPTH_BAD .. DEPTH_UNPLACED (preset ~0, ~0, 0, 0).  F's row
-// ranges are device memory.
+// keep: ceil(n / 64) words; acc: the head at ctr::DEPTH_BAD (preset ~0, ~0, 0, 0).  F's row ranges
+// are device memory.
 static hipError_t launch_depth_check(const uint8_t *U, const uint64_t *pos, uint64_t n, uint64_t total, const sbh_bam::Filter &F,
                                      int32_t n_ref, uint64_t *keep, unsigned long long *acc, hipStream_t st) {
   if (!n) return hipSuccess;
@@ -492,46 +477,29 @@ int sbh_depth_create(sbh_ctx *ctx, const sbh_depth_span *spans, uint32_t n_spans
   if (!ctx || !out) return SBH_E_ARG;
   *out = nullptr;
   if (flags & ~SBH_DEPTH_DEL) return fail(ctx, SBH_E_ARG, "depth: unknown flag bits 0x%x", flags & ~SBH_DEPTH_DEL);
-  if (!sbh_dep::spans_ok(depth_spans(spans), n_spans, n_ref))
-    return fail(ctx, SBH_E_ARG,
-                "depth spans: at least one, ref_id in [0, n_ref) strictly ascending, 0 <= beg < end <= 2^31 - 1");
-  int rc = set_device(ctx);
+  int rc = spans_refused(ctx, "depth", spans, n_spans, n_ref);
+  if (rc) return rc;
+  rc = set_device(ctx);
   if (rc) return rc;
   sbh_depth *d = new sbh_depth();
   d->ctx = ctx;
   d->n_ref = n_ref;
   d->flags = flags;
-  d->spans.assign(spans, spans + n_spans);
-  d->off.assign(n_spans + 1, 0);
-  for (uint32_t k = 0; k < n_spans; ++k) d->off[k + 1] = d->off[k] + (uint64_t)(spans[k].end - spans[k].beg) + 1;
-  d->S = d->off[n_spans];
-  const uint64_t nt = depth_tiles(d->S);
-  hipError_t e = nt < 0x7fffffffull ? hipSuccess : hipErrorOutOfMemory;  // (one workgroup per tile)
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&d->st, hipStreamNonBlocking);
-  const bool have_stream = e == hipSuccess;
-  if (e == hipSuccess) e = d->slots.ensure(d->S);
-  if (e == hipSuccess) e = d->d_spans.ensure(n_spans);
-  if (e == hipSuccess) e = d->d_off.ensure(n_spans + 1);
-  for (auto *b : {&d->tsum, &d->tbase, &d->heads, &d->hbase})
-    if (e == hipSuccess) e = b->ensure(nt + 1);
-  if (e == hipSuccess) e = d->tstat.ensure(3 * nt);
-  if (e == hipSuccess) e = d->tmp.ensure(scan_tmp_words(nt + 1));
-  if (e == hipSuccess) e = d->acc.ensure(3);
-  if (e == hipSuccess) e = hipMemcpyAsync(d->d_spans.p, spans, n_spans * sizeof(sbh_depth_span), hipMemcpyHostToDevice, d->st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d->d_off.p, d->off.data(), 8 * (n_spans + 1), hipMemcpyHostToDevice, d->st);
-  if (e == hipSuccess) e = hipMemsetAsync(d->slots.p, 0, 4 * d->S, d->st);
-  if (e == hipSuccess) e = hipStreamSynchronize(d->st);  // (the copies' sources are the caller's and this frame's)
-  if (e != hipSuccess) {
-    const uint64_t S = d->S;
-    delete d;
-    if (e == hipErrorOutOfMemory || !have_stream) {
-      (void)hipGetLastError();
-      return fail(ctx, SBH_E_NOMEM, "depth: no memory for %llu slots (4 bytes each)", (unsigned long long)S);
-    }
-    return fail(ctx, SBH_E_HIP, "depth create: %s", hipGetErrorString(e));
-  }
-  *out = d;
-  return SBH_OK;
+  d->assign(spans, n_spans, 1);
+  char nomem[80];
+  std::snprintf(nomem, sizeof nomem, "depth: no memory for %llu slots (4 bytes each)", (unsigned long long)d->S);
+  return accum_open(d, out, nomem, "depth create", [d] {
+    const uint64_t nt = depth_tiles(d->S);
+    hipError_t e = d->upload(nt, d->st);
+    if (e == hipSuccess) e = d->slots.ensure(d->S);
+    for (auto *b : {&d->tsum, &d->tbase, &d->heads, &d->hbase})
+      if (e == hipSuccess) e = b->ensure(nt + 1);
+    if (e == hipSuccess) e = d->tstat.ensure(3 * nt);
+    if (e == hipSuccess) e = d->tmp.ensure(scan_tmp_words(nt + 1));
+    if (e == hipSuccess) e = d->acc.ensure(3);
+    if (e == hipSuccess) e = hipMemsetAsync(d->slots.p, 0, 4 * d->S, d->st);
+    return e;
+  });
 }
 
 int sbh_depth_destroy(sbh_depth *d) {
@@ -541,11 +509,8 @@ int sbh_depth_destroy(sbh_depth *d) {
 
 int sbh_depth_reset(sbh_depth *d) {
   if (!d) return SBH_E_ARG;
-  sbh_ctx *ctx = d->ctx;
-  int rc = set_device(ctx);
+  int rc = d->reset(d->slots.p, 4 * d->S);
   if (rc) return rc;
-  HIPCHK(ctx, hipMemsetAsync(d->slots.p, 0, 4 * d->S, d->st));
-  HIPCHK(ctx, hipStreamSynchronize(d->st));
   d->finished = false;
   d->sz = sbh_depth_sizes{};
   return SBH_OK;
@@ -556,40 +521,31 @@ int sbh_depth_reset(sbh_depth *d) {
 int sbh_records_depth_add(sbh_shard *sh, sbh_depth *d, const sbh_record_filter *filter, sbh_depth_add_result *out) {
   if (!sh || !d || !out) return SBH_E_ARG;
   sbh_ctx *ctx = sh->ctx;
-  if (d->ctx != ctx) return fail(ctx, SBH_E_ARG, "records_depth_add: the shard and the accumulator belong to different contexts");
   auto &R = sh->rec;
-  if (!R.valid) return fail(ctx, SBH_E_STATE, "records_depth_add without a records scan");
-  if (d->finished) return fail(ctx, SBH_E_STATE, "records_depth_add after sbh_depth_finish (sbh_depth_reset reopens)");
+  auto &D = sh->dep;
   sbh_bam::Filter F;
-  int rc = row_filter(ctx, filter, &F);
+  int rc = add_begin(sh, d, "records_depth_add", d->finished ? "after sbh_depth_finish (sbh_depth_reset reopens)" : nullptr,
+                     filter, &F);
   if (rc) return rc;
   const uint64_t n = R.sz.n;
   *out = sbh_depth_add_result{n, 0, 0, 0, 0};
   if (!n) return SBH_OK;
-  rc = set_device(ctx);
-  if (rc) return rc;
   hipStream_t st = sh->st;
-  auto &D = sh->dep;
-  HIPCHK(ctx, D.keep.ensure((n + 63) / 64));
-  HIPCHK(ctx, stage_row_ranges(sh, &F));
   unsigned long long *acc = sh->ctr.p + ctr::DEPTH_BAD;
-  static_assert(ctr::DEPTH_PAST == ctr::DEPTH_BAD + 1 && ctr::DEPTH_KEPT == ctr::DEPTH_BAD + 2 &&
-                    ctr::DEPTH_UNPLACED == ctr::DEPTH_BAD + 3 && ctr::DEPTH_COUNTED == ctr::DEPTH_BAD + 4 &&
-                    ctr::DEPTH_COV == ctr::DEPTH_BAD + 5,
-                "two memsets, one copy each way");
-  HIPCHK(ctx, hipMemsetAsync(acc, 0xff, 16, st));
-  HIPCHK(ctx, hipMemsetAsync(acc + 2, 0, 32, st));
-  HIPCHK(ctx, launch_depth_check(sh->U.p, R.pos.p, n, sh->utotal, F, d->n_ref, D.keep.p, acc, st));
-  HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::DEPTH_BAD, acc, 32, hipMemcpyDeviceToHost, st));
-  HIPCHK(ctx, hipStreamSynchronize(st));
-  rc = rows_verdict(sh, sh->h_ctr[ctr::DEPTH_BAD], sh->h_ctr[ctr::DEPTH_PAST], ", or its CIGAR or reference is out of range");
+  const AddTrip trip{sh, acc, ctr::DEPTH_BAD};
+  rc = trip.open(&F, &D.keep, ctr::DEPTH_END - ctr::DEPTH_BAD - ctr::ADD_A);
   if (rc) return rc;
-  out->n_kept = sh->h_ctr[ctr::DEPTH_KEPT];
-  out->n_unplaced = sh->h_ctr[ctr::DEPTH_UNPLACED];
+  HIPCHK(ctx, launch_depth_check(sh->U.p, R.pos.p, n, sh->utotal, F, d->n_ref, D.keep.p, acc, st));
+  rc = trip.verdict(", or its CIGAR or reference is out of range");
+  if (rc) return rc;
+  out->n_kept = trip.a();
+  out->n_unplaced = trip.b();
   if (out->n_kept > out->n_unplaced) {
+    static_assert(ctr::DEPTH_COV == ctr::DEPTH_COUNTED + 1, "one copy");
+    unsigned long long *ev = sh->ctr.p + ctr::DEPTH_COUNTED;
     HIPCHK(ctx, launch_depth_events(sh->U.p, R.pos.p, n, D.keep.p, d->d_spans.p, d->d_off.p, (uint32_t)d->spans.size(),
-                                    d->flags, d->slots.p, d->S, acc + 4, st));
-    HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::DEPTH_COUNTED, acc + 4, 16, hipMemcpyDeviceToHost, st));
+                                    d->flags, d->slots.p, d->S, ev, st));
+    HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::DEPTH_COUNTED, ev, 16, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
     out->n_counted = sh->h_ctr[ctr::DEPTH_COUNTED];
     out->cov_bases = sh->h_ctr[ctr::DEPTH_COV];
@@ -635,10 +591,9 @@ int sbh_depth_fetch(sbh_depth *d, uint32_t span, uint64_t from, uint64_t n, uint
   if (!d || (n && !depth)) return SBH_E_ARG;
   sbh_ctx *ctx = d->ctx;
   if (!d->finished) return fail(ctx, SBH_E_STATE, "sbh_depth_fetch before sbh_depth_finish");
-  if (span >= d->spans.size()) return fail(ctx, SBH_E_ARG, "sbh_depth_fetch: span %u of %zu", span, d->spans.size());
-  const uint64_t len = (uint64_t)(d->spans[span].end - d->spans[span].beg);
-  if (from > len || n > len - from) return fail(ctx, SBH_E_ARG, "sbh_depth_fetch past the span");
-  int rc = set_device(ctx);
+  int rc = d->range(ctx, "sbh_depth_fetch", span, from, n);
+  if (rc) return rc;
+  rc = set_device(ctx);
   if (rc) return rc;
   if (n) HIPCHK(ctx, hipMemcpyAsync(depth, d->slots.p + d->off[span] + from, 4 * n, hipMemcpyDeviceToHost, d->st));
   HIPCHK(ctx, hipStreamSynchronize(d->st));
@@ -676,8 +631,7 @@ int sbh_depth_add_host(const uint8_t *flat, uint64_t flat_size, const uint64_t *
   uint64_t bad = sbh_bam::NO_ROW;
   const int rc = sbh_dep::add_host(flat, flat_size, starts, n, F, depth_spans(spans), n_spans, n_ref, flags, slots,
                                      reinterpret_cast<sbh_dep::AddResult *>(out), &bad);
-  if (bad_row) *bad_row = bad;
-  return rc == 0 ? SBH_OK : SBH_E_BAD_RECORD;
+  return host_rows_status(rc, bad, bad_row);
 }
 
 int sbh_depth_finish_host(int32_t *slots, const sbh_depth_span *spans, uint32_t n_spans, sbh_depth_run *runs,

@@ -83,18 +83,6 @@ SBH_HD inline bool ops_ok(const uint8_t *r) {
   return true;
 }
 
-// the span holding slot s: the last k with off[k] <= s (off: n + 1 ascending entries, off[0] == 0,
-// s < off[n])
-SBH_HD inline uint32_t span_of_slot(const uint64_t *off, uint32_t n, uint64_t s) {
-  uint32_t lo = 0, hi = n;  // first k with off[k] > s, in [1, n]
-  while (lo < hi) {
-    const uint32_t m = (lo + hi) >> 1;
-    if (off[m] <= s) lo = m + 1;
-    else hi = m;
-  }
-  return lo ? lo - 1 : 0;
-}
-
 }  // namespace sbh_dep
 
 // ---- the host side (plain host functions under hipcc too) --------------------------------------
@@ -134,20 +122,10 @@ inline uint64_t slots_of(const Span *sp, uint32_t n) {
 inline int add_host(const uint8_t *flat, uint64_t flat_size, const uint64_t *starts, uint64_t n, const sbh_bam::Filter &F,
                     const Span *sp, uint32_t n_spans, int32_t n_ref, uint32_t flags, int32_t *slots, AddResult *res,
                     uint64_t *bad_row) {
-  *bad_row = sbh_bam::NO_ROW;
   *res = AddResult{n, 0, 0, 0, 0};
-  uint64_t len = 0;
-  for (uint64_t i = 0; i < n; ++i) {
-    bool ok = sbh_bam::row_check(flat, flat_size, starts[i], &len) == sbh_bam::ROW_OK;
-    if (ok && sbh_bam::row_keep(flat + starts[i], i, F)) {
-      const uint8_t *r = flat + starts[i];
-      ok = (int32_t)sbh_bam::ld32(r + 4) < n_ref && ops_ok(r);
-    }
-    if (!ok) {
-      *bad_row = i;
-      return 1;
-    }
-  }
+  *bad_row = sbh_bam::first_bad_row(flat, flat_size, starts, n, F,
+                                    [n_ref](const uint8_t *r) { return (int32_t)sbh_bam::ld32(r + 4) < n_ref && ops_ok(r); });
+  if (*bad_row != sbh_bam::NO_ROW) return 1;
   for (uint64_t i = 0; i < n; ++i) {
     const uint8_t *r = flat + starts[i];
     if (!sbh_bam::row_keep(r, i, F)) continue;

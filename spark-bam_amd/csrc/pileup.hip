@@ -57,10 +57,6 @@ __device__ __forceinline__ uint32_t lane_u32(uint32_t v, int src) { return (uint
 __device__ __forceinline__ uint64_t lane_u64(uint64_t v, int src) {
   return (uint64_t)lane_u32((uint32_t)v, src) | (uint64_t)lane_u32((uint32_t)(v >> 32), src) << 32;
 }
-// 64 values below 2^28: the low 16 bits sum below 2^22, the rest below 2^18
-__device__ __forceinline__ uint64_t wave_incl_scan64(uint32_t v) {
-  return (uint64_t)wave_incl_scan(v & 0xffffu) + ((uint64_t)wave_incl_scan(v >> 16) << 16);
-}
 
 // keep: one u64 per 64 rows, every word below ceil(n / 64) written.  acc: bad, past (preset ~0),
 // n_kept, n_unplaced (preset 0).
@@ -274,20 +270,7 @@ __global__ __launch_bounds__(256) void k_pile_events(const uint8_t *__restrict__
 }
 
 // ---- the tile kernels ---------------------------------------------------------------------------
-// What a lane needs about the span of a position: s is a span's first when s == off[k], its last
-// when s + 1 == off[k + 1].  off has n_spans + 1 entries and s < S == off[n_spans], so
-// span_of_pos' k is below n_spans and off[k + 1] exists.
-struct PosSpan {
-  uint32_t k;
-  uint64_t first, next;  // off[k], off[k + 1]
-};
-__device__ __forceinline__ PosSpan pos_span(const uint64_t *off, uint32_t n_spans, uint64_t s) {
-  const uint32_t k = sbh_pile::span_of_pos(off, n_spans, s);
-  return PosSpan{k, off[k], off[k + 1]};
-}
-__device__ __forceinline__ void pos_span_to(PosSpan &q, const uint64_t *off, uint32_t n_spans, uint64_t s) {
-  while (s >= q.next && q.k + 1 < n_spans) ++q.k, q.first = q.next, q.next = off[q.k + 1];
-}
+// (what a lane needs about the span of a position is a SpanCursor, sbh_internal.h)
 __device__ __forceinline__ void load_pos(const uint4 *counts, uint64_t s, uint32_t c[NCH]) {
   const uint4 a = counts[2 * s], b = counts[2 * s + 1];
   c[0] = a.x, c[1] = a.y, c[2] = a.z, c[3] = a.w, c[4] = b.x, c[5] = b.y, c[6] = b.z, c[7] = b.w;
@@ -338,12 +321,12 @@ __global__ __launch_bounds__(TILE_T) void k_pile_calls(const uint4 *__restrict__
   uint64_t nh = 0;
   const uint64_t s0 = t0 + 4 * threadIdx.x;
   if (s0 < S) {
-    PosSpan q = pos_span(off, n_spans, s0);
+    SpanCursor q = SpanCursor::span_at(off, n_spans, s0);
 #pragma unroll
     for (uint32_t e = 0; e < 4; ++e) {
       const uint32_t cb = (word >> (8 * e)) & 0xffu;
       if (s0 + e < S) {
-        pos_span_to(q, off, n_spans, s0 + e);
+        q.span_to(off, n_spans, s0 + e);
         nh += cb && (s0 + e == q.first || !prev);
       }
       prev = cb;
@@ -413,13 +396,13 @@ __global__ __launch_bounds__(TILE_T) void k_pile_intervals(const uint8_t *__rest
                                                    : (blockIdx.x + 1 < gridDim.x ? calls[t0 + PILE_TILE] : 0u);
   uint32_t hd = 0, tl = 0;
   if (s0 < S) {
-    PosSpan q = pos_span(off, n_spans, s0);
+    SpanCursor q = SpanCursor::span_at(off, n_spans, s0);
     uint32_t prev = before;
 #pragma unroll
     for (uint32_t e = 0; e < 4; ++e) {
       const uint32_t cb = (word >> (8 * e)) & 0xffu, nb = e < 3 ? (word >> (8 * e + 8)) & 0xffu : behind;
       if (s0 + e < S && cb) {
-        pos_span_to(q, off, n_spans, s0 + e);
+        q.span_to(off, n_spans, s0 + e);
         if (s0 + e == q.first || !prev) hd |= 1u << e;
         if (s0 + e + 1 == q.next || !nb) tl |= 1u << e;
       }
@@ -433,11 +416,11 @@ __global__ __launch_bounds__(TILE_T) void k_pile_intervals(const uint8_t *__rest
   for (uint32_t w = 0; w < wave; ++w) before_waves += s_wave[w];
   uint64_t rank = hbase[blockIdx.x] + before_waves + incl - nh;  // heads before the lane's positions
   if (hd | tl) {
-    PosSpan q = pos_span(off, n_spans, s0);
+    SpanCursor q = SpanCursor::span_at(off, n_spans, s0);
 #pragma unroll
     for (uint32_t e = 0; e < 4; ++e) {
       if (!(((hd | tl) >> e) & 1u)) continue;
-      pos_span_to(q, off, n_spans, s0 + e);
+      q.span_to(off, n_spans, s0 + e);
       const int64_t at = sp[q.k].beg + (int64_t)(s0 + e - q.first);
       if ((hd >> e) & 1u) {
         if (rank < n_iv) {
@@ -475,47 +458,30 @@ int sbh_pileup_create(sbh_ctx *ctx, const sbh_depth_span *spans, uint32_t n_span
   if (!ctx || !out) return SBH_E_ARG;
   *out = nullptr;
   if (min_baseq < 0 || min_baseq > 255) return fail(ctx, SBH_E_ARG, "pileup: min_baseq %d outside [0, 255]", min_baseq);
-  if (!sbh_dep::spans_ok(pile_spans(spans), n_spans, n_ref))
-    return fail(ctx, SBH_E_ARG,
-                "pileup spans: at least one, ref_id in [0, n_ref) strictly ascending, 0 <= beg < end <= 2^31 - 1");
-  int rc = set_device(ctx);
+  int rc = spans_refused(ctx, "pileup", spans, n_spans, n_ref);
+  if (rc) return rc;
+  rc = set_device(ctx);
   if (rc) return rc;
   sbh_pileup *p = new sbh_pileup();
   p->ctx = ctx;
   p->n_ref = n_ref;
   p->min_baseq = (uint32_t)min_baseq;
-  p->spans.assign(spans, spans + n_spans);
-  p->off.assign(n_spans + 1, 0);
-  for (uint32_t k = 0; k < n_spans; ++k) p->off[k + 1] = p->off[k] + (uint64_t)(spans[k].end - spans[k].beg);
-  p->S = p->off[n_spans];
-  const uint64_t nt = pile_tiles(p->S);
-  hipError_t e = nt < 0x7fffffffull ? hipSuccess : hipErrorOutOfMemory;  // (one workgroup per tile)
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&p->st, hipStreamNonBlocking);
-  const bool have_stream = e == hipSuccess;
-  if (e == hipSuccess) e = p->counts.ensure(2 * p->S);
-  if (e == hipSuccess) e = p->calls.ensure(nt * PILE_TILE);
-  if (e == hipSuccess) e = p->d_spans.ensure(n_spans);
-  if (e == hipSuccess) e = p->d_off.ensure(n_spans + 1);
-  if (e == hipSuccess) e = p->heads.ensure(nt + 1);
-  if (e == hipSuccess) e = p->hbase.ensure(nt + 1);
-  if (e == hipSuccess) e = p->tstat.ensure(TSTAT * nt);
-  if (e == hipSuccess) e = p->tmp.ensure(scan_tmp_words(nt + 1));
-  if (e == hipSuccess) e = p->acc.ensure(TSTAT);
-  if (e == hipSuccess) e = hipMemcpyAsync(p->d_spans.p, spans, n_spans * sizeof(sbh_depth_span), hipMemcpyHostToDevice, p->st);
-  if (e == hipSuccess) e = hipMemcpyAsync(p->d_off.p, p->off.data(), 8 * (n_spans + 1), hipMemcpyHostToDevice, p->st);
-  if (e == hipSuccess) e = hipMemsetAsync(p->counts.p, 0, 32 * p->S, p->st);
-  if (e == hipSuccess) e = hipStreamSynchronize(p->st);  // (the copies' sources are the caller's and this frame's)
-  if (e != hipSuccess) {
-    const uint64_t S = p->S;
-    delete p;
-    if (e == hipErrorOutOfMemory || !have_stream) {
-      (void)hipGetLastError();
-      return fail(ctx, SBH_E_NOMEM, "pileup: no memory for %llu positions (33 bytes each)", (unsigned long long)S);
-    }
-    return fail(ctx, SBH_E_HIP, "pileup create: %s", hipGetErrorString(e));
-  }
-  *out = p;
-  return SBH_OK;
+  p->assign(spans, n_spans, 0);
+  char nomem[80];
+  std::snprintf(nomem, sizeof nomem, "pileup: no memory for %llu positions (33 bytes each)", (unsigned long long)p->S);
+  return accum_open(p, out, nomem, "pileup create", [p] {
+    const uint64_t nt = pile_tiles(p->S);
+    hipError_t e = p->upload(nt, p->st);
+    if (e == hipSuccess) e = p->counts.ensure(2 * p->S);
+    if (e == hipSuccess) e = p->calls.ensure(nt * PILE_TILE);
+    if (e == hipSuccess) e = p->heads.ensure(nt + 1);
+    if (e == hipSuccess) e = p->hbase.ensure(nt + 1);
+    if (e == hipSuccess) e = p->tstat.ensure(TSTAT * nt);
+    if (e == hipSuccess) e = p->tmp.ensure(scan_tmp_words(nt + 1));
+    if (e == hipSuccess) e = p->acc.ensure(TSTAT);
+    if (e == hipSuccess) e = hipMemsetAsync(p->counts.p, 0, 32 * p->S, p->st);
+    return e;
+  });
 }
 
 int sbh_pileup_destroy(sbh_pileup *p) {
@@ -525,11 +491,8 @@ int sbh_pileup_destroy(sbh_pileup *p) {
 
 int sbh_pileup_reset(sbh_pileup *p) {
   if (!p) return SBH_E_ARG;
-  sbh_ctx *ctx = p->ctx;
-  int rc = set_device(ctx);
+  int rc = p->reset(p->counts.p, 32 * p->S);
   if (rc) return rc;
-  HIPCHK(ctx, hipMemsetAsync(p->counts.p, 0, 32 * p->S, p->st));
-  HIPCHK(ctx, hipStreamSynchronize(p->st));
   p->finished = false;
   p->sz = sbh_pileup_sizes{};
   return SBH_OK;
@@ -540,46 +503,36 @@ int sbh_pileup_reset(sbh_pileup *p) {
 int sbh_records_pileup_add(sbh_shard *sh, sbh_pileup *p, const sbh_record_filter *filter, sbh_pileup_add_result *out) {
   if (!sh || !p || !out) return SBH_E_ARG;
   sbh_ctx *ctx = sh->ctx;
-  if (p->ctx != ctx) return fail(ctx, SBH_E_ARG, "records_pileup_add: the shard and the accumulator belong to different contexts");
   auto &R = sh->rec;
-  if (!R.valid) return fail(ctx, SBH_E_STATE, "records_pileup_add without a records scan");
-  if (p->finished) return fail(ctx, SBH_E_STATE, "records_pileup_add after sbh_pileup_finish (sbh_pileup_reset reopens)");
+  auto &D = sh->dep;  // (the keep bits of the last depth or pileup add)
   sbh_bam::Filter F;
-  int rc = row_filter(ctx, filter, &F);
+  int rc = add_begin(sh, p, "records_pileup_add", p->finished ? "after sbh_pileup_finish (sbh_pileup_reset reopens)" : nullptr,
+                     filter, &F);
   if (rc) return rc;
   const uint64_t n = R.sz.n;
   *out = sbh_pileup_add_result{};
   out->n = n;
   if (!n) return SBH_OK;
-  rc = set_device(ctx);
-  if (rc) return rc;
   hipStream_t st = sh->st;
-  auto &D = sh->dep;  // (the keep bits of the last depth or pileup add)
-  HIPCHK(ctx, D.keep.ensure((n + 63) / 64));
-  HIPCHK(ctx, stage_row_ranges(sh, &F));
   unsigned long long *acc = sh->ctr.p + ctr::PILE_BAD;
-  static_assert(ctr::PILE_PAST == ctr::PILE_BAD + 1 && ctr::PILE_KEPT == ctr::PILE_BAD + 2 &&
-                    ctr::PILE_UNPLACED == ctr::PILE_BAD + 3 && ctr::PILE_COUNTED == ctr::PILE_BAD + 4 &&
-                    ctr::PILE_TOTALS == ctr::PILE_BAD + 5 && ctr::PILE_END == ctr::PILE_TOTALS + NCH,
-                "two memsets, one copy each way");
-  HIPCHK(ctx, hipMemsetAsync(acc, 0xff, 16, st));
-  HIPCHK(ctx, hipMemsetAsync(acc + 2, 0, 8 * (ctr::PILE_END - ctr::PILE_KEPT), st));
+  const AddTrip trip{sh, acc, ctr::PILE_BAD};
+  rc = trip.open(&F, &D.keep, ctr::PILE_END - ctr::PILE_BAD - ctr::ADD_A);
+  if (rc) return rc;
   hipLaunchKernelGGL(k_pile_check, dim3(rows_grid(n)), dim3(256), 0, st, sh->U.p, R.pos.p, n, sh->utotal, F, p->n_ref,
                      D.keep.p, acc);
   HIPCHK(ctx, hipGetLastError());
-  HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::PILE_BAD, acc, 32, hipMemcpyDeviceToHost, st));
-  HIPCHK(ctx, hipStreamSynchronize(st));
-  rc = rows_verdict(sh, sh->h_ctr[ctr::PILE_BAD], sh->h_ctr[ctr::PILE_PAST],
-                    ", or its CIGAR, query length or reference is out of range");
+  rc = trip.verdict(", or its CIGAR, query length or reference is out of range");
   if (rc) return rc;
-  out->n_kept = sh->h_ctr[ctr::PILE_KEPT];
-  out->n_unplaced = sh->h_ctr[ctr::PILE_UNPLACED];
+  out->n_kept = trip.a();
+  out->n_unplaced = trip.b();
   if (out->n_kept > out->n_unplaced) {
+    static_assert(ctr::PILE_TOTALS == ctr::PILE_COUNTED + 1 && ctr::PILE_END == ctr::PILE_TOTALS + NCH, "one copy");
+    unsigned long long *ev = sh->ctr.p + ctr::PILE_COUNTED;
     hipLaunchKernelGGL(k_pile_events, dim3(rows_grid(n)), dim3(256), 0, st, sh->U.p, R.pos.p, n, D.keep.p,
                        reinterpret_cast<const Span *>(p->d_spans.p), p->d_off.p, (uint32_t)p->spans.size(), p->min_baseq,
-                       reinterpret_cast<uint32_t *>(p->counts.p), p->S, acc + 4);
+                       reinterpret_cast<uint32_t *>(p->counts.p), p->S, ev);
     HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::PILE_COUNTED, acc + 4, 8 * (1 + NCH), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::PILE_COUNTED, ev, 8 * (1 + NCH), hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
     out->n_counted = sh->h_ctr[ctr::PILE_COUNTED];
     for (uint32_t k = 0; k < NCH; ++k) out->totals[k] = sh->h_ctr[ctr::PILE_TOTALS + k];
@@ -630,18 +583,10 @@ int sbh_pileup_finish(sbh_pileup *p, uint32_t min_depth, uint32_t call_pct, sbh_
   return SBH_OK;
 }
 
-// span, from, n against the span's length: 0 or the error
-static int pile_range(sbh_pileup *p, const char *what, uint32_t span, uint64_t from, uint64_t n) {
-  if (span >= p->spans.size()) return fail(p->ctx, SBH_E_ARG, "%s: span %u of %zu", what, span, p->spans.size());
-  const uint64_t len = (uint64_t)(p->spans[span].end - p->spans[span].beg);
-  if (from > len || n > len - from) return fail(p->ctx, SBH_E_ARG, "%s past the span", what);
-  return SBH_OK;
-}
-
 int sbh_pileup_counts_fetch(sbh_pileup *p, uint32_t span, uint64_t from, uint64_t n, uint32_t *out) {
   if (!p || (n && !out)) return SBH_E_ARG;
   sbh_ctx *ctx = p->ctx;
-  int rc = pile_range(p, "sbh_pileup_counts_fetch", span, from, n);
+  int rc = p->range(ctx, "sbh_pileup_counts_fetch", span, from, n);
   if (rc) return rc;
   rc = set_device(ctx);
   if (rc) return rc;
@@ -655,7 +600,7 @@ int sbh_pileup_calls_fetch(sbh_pileup *p, uint32_t span, uint64_t from, uint64_t
   if (!p || (n && !out)) return SBH_E_ARG;
   sbh_ctx *ctx = p->ctx;
   if (!p->finished) return fail(ctx, SBH_E_STATE, "sbh_pileup_calls_fetch before sbh_pileup_finish");
-  int rc = pile_range(p, "sbh_pileup_calls_fetch", span, from, n);
+  int rc = p->range(ctx, "sbh_pileup_calls_fetch", span, from, n);
   if (rc) return rc;
   rc = set_device(ctx);
   if (rc) return rc;
@@ -701,8 +646,7 @@ int sbh_pileup_add_host(const uint8_t *flat, uint64_t flat_size, const uint64_t 
   uint64_t bad = sbh_bam::NO_ROW;
   const int rc = sbh_pile::add_host(flat, flat_size, starts, n, F, pile_spans(spans), n_spans, n_ref, (uint32_t)min_baseq,
                                     counts, reinterpret_cast<sbh_pile::AddResult *>(out), &bad);
-  if (bad_row) *bad_row = bad;
-  return rc == 0 ? SBH_OK : SBH_E_BAD_RECORD;
+  return host_rows_status(rc, bad, bad_row);
 }
 
 int sbh_pileup_finish_host(const uint32_t *counts, const sbh_depth_span *spans, uint32_t n_spans, uint32_t min_depth,

@@ -104,11 +104,6 @@ SBH_HD inline uint64_t depth_of(const uint32_t c[NCH]) {
 }
 SBH_HD inline bool is_called(uint8_t call) { return call != 0 && call != 'N'; }
 
-// the span holding position s: the last k with off[k] <= s (off: n + 1 ascending entries, s < off[n])
-SBH_HD inline uint32_t span_of_pos(const uint64_t *off, uint32_t n, uint64_t s) {
-  return sbh_dep::span_of_slot(off, n, s);
-}
-
 }  // namespace sbh_pile
 
 // ---- the host side (plain host functions under hipcc too) --------------------------------------
@@ -132,20 +127,10 @@ inline uint64_t positions_of(const Span *sp, uint32_t n) {
 inline int add_host(const uint8_t *flat, uint64_t flat_size, const uint64_t *starts, uint64_t n, const sbh_bam::Filter &F,
                     const Span *sp, uint32_t n_spans, int32_t n_ref, uint32_t min_baseq, uint32_t *counts, AddResult *res,
                     uint64_t *bad_row) {
-  *bad_row = sbh_bam::NO_ROW;
   *res = AddResult{n, 0, 0, 0, {0, 0, 0, 0, 0, 0, 0, 0}};
-  uint64_t len = 0;
-  for (uint64_t i = 0; i < n; ++i) {
-    bool ok = sbh_bam::row_check(flat, flat_size, starts[i], &len) == sbh_bam::ROW_OK;
-    if (ok && sbh_bam::row_keep(flat + starts[i], i, F)) {
-      const uint8_t *r = flat + starts[i];
-      ok = (int32_t)sbh_bam::ld32(r + 4) < n_ref && walk_ok(r);
-    }
-    if (!ok) {
-      *bad_row = i;
-      return 1;
-    }
-  }
+  *bad_row = sbh_bam::first_bad_row(flat, flat_size, starts, n, F,
+                                    [n_ref](const uint8_t *r) { return (int32_t)sbh_bam::ld32(r + 4) < n_ref && walk_ok(r); });
+  if (*bad_row != sbh_bam::NO_ROW) return 1;
   for (uint64_t i = 0; i < n; ++i) {
     const uint8_t *r = flat + starts[i];
     if (!sbh_bam::row_keep(r, i, F)) continue;

@@ -1,14 +1,16 @@
 // sbh_host.h -- the host side's private header: the context, the shard and the other structs
 // behind the opaque handles of include/sparkbam.h, the error helpers, and the host helpers that
 // one file's entry points (sbh_api.hip, api_check.hip, api_records.hip, and the output stages' calls
-// behind the kernels of bai.hip, sam.hip, bam_gather.hip, depth.hip, pileup.hip, tally.hip, fastq.hip, zdeflate.hip) borrow from another's.  Launchers are
-// declared in sbh_internal.h; nothing here is seen by device code.
+// behind the kernels of bai.hip, sam.hip, bam_gather.hip, depth.hip, pileup.hip, tally.hip, stats.hip,
+// fastq.hip, zdeflate.hip) borrow from another's.  Launchers are declared in sbh_internal.h; nothing
+// here is seen by device code.
 //
 // The stages that run over the rows of the last records scan under an sbh_record_filter
 // (bam_gather.hip, depth.hip, pileup.hip, tally.hip, fastq.hip, stats.hip) share one frame, declared at the end
 // of this header and defined in bam_gather.hip: row_filter (the filter and its one message),
 // stage_row_ranges (the device copy of the row ranges, sbh_shard::row_ranges) and rows_verdict (bad
-// row, past row -> SBH_OK / SBH_E_NEED_HALO / SBH_E_BAD_RECORD); the accumulators share sbh::Accum.
+// row, past row -> SBH_OK / SBH_E_NEED_HALO / SBH_E_BAD_RECORD).  The four accumulators share sbh::Accum
+// and, behind the row frame, the frame of accum.hip: accum_open, Accum::reset, add_begin, AddTrip, SpanTable.
 #pragma once
 #include <algorithm>
 #include <cstdio>
@@ -346,6 +348,7 @@ namespace sbh {
 struct Accum {
   sbh_ctx *ctx = nullptr;
   hipStream_t st = nullptr;
+  int reset(void *p, uint64_t bytes);  // sbh_*_reset: `bytes` at p zeroed on st, st synchronised (accum.hip)
   void drain() {
     if (ctx) (void)hipSetDevice(ctx->device);
     if (st) {
@@ -355,18 +358,30 @@ struct Accum {
     }
   }
 };
+
+// The spans of a depth or pileup accumulator, host and device (accum.hip).  Span k owns the slots
+// [off[k], off[k + 1]): its end - beg positions and `extra` (depth: 1, pileup: 0) behind them.
+struct SpanTable {
+  std::vector<sbh_depth_span> spans;
+  std::vector<uint64_t> off;  // n_spans + 1: the first slot of each span, then S
+  uint64_t S = 0;
+  DBuf<sbh_depth_span> d_spans;
+  DBuf<uint64_t> d_off;
+  void assign(const sbh_depth_span *sp, uint32_t n_spans, uint32_t extra);  // (spans_refused has judged them)
+  // the device copies, on st (the caller synchronises it); hipErrorOutOfMemory for 2^31 - 1 tiles or
+  // more: the tile kernels run one workgroup per tile
+  hipError_t upload(uint64_t n_tiles, hipStream_t st);
+  // positions [from, from + n) of `span`: SBH_OK, or SBH_E_ARG in the words of `what`, the fetch's name
+  int range(sbh_ctx *ctx, const char *what, uint32_t span, uint64_t from, uint64_t n) const;
+};
 }  // namespace sbh
 
 // A depth accumulator (sbh_depth_create): owned by a context, fed by any number of its shards.
-struct sbh_depth : sbh::Accum {
-  std::vector<sbh_depth_span> spans;
-  std::vector<uint64_t> off;  // n_spans + 1: the first slot of each span, then S
+struct sbh_depth : sbh::Accum, sbh::SpanTable {
   int32_t n_ref = 0;
   uint32_t flags = 0;
-  uint64_t S = 0;
   sbh::DBuf<int32_t> slots;  // S; after finish the depth (u32)
-  sbh::DBuf<sbh_depth_span> d_spans;
-  sbh::DBuf<uint64_t> d_off, tsum, tbase, heads, hbase, tstat, tmp;
+  sbh::DBuf<uint64_t> tsum, tbase, heads, hbase, tstat, tmp;
   sbh::DBuf<unsigned long long> acc;  // max, covered, sum
   sbh::DBuf<sbh_depth_run> runs;
   sbh_depth_sizes sz{};
@@ -376,16 +391,13 @@ struct sbh_depth : sbh::Accum {
 
 // A pileup accumulator (sbh_pileup_create): eight u32 channels per position, owned by a context, fed
 // by any number of its shards.  An add borrows the adding shard's depth scratch (the keep bits).
-struct sbh_pileup : sbh::Accum {
-  std::vector<sbh_depth_span> spans;
-  std::vector<uint64_t> off;  // n_spans + 1: the first position of each span, then S
+struct sbh_pileup : sbh::Accum, sbh::SpanTable {
   int32_t n_ref = 0;
   uint32_t min_baseq = 0;
-  uint64_t S = 0;
   sbh::DBuf<uint4> counts;  // 2 S: position s is counts[2 s], counts[2 s + 1] (A C G T | N DEL INS LOWQ)
   sbh::DBuf<uint8_t> calls;  // S, after finish
-  sbh::DBuf<sbh_depth_span> d_spans, ivals;
-  sbh::DBuf<uint64_t> d_off, heads, hbase, tstat, tmp;
+  sbh::DBuf<sbh_depth_span> ivals;
+  sbh::DBuf<uint64_t> heads, hbase, tstat, tmp;
   sbh::DBuf<unsigned long long> acc;  // the folded tile stats
   sbh_pileup_sizes sz{};
   bool finished = false;
@@ -502,6 +514,58 @@ hipError_t stage_row_ranges(sbh_shard *sh, sbh_bam::Filter *F);
 // row refused (~0: none, SBH_OK), past = the first row refused only because it runs past the stream.
 // `also` ends the SBH_E_BAD_RECORD message with what the stage refuses beyond row_check ("": nothing).
 int rows_verdict(sbh_shard *sh, uint64_t bad, uint64_t past, const char *also);
+// The tail of the four *_add_host: rc 0 or 1 and the bad row, as the core header's add_host gave them.
+inline int host_rows_status(int rc, uint64_t bad, uint64_t *bad_row) {
+  if (bad_row) *bad_row = bad;
+  return rc == 0 ? SBH_OK : SBH_E_BAD_RECORD;
+}
+
+// ---- the accumulators' shared frame (accum.hip) ------------------------------------------------
+// The tail of every sbh_*_create.  a: the new accumulator, its ctx and fields set.  Gives it its stream,
+// runs fill() -- the stage's allocations, copies and memsets on a->st -- and synchronises; *out = a.  A
+// failure deletes a: SBH_E_NOMEM with `nomem`, the whole message, when memory or the stream was not to be
+// had, else SBH_E_HIP "<what>: <HIP's text>".
+template <class A, class Fill>
+int accum_open(A *a, A **out, const char *nomem, const char *what, Fill fill) {
+  sbh_ctx *ctx = a->ctx;
+  hipError_t e = hipStreamCreateWithFlags(&a->st, hipStreamNonBlocking);
+  const bool have_stream = e == hipSuccess;
+  if (e == hipSuccess) e = fill();
+  if (e == hipSuccess) e = hipStreamSynchronize(a->st);
+  if (e == hipSuccess) {
+    *out = a;
+    return SBH_OK;
+  }
+  delete a;
+  if (e == hipErrorOutOfMemory || !have_stream) {
+    (void)hipGetLastError();
+    return fail(ctx, SBH_E_NOMEM, "%s", nomem);
+  }
+  return fail(ctx, SBH_E_HIP, "%s: %s", what, hipGetErrorString(e));
+}
+// SBH_OK, or SBH_E_ARG with the one message of sbh_depth_create ("depth") and sbh_pileup_create ("pileup").
+int spans_refused(sbh_ctx *ctx, const char *stage, const sbh_depth_span *sp, uint32_t n_spans, int32_t n_ref);
+
+// The refusals of every sbh_records_*_add (sh and a are not null) in the words of `name`, the call's, and
+// in this order: the shard of another context, a shard without a records scan, `closed` (null, or what a
+// finished accumulator says behind the name), the filter (row_filter: *F, its row ranges still the
+// caller's).  The caller then presets its result and returns SBH_OK for a scan without rows.
+int add_begin(sbh_shard *sh, const Accum *a, const char *name, const char *closed, const sbh_record_filter *filter,
+              sbh_bam::Filter *F);
+// The one round trip of an add, on the shard's stream.  head: the device words bad, past, a, b
+// (ctr::ADD_BAD ..) and whatever else the stage counts behind them; mirror: where in h_ctr the four land.
+struct AddTrip {
+  sbh_shard *sh;
+  unsigned long long *head;
+  uint32_t mirror;
+  // the device made current, keep (null: none) grown to a bit per row, F's row ranges staged; then two
+  // memsets: bad and past ~0, the `zeroed` words from a on 0
+  int open(sbh_bam::Filter *F, DBuf<uint64_t> *keep, uint64_t zeroed) const;
+  // behind the stage's launches: the head copied back, the stream synchronised, rows_verdict(bad, past, also)
+  int verdict(const char *also) const;
+  uint64_t a() const { return sh->h_ctr[mirror + ctr::ADD_A]; }
+  uint64_t b() const { return sh->h_ctr[mirror + ctr::ADD_B]; }
+};
 
 }  // namespace sbh
 

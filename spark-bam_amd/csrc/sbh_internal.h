@@ -23,6 +23,12 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x) {
   return x;
 }
 
+// The same for 64 values below 2^28, whose sum needs more than 32 bits: two scans, the low 16 bits
+// (which sum below 2^22) and the rest (below 2^18).
+__device__ __forceinline__ uint64_t wave_incl_scan64(uint32_t v) {
+  return (uint64_t)wave_incl_scan(v & 0xffffu) + ((uint64_t)wave_incl_scan(v >> 16) << 16);
+}
+
 // v summed over the 64 lanes of a wave, in every lane
 __device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
   for (int m = 1; m < 64; m <<= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, m);
@@ -59,6 +65,29 @@ struct RowMinima {
   __device__ __forceinline__ void send(unsigned long long *bad_out, unsigned long long *past_out) const {
     if (bad != ~0ull) atomicMin(bad_out, (unsigned long long)bad);
     if (past != ~0ull) atomicMin(past_out, (unsigned long long)past);
+  }
+};
+
+// Where a slot of a span table stands (depth.hip's slots, pileup.hip's positions): span k owns
+// [off[k], off[k + 1]), off has n_spans + 1 ascending entries, off[0] == 0, and s < off[n_spans].  Slot s
+// is its span's first when s == first and its last when s + 1 == next.
+struct SpanCursor {
+  uint32_t k;
+  uint64_t first, next;  // off[k], off[k + 1]
+  // the span holding slot s: the last k with off[k] <= s (below n_spans, so off[k + 1] exists)
+  static __device__ __forceinline__ SpanCursor span_at(const uint64_t *off, uint32_t n_spans, uint64_t s) {
+    uint32_t lo = 0, hi = n_spans;  // first k with off[k] > s, in [1, n_spans]
+    while (lo < hi) {
+      const uint32_t m = (lo + hi) >> 1;
+      if (off[m] <= s) lo = m + 1;
+      else hi = m;
+    }
+    const uint32_t k = lo ? lo - 1 : 0;
+    return SpanCursor{k, off[k], off[k + 1]};
+  }
+  // on to the span of slot s, from the span of a slot before it (spans may be 1 slot long: a loop)
+  __device__ __forceinline__ void span_to(const uint64_t *off, uint32_t n_spans, uint64_t s) {
+    while (s >= next && k + 1 < n_spans) ++k, first = next, next = off[k + 1];
   }
 };
 
@@ -374,29 +403,25 @@ constexpr uint32_t SAM_BAD = 48, H_SAM_NHOST = 49, H_SAM_TOTAL = 50;
 constexpr uint32_t BAM_BAD = 51, BAM_PAST = 52, H_BAM_BYTES = 53, H_BAM_KH = 54;
 // coordinate order (k_sort_keys): descents key[k - 1] > key[k], the OR and the AND of all keys
 constexpr uint32_t SORT_DESC = 55, SORT_OR = 56, SORT_AND = 57, SORT_END = 58;
-// depth add (k_depth_check): first bad row, first row that only runs past the stream's end, kept
-// rows, kept rows without a reference; (k_depth_events): rows walked, bases covered
-constexpr uint32_t DEPTH_BAD = SORT_END, DEPTH_PAST = DEPTH_BAD + 1, DEPTH_KEPT = DEPTH_BAD + 2;
-constexpr uint32_t DEPTH_UNPLACED = DEPTH_BAD + 3, DEPTH_COUNTED = DEPTH_BAD + 4, DEPTH_COV = DEPTH_BAD + 5;
-constexpr uint32_t DEPTH_END = DEPTH_BAD + 6;
-// tally add (sbh_records_tally_add), h_ctr only -- the device words are the accumulator's staging
-// words: first bad row, first row that only runs past the stream's end, kept rows (QC-pass, QC-fail)
-constexpr uint32_t H_TALLY_BAD = DEPTH_END, H_TALLY_PAST = H_TALLY_BAD + 1, H_TALLY_KEPT = H_TALLY_BAD + 2;
-constexpr uint32_t TALLY_END = H_TALLY_BAD + 4;
+// The head of an accumulator add's counters, the four words of its one round trip (sbh::AddTrip,
+// sbh_host.h): first bad row, first row that only runs past the stream's end, then two counters of the
+// stage's own.  Every add's row kernel writes them in this order and reads nothing else back.
+constexpr uint32_t ADD_BAD = 0, ADD_PAST = 1, ADD_A = 2, ADD_B = 3, ADD_HEAD = 4;
+// depth add: the head (k_depth_check: kept rows, kept rows without a reference); (k_depth_events):
+// rows walked, bases covered
+constexpr uint32_t DEPTH_BAD = SORT_END, DEPTH_COUNTED = DEPTH_BAD + ADD_HEAD, DEPTH_COV = DEPTH_COUNTED + 1;
+constexpr uint32_t DEPTH_END = DEPTH_COV + 1;
+// tally and stats adds, h_ctr only -- the device words are the accumulator's staging words: the head
+// (k_tally_rows: kept rows QC-pass, QC-fail; k_stats_rows: kept rows, counted rows)
+constexpr uint32_t H_STAGE_HEAD = DEPTH_END, STAGE_END = H_STAGE_HEAD + ADD_HEAD;
 // FASTQ scan (sbh_records_fastq_scan): first invalid row, first row that only runs past the stream's
 // end; h_ctr only: the parts' bytes (3 words), then their lines (3 words)
-constexpr uint32_t FASTQ_BAD = TALLY_END, FASTQ_PAST = FASTQ_BAD + 1, H_FASTQ_SUMS = FASTQ_BAD + 2;
+constexpr uint32_t FASTQ_BAD = STAGE_END, FASTQ_PAST = FASTQ_BAD + 1, H_FASTQ_SUMS = FASTQ_BAD + 2;
 constexpr uint32_t FASTQ_END = H_FASTQ_SUMS + 6;
-// pileup add (k_pile_check): first bad row, first row that only runs past the stream's end, kept
-// rows, kept rows without a reference; (k_pile_events): rows walked, then what went into each of
-// the eight channels
-constexpr uint32_t PILE_BAD = FASTQ_END, PILE_PAST = PILE_BAD + 1, PILE_KEPT = PILE_BAD + 2;
-constexpr uint32_t PILE_UNPLACED = PILE_BAD + 3, PILE_COUNTED = PILE_BAD + 4, PILE_TOTALS = PILE_BAD + 5;
+// pileup add: the head (k_pile_check: kept rows, kept rows without a reference); (k_pile_events):
+// rows walked, then what went into each of the eight channels
+constexpr uint32_t PILE_BAD = FASTQ_END, PILE_COUNTED = PILE_BAD + ADD_HEAD, PILE_TOTALS = PILE_COUNTED + 1;
 constexpr uint32_t PILE_END = PILE_TOTALS + 8;
-// stats add (sbh_records_stats_add), h_ctr only -- the device words are the accumulator's staging
-// words: first bad row, first row that only runs past the stream's end, kept rows, counted rows
-constexpr uint32_t H_STATS_BAD = PILE_END, H_STATS_PAST = H_STATS_BAD + 1, H_STATS_KEPT = H_STATS_BAD + 2;
-constexpr uint32_t H_STATS_COUNTED = H_STATS_BAD + 3, STATS_END = H_STATS_BAD + 4;
 // inflate status (launch_first_bad): the first block whose status is not INF_OK
 constexpr uint32_t FIRST_BAD = 100;
 // h_ctr only: that block's status (u32), fetched after the run's copy of [0, CTR_RUN_WORDS)
@@ -413,10 +438,9 @@ constexpr uint32_t CTR_CALL_END = 4 + ctr::FULL_NNZ * ctr::FULL_FLAGS + ctr::FUL
 static_assert(CTR_CALL_END <= CTR_TRUE_SPREAD && CTR_NEXT18 + 4 <= CTR_WORDS, "counter buffer layout");
 static_assert(ctr::FULL_END == CTR_CALL_END, "the full checker's counters end the per-call region");
 static_assert(ctr::DEPTH_END <= ctr::FIRST_BAD, "the depth counters end before the first bad block");
-static_assert(ctr::TALLY_END <= ctr::FIRST_BAD, "the tally add's mirror words end before the first bad block");
+static_assert(ctr::STAGE_END <= ctr::FIRST_BAD, "the tally and stats adds' mirror words end before the first bad block");
 static_assert(ctr::FASTQ_END <= ctr::FIRST_BAD, "the FASTQ scan's words end before the first bad block");
 static_assert(ctr::PILE_END <= ctr::FIRST_BAD, "the pileup add's counters end before the first bad block");
-static_assert(ctr::STATS_END <= ctr::FIRST_BAD, "the stats add's mirror words end before the first bad block");
 // what the run template presets (the eager counters, FindRecordStart's best, the proof
 // counters, the first bad block) travels in the run's one copy each way ...
 static_assert(ctr::EAGER_END <= CTR_RUN_WORDS && ctr::FRS_BEST < CTR_RUN_WORDS &&

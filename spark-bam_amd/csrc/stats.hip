@@ -337,22 +337,14 @@ int sbh_stats_create(sbh_ctx *ctx, const sbh_stats_params *params, sbh_stats **o
   s->ctx = ctx;
   s->params = *params;
   s->words = sbh_stat::layout_of(P).words;
-  hipError_t e = hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking);
-  const bool have_stream = e == hipSuccess;
-  if (e == hipSuccess) e = s->stage.ensure(ST_TAB + s->words);
-  if (e == hipSuccess) e = s->totals.ensure(s->words);
-  if (e == hipSuccess) e = hipMemsetAsync(s->totals.p, 0, 8 * s->words, s->st);
-  if (e == hipSuccess) e = hipStreamSynchronize(s->st);
-  if (e != hipSuccess) {
-    delete s;
-    if (e == hipErrorOutOfMemory || !have_stream) {
-      (void)hipGetLastError();
-      return fail(ctx, SBH_E_NOMEM, "stats: no memory for the tables of %u cycles", P.cycles);
-    }
-    return fail(ctx, SBH_E_HIP, "stats create: %s", hipGetErrorString(e));
-  }
-  *out = s;
-  return SBH_OK;
+  char nomem[80];
+  std::snprintf(nomem, sizeof nomem, "stats: no memory for the tables of %u cycles", P.cycles);
+  return accum_open(s, out, nomem, "stats create", [s] {
+    hipError_t e = s->stage.ensure(ST_TAB + s->words);
+    if (e == hipSuccess) e = s->totals.ensure(s->words);
+    if (e == hipSuccess) e = hipMemsetAsync(s->totals.p, 0, 8 * s->words, s->st);
+    return e;
+  });
 }
 
 int sbh_stats_destroy(sbh_stats *s) {
@@ -360,15 +352,7 @@ int sbh_stats_destroy(sbh_stats *s) {
   return SBH_OK;
 }
 
-int sbh_stats_reset(sbh_stats *s) {
-  if (!s) return SBH_E_ARG;
-  sbh_ctx *ctx = s->ctx;
-  int rc = set_device(ctx);
-  if (rc) return rc;
-  HIPCHK(ctx, hipMemsetAsync(s->totals.p, 0, 8 * s->words, s->st));
-  HIPCHK(ctx, hipStreamSynchronize(s->st));
-  return SBH_OK;
-}
+int sbh_stats_reset(sbh_stats *s) { return s ? s->reset(s->totals.p, 8 * s->words) : SBH_E_ARG; }
 
 // Two memsets, k_stats_rows, k_stats_bases (one launch per 2^25 rows), one round trip (bad row, past
 // row, kept rows, counted rows), then k_stats_commit only when no row is bad: a failed add has
@@ -376,33 +360,27 @@ int sbh_stats_reset(sbh_stats *s) {
 int sbh_records_stats_add(sbh_shard *sh, sbh_stats *s, const sbh_record_filter *filter, sbh_stats_add_result *out) {
   if (!sh || !s || !out) return SBH_E_ARG;
   sbh_ctx *ctx = sh->ctx;
-  if (s->ctx != ctx) return fail(ctx, SBH_E_ARG, "records_stats_add: the shard and the accumulator belong to different contexts");
   auto &R = sh->rec;
-  if (!R.valid) return fail(ctx, SBH_E_STATE, "records_stats_add without a records scan");
   sbh_bam::Filter F;
-  int rc = row_filter(ctx, filter, &F);
+  int rc = add_begin(sh, s, "records_stats_add", nullptr, filter, &F);
   if (rc) return rc;
   const uint64_t n = R.sz.n;
   *out = sbh_stats_add_result{n, 0, 0};
   if (!n) return SBH_OK;
-  rc = set_device(ctx);
-  if (rc) return rc;
   hipStream_t st = sh->st;
-  HIPCHK(ctx, stage_row_ranges(sh, &F));
-  static_assert(ST_BAD == 0 && ST_PAST == 1 && ST_KEPT == 2 && ST_TAB + sbh_stat::SN_SEQUENCES == 3 &&
-                    ctr::H_STATS_PAST == ctr::H_STATS_BAD + 1 && ctr::H_STATS_KEPT == ctr::H_STATS_BAD + 2 &&
-                    ctr::H_STATS_COUNTED == ctr::H_STATS_BAD + 3,
-                "two memsets, one copy back: bad, past, kept, counted");
+  // the head: bad, past, kept, counted -- sn[sequences], the first word of the tables
+  static_assert(ST_BAD == ctr::ADD_BAD && ST_PAST == ctr::ADD_PAST && ST_KEPT == ctr::ADD_A &&
+                    ST_TAB + sbh_stat::SN_SEQUENCES == ctr::ADD_B,
+                "the staging words open with the head");
   const sbh_stat::Params P{s->params.cycles, s->params.max_insert};
-  HIPCHK(ctx, hipMemsetAsync(s->stage.p, 0xff, 16, st));
-  HIPCHK(ctx, hipMemsetAsync(s->stage.p + ST_KEPT, 0, 8 * (1 + s->words), st));
-  HIPCHK(ctx, launch_stats_add(sh->U.p, R.pos.p, n, sh->utotal, F, P, s->stage.p, st));
-  HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::H_STATS_BAD, s->stage.p, 32, hipMemcpyDeviceToHost, st));
-  HIPCHK(ctx, hipStreamSynchronize(st));
-  rc = rows_verdict(sh, sh->h_ctr[ctr::H_STATS_BAD], sh->h_ctr[ctr::H_STATS_PAST], "");
+  const AddTrip trip{sh, s->stage.p, ctr::H_STAGE_HEAD};
+  rc = trip.open(&F, nullptr, 1 + s->words);
   if (rc) return rc;
-  out->n_kept = sh->h_ctr[ctr::H_STATS_KEPT];
-  out->n_counted = sh->h_ctr[ctr::H_STATS_COUNTED];
+  HIPCHK(ctx, launch_stats_add(sh->U.p, R.pos.p, n, sh->utotal, F, P, s->stage.p, st));
+  rc = trip.verdict("");
+  if (rc) return rc;
+  out->n_kept = trip.a();
+  out->n_counted = trip.b();
   if (out->n_kept) {
     HIPCHK(ctx, launch_stats_commit(s->totals.p, s->stage.p + ST_TAB, s->words, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
@@ -440,8 +418,7 @@ int sbh_stats_add_host(const uint8_t *flat, uint64_t flat_size, const uint64_t *
   uint64_t bad = sbh_bam::NO_ROW;
   const int rc = sbh_stat::add_host(flat, flat_size, starts, n, F, P, sbh_stat::Tables{sn, read_len, qual, base, gc, isize, mapq},
                                     reinterpret_cast<sbh_stat::AddResult *>(out), &bad);
-  if (bad_row) *bad_row = bad;
-  return rc == 0 ? SBH_OK : SBH_E_BAD_RECORD;
+  return host_rows_status(rc, bad, bad_row);
 }
 
 }  // extern "C"

@@ -172,14 +172,9 @@ struct Tables {  // sn[STAT_SN], read_len[C + 2], qual[2][C + 1][94], base[C + 1
 // untouched).
 inline int add_host(const uint8_t *flat, uint64_t flat_size, const uint64_t *starts, uint64_t n, const sbh_bam::Filter &F,
                     const Params &P, const Tables &T, AddResult *res, uint64_t *bad_row) {
-  *bad_row = sbh_bam::NO_ROW;
   *res = AddResult{n, 0, 0};
-  uint64_t len = 0;
-  for (uint64_t i = 0; i < n; ++i)
-    if (sbh_bam::row_check(flat, flat_size, starts[i], &len) != sbh_bam::ROW_OK) {
-      *bad_row = i;
-      return 1;
-    }
+  *bad_row = sbh_bam::first_bad_row(flat, flat_size, starts, n, F, [](const uint8_t *) { return true; });
+  if (*bad_row != sbh_bam::NO_ROW) return 1;
   const uint32_t C = P.cycles;
   for (uint64_t i = 0; i < n; ++i) {
     const uint8_t *r = flat + starts[i];

@@ -183,22 +183,14 @@ int sbh_tally_create(sbh_ctx *ctx, int32_t n_ref, sbh_tally **out) {
   t->ctx = ctx;
   t->n_ref = n_ref;
   t->words = FLAG_WORDS + 2 * ((uint64_t)n_ref + 1);
-  hipError_t e = hipStreamCreateWithFlags(&t->st, hipStreamNonBlocking);
-  const bool have_stream = e == hipSuccess;
-  if (e == hipSuccess) e = t->stage.ensure(ST_FLAG + t->words);
-  if (e == hipSuccess) e = t->totals.ensure(t->words);
-  if (e == hipSuccess) e = hipMemsetAsync(t->totals.p, 0, 8 * t->words, t->st);
-  if (e == hipSuccess) e = hipStreamSynchronize(t->st);
-  if (e != hipSuccess) {
-    delete t;
-    if (e == hipErrorOutOfMemory || !have_stream) {
-      (void)hipGetLastError();
-      return fail(ctx, SBH_E_NOMEM, "tally: no memory for the counters of %d references", n_ref);
-    }
-    return fail(ctx, SBH_E_HIP, "tally create: %s", hipGetErrorString(e));
-  }
-  *out = t;
-  return SBH_OK;
+  char nomem[80];
+  std::snprintf(nomem, sizeof nomem, "tally: no memory for the counters of %d references", n_ref);
+  return accum_open(t, out, nomem, "tally create", [t] {
+    hipError_t e = t->stage.ensure(ST_FLAG + t->words);
+    if (e == hipSuccess) e = t->totals.ensure(t->words);
+    if (e == hipSuccess) e = hipMemsetAsync(t->totals.p, 0, 8 * t->words, t->st);
+    return e;
+  });
 }
 
 int sbh_tally_destroy(sbh_tally *t) {
@@ -206,45 +198,30 @@ int sbh_tally_destroy(sbh_tally *t) {
   return SBH_OK;
 }
 
-int sbh_tally_reset(sbh_tally *t) {
-  if (!t) return SBH_E_ARG;
-  sbh_ctx *ctx = t->ctx;
-  int rc = set_device(ctx);
-  if (rc) return rc;
-  HIPCHK(ctx, hipMemsetAsync(t->totals.p, 0, 8 * t->words, t->st));
-  HIPCHK(ctx, hipStreamSynchronize(t->st));
-  return SBH_OK;
-}
+int sbh_tally_reset(sbh_tally *t) { return t ? t->reset(t->totals.p, 8 * t->words) : SBH_E_ARG; }
 
 // Two memsets, k_tally_rows, one round trip (bad row, past row, the two totals of kept rows), then
 // k_tally_commit only when no row is bad: a failed add has written nothing into the totals.
 int sbh_records_tally_add(sbh_shard *sh, sbh_tally *t, const sbh_record_filter *filter, sbh_tally_add_result *out) {
   if (!sh || !t || !out) return SBH_E_ARG;
   sbh_ctx *ctx = sh->ctx;
-  if (t->ctx != ctx) return fail(ctx, SBH_E_ARG, "records_tally_add: the shard and the accumulator belong to different contexts");
   auto &R = sh->rec;
-  if (!R.valid) return fail(ctx, SBH_E_STATE, "records_tally_add without a records scan");
   sbh_bam::Filter F;
-  int rc = row_filter(ctx, filter, &F);
+  int rc = add_begin(sh, t, "records_tally_add", nullptr, filter, &F);
   if (rc) return rc;
   const uint64_t n = R.sz.n;
   *out = sbh_tally_add_result{n, 0};
   if (!n) return SBH_OK;
-  rc = set_device(ctx);
-  if (rc) return rc;
   hipStream_t st = sh->st;
-  HIPCHK(ctx, stage_row_ranges(sh, &F));
-  static_assert(ST_BAD == 0 && ST_PAST == 1 && ST_FLAG == 2 && ctr::H_TALLY_PAST == ctr::H_TALLY_BAD + 1 &&
-                    ctr::H_TALLY_KEPT == ctr::H_TALLY_BAD + 2,
-                "two memsets, one copy back: bad, past, total[QC-pass], total[QC-fail]");
-  HIPCHK(ctx, hipMemsetAsync(t->stage.p, 0xff, 16, st));
-  HIPCHK(ctx, hipMemsetAsync(t->stage.p + ST_FLAG, 0, 8 * t->words, st));
-  HIPCHK(ctx, launch_tally_rows(sh->U.p, R.pos.p, n, sh->utotal, F, t->n_ref, t->stage.p, st));
-  HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::H_TALLY_BAD, t->stage.p, 32, hipMemcpyDeviceToHost, st));
-  HIPCHK(ctx, hipStreamSynchronize(st));
-  rc = rows_verdict(sh, sh->h_ctr[ctr::H_TALLY_BAD], sh->h_ctr[ctr::H_TALLY_PAST], ", or its reference is out of range");
+  // the head: bad, past, total[QC-pass], total[QC-fail] -- the first two flag counters
+  static_assert(ST_BAD == ctr::ADD_BAD && ST_PAST == ctr::ADD_PAST && ST_FLAG == ctr::ADD_A, "the staging words open with the head");
+  const AddTrip trip{sh, t->stage.p, ctr::H_STAGE_HEAD};
+  rc = trip.open(&F, nullptr, t->words);
   if (rc) return rc;
-  out->n_kept = sh->h_ctr[ctr::H_TALLY_KEPT] + sh->h_ctr[ctr::H_TALLY_KEPT + 1];
+  HIPCHK(ctx, launch_tally_rows(sh->U.p, R.pos.p, n, sh->utotal, F, t->n_ref, t->stage.p, st));
+  rc = trip.verdict(", or its reference is out of range");
+  if (rc) return rc;
+  out->n_kept = trip.a() + trip.b();
   if (out->n_kept) {
     HIPCHK(ctx, launch_tally_commit(t->totals.p, t->stage.p + ST_FLAG, t->words, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
@@ -277,8 +254,7 @@ int sbh_tally_add_host(const uint8_t *flat, uint64_t flat_size, const uint64_t *
   if (!bam_filter_of(filter, &F)) return SBH_E_ARG;
   uint64_t bad = sbh_bam::NO_ROW;
   const int rc = sbh_tal::add_host(flat, flat_size, starts, n, F, n_ref, flag, ref, reinterpret_cast<sbh_tal::AddResult *>(out), &bad);
-  if (bad_row) *bad_row = bad;
-  return rc == 0 ? SBH_OK : SBH_E_BAD_RECORD;
+  return host_rows_status(rc, bad, bad_row);
 }
 
 }  // extern "C"

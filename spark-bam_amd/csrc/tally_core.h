@@ -82,17 +82,10 @@ struct AddResult {  // sbh_tally_add_result's layout
 // bad row: *bad_row, the arrays untouched).
 inline int add_host(const uint8_t *flat, uint64_t flat_size, const uint64_t *starts, uint64_t n, const sbh_bam::Filter &F,
                     int32_t n_ref, uint64_t *flag, uint64_t *ref, AddResult *res, uint64_t *bad_row) {
-  *bad_row = sbh_bam::NO_ROW;
   *res = AddResult{n, 0};
-  uint64_t len = 0;
-  for (uint64_t i = 0; i < n; ++i) {
-    bool ok = sbh_bam::row_check(flat, flat_size, starts[i], &len) == sbh_bam::ROW_OK;
-    if (ok && sbh_bam::row_keep(flat + starts[i], i, F)) ok = (int32_t)sbh_bam::ld32(flat + starts[i] + 4) < n_ref;
-    if (!ok) {
-      *bad_row = i;
-      return 1;
-    }
-  }
+  *bad_row = sbh_bam::first_bad_row(flat, flat_size, starts, n, F,
+                                    [n_ref](const uint8_t *r) { return (int32_t)sbh_bam::ld32(r + 4) < n_ref; });
+  if (*bad_row != sbh_bam::NO_ROW) return 1;
   for (uint64_t i = 0; i < n; ++i) {
     const uint8_t *r = flat + starts[i];
     if (!sbh_bam::row_keep(r, i, F)) continue;
