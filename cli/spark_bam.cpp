@@ -10,8 +10,9 @@
 //   spark-bam index-records BAM [OUT]                        (check/index/IndexRecords.scala)
 //   spark-bam index-bai     BAM [OUT]                        (the .bai samtools index writes; htslib hts.c)
 //   spark-bam view [-h] [-o FILE] BAM                        (the records as SAM text: htsjdk getSAMString)
-//   spark-bam view -b -o OUT [-f INT] [-F INT] [-q INT] [-r ROWS] [--level N] [--index-bai] [--sort] BAM
-//   spark-bam sort [-o OUT] [--level N] [--index-bai] BAM [OUT]  (coordinate order, as samtools sort)
+//   spark-bam view -b -o OUT [-f INT] [-F INT] [-q INT] [-r ROWS] [--level N] [--index-bai] [--sort|--sort-name] BAM
+//   spark-bam sort [-N] [-o OUT] [--level N] [--index-bai] BAM [OUT]  (coordinate order, as samtools sort;
+//                                                             -N: read-name order, as samtools sort -N)
 //                                                            (the records that pass, as a BAM gathered on the GPU)
 //   spark-bam check-blocks -s [-r RECORDS] [-l N] BAM        (cli/.../check/blocks/CheckBlocks.scala)
 //   spark-bam htsjdk-rewrite [-r READS] [-b] [-i] [--index-bai] BAM OUT  (cli/.../rewrite/HTSJDKRewrite.scala)
@@ -263,7 +264,8 @@ struct Args {
   // view -b: BAM output of the records with (flag & -f) == -f, (flag & -F) == 0, mapq >= -q and an
   // index in -r (read_ranges); --level as sbh_bgzf_compress_level; --index-bai (idx_bai) writes OUT.bai
   // view -b --sort, sort: the kept records in coordinate order (sbh_records_bam_scan_order), SO:coordinate
-  bool bam_out = false, sort = false;
+  // view -b --sort-name, sort -N: in read-name order (sbh_records_bam_scan_names), SO:queryname; no --index-bai
+  bool bam_out = false, sort = false, sort_name = false;
   uint32_t flag_require = 0, flag_exclude = 0;
   int min_mapq = 0, level = SBH_LEVEL_HTSJDK;
   // depth: -a every position of the spans, -r REGION, -J D ops cover, --bedgraph; -F defaults to 1796
@@ -331,11 +333,15 @@ Args parse(int argc, char **argv) {
                 "            check-blocks htsjdk-rewrite view sort depth pileup consensus flagstat idxstats stats fastq\n"
                 "            fasta\n"
                 "  view [-h|--header] [-o FILE] <bam>: the records as SAM text (-h: the header text first)\n"
-                "  view -b -o OUT [-f INT] [-F INT] [-q INT] [-r ROWS] [--level N] [--index-bai] [--sort] <bam>: the records with\n"
+                "  view -b -o OUT [-f INT] [-F INT] [-q INT] [-r ROWS] [--level N] [--index-bai] [--sort|--sort-name] <bam>:\n"
+                "       the records with\n"
                 "       (flag & f) == f, (flag & F) == 0, mapq >= q and an index in ROWS (a-b,c-d: htsjdk-rewrite's -r)\n"
                 "       as a BAM at deflate level N (5: htsjdk's bytes; -1: the fast coder); --index-bai writes OUT.bai;\n"
                 "       --sort: in coordinate order (reference, position, strand; unplaced last), header SO:coordinate\n"
-                "  sort [-o OUT] [--level N] [--index-bai] <bam> [OUT]: every record, coordinate-sorted on the GPU\n"
+                "       --sort-name: in read-name order (bytes of the name, a prefix first; then read 1, read 2; primary,\n"
+                "       secondary, supplementary), header SO:queryname; not with --index-bai (a BAI needs coordinate order)\n"
+                "  sort [-N] [-o OUT] [--level N] [--index-bai] <bam> [OUT]: every record, coordinate-sorted on the GPU;\n"
+                "       -N: sorted by read name instead (samtools sort -N's byte order), not with --index-bai\n"
                 "  depth [-a] [-r REGION] [-f INT] [-F INT] [-q INT] [-J] [--bedgraph] [-o FILE] <bam>: per-base depth as\n"
                 "       RNAME POS DEPTH lines (samtools depth; -a: zero-depth positions too) or, with --bedgraph, RNAME BEG END\n"
                 "       DEPTH runs (genomecov -bg); REGION is NAME or NAME:BEG-END (1-based, inclusive); -F defaults to 1796;\n"
@@ -390,6 +396,8 @@ Args parse(int argc, char **argv) {
     else if (view && (t == "-h" || t == "--header")) a.sam_header = true;
     else if (view && (t == "-b" || t == "--bam")) a.bam_out = true;
     else if (view && t == "--sort") a.sort = true;
+    else if (view && t == "--sort-name") a.sort_name = true;
+    else if (a.cmd == "sort" && t == "-N") a.sort_name = true;
     else if (view && (t == "-c" || t == "--count")) a.count_only = true;
     else if (a.cmd == "stats" && t == "--cycles") a.stat_cycles = parse_int(next());
     else if (a.cmd == "stats" && (t == "-i" || t == "--insert-size")) a.stat_insert = parse_int(next());
@@ -426,7 +434,7 @@ Args parse(int argc, char **argv) {
   if (pos.empty()) throw Error(SBH_E_ARG, "missing BAM path");
   a.path = pos[0];
   if (a.count_only) {
-    if (a.bam_out || a.sam_header || a.has_read_ranges || a.idx_bai || a.sort || !a.out.empty() || pos.size() != 1 ||
+    if (a.bam_out || a.sam_header || a.has_read_ranges || a.idx_bai || a.sort || a.sort_name || !a.out.empty() || pos.size() != 1 ||
         (pos[0].size() > 1 && pos[0][0] == '-'))
       throw Error(SBH_E_ARG, "usage: view -c [-f INT] [-F INT] [-q INT] <bam>");
   }
@@ -434,8 +442,13 @@ Args parse(int argc, char **argv) {
   if (fq && !a.has_exclude) a.flag_exclude = 0x900;  // SECONDARY, SUPPLEMENTARY: samtools fastq's
   if (fq && a.suffix_never && a.suffix_always) throw Error(SBH_E_ARG, "usage: " + a.cmd + " takes -n or -N, not both");
   if ((a.cmd == "depth" || pile) && !a.has_exclude) a.flag_exclude = 1796;  // UNMAP, SECONDARY, QCFAIL, DUP: samtools depth's
+  if (a.sort && a.sort_name) throw Error(SBH_E_ARG, "usage: view -b takes --sort or --sort-name, not both");
+  if (a.sort_name && a.idx_bai)
+    throw Error(SBH_E_ARG, std::string(a.cmd == "sort" ? "sort -N" : "view --sort-name") +
+                               " with --index-bai: a BAI indexes by position and needs coordinate order, not read-name order");
   if (a.cmd == "sort") {
-    a.bam_out = a.sort = true;
+    a.bam_out = true;
+    a.sort = !a.sort_name;
     if (a.out.empty()) throw Error(SBH_E_ARG, "usage: sort needs -o OUT (a BAM is not written to the terminal)");
   }
   if (a.cmd == "view" && a.bam_out && a.out.empty())
@@ -1110,8 +1123,8 @@ int tally(const Args &a);
 int view(const Args &a) {
   if (a.count_only) return tally(a);
   if (a.bam_out) return view_bam(a);
-  if (a.has_read_ranges || a.flag_require || a.flag_exclude || a.min_mapq || a.idx_bai || a.sort)
-    throw Error(SBH_E_ARG, "view: -f / -F / -q / -r / --index-bai / --sort select records for BAM output: they need -b");
+  if (a.has_read_ranges || a.flag_require || a.flag_exclude || a.min_mapq || a.idx_bai || a.sort || a.sort_name)
+    throw Error(SBH_E_ARG, "view: -f / -F / -q / -r / --index-bai / --sort / --sort-name select records for BAM output: they need -b");
   Loaded L(a.path);
   std::vector<char> text;
   uint64_t head = 0;
@@ -1151,10 +1164,11 @@ int view_bam(const Args &a) {
     Loaded L(a.path);
     std::vector<uint8_t> head(L.hdr.end);
     if (L.hdr.end) chk(sbh_read_flat(L.sh, 0, L.hdr.end, head.data()), "read header");
-    if (a.sort) {
+    if (a.sort || a.sort_name) {
       std::vector<uint8_t> so(head.size() + 64);
       uint64_t so_n = 0;
-      chk(sbh_bam_header_set_so(head.data(), head.size(), "coordinate", so.data(), so.size(), &so_n), "header SO");
+      chk(sbh_bam_header_set_so(head.data(), head.size(), a.sort_name ? "queryname" : "coordinate", so.data(), so.size(), &so_n),
+          "header SO");
       so.resize(so_n);
       head.swap(so);
     }
@@ -1172,8 +1186,11 @@ int view_bam(const Args &a) {
     f.row_end = re.data();
     f.n_row_ranges = rb.size();
     sbh_bam_sizes bs{};
-    chk(sbh_records_bam_scan_order(L.sh, head.data(), head.size(), &f, a.sort ? SBH_ORDER_COORDINATE : SBH_ORDER_SCAN, &bs),
-        "bam scan");
+    if (a.sort_name)
+      chk(sbh_records_bam_scan_names(L.sh, head.data(), head.size(), &f, &bs), "bam scan");
+    else
+      chk(sbh_records_bam_scan_order(L.sh, head.data(), head.size(), &f, a.sort ? SBH_ORDER_COORDINATE : SBH_ORDER_SCAN, &bs),
+          "bam scan");
     out.resize(sbh_bgzf_compress_bound(bs.bytes));
     chk(sbh_bgzf_compress_level(g_ctx, sbh_records_bam_device_ptr(L.sh), bs.bytes, 1, a.level, out.data(), out.size(), &size,
                                 &nb, nullptr),

@@ -742,6 +742,30 @@ int sbh_records_bam_sorted(sbh_shard *sh, int *already);
  * SBH_E_BAD_RECORD with *bad_row = the first invalid row (sbh_bam_gather_host's validation). */
 int sbh_bam_sort_host(const uint8_t *flat, uint64_t flat_size, const uint64_t *starts, uint64_t n,
                       uint64_t *perm /*[n]*/, uint64_t *bad_row);
+/* The same stream with the kept rows in read-name order (samtools sort -N): ascending name, then
+ * ascending tie, rows equal in both in scan order (a stable sort on the device;
+ * csrc/bam_name_core.h holds the definition for device and host).  The name is the
+ * l_read_name - 1 bytes behind the fixed fields, compared as unsigned bytes after padding with
+ * zeros to 256 bytes -- a prefix comes first; strcmp's order for the names SAM allows.
+ *   tie = ((flag >> 6) & 3) << 2 | ((flag >> 11) & 1) << 1 | ((flag >> 8) & 1)
+ * -- READ1 / READ2 as samtools compares flag & 0xc0, then primary, secondary, supplementary.  The
+ * tie is this library's own and not htsjdk's comparator chain; natural order (sort -n) is not built.
+ * State, invalidation, errors and sbh_records_bam_fetch (rows[k] = the scan row of the k-th output
+ * record) as sbh_records_bam_scan_order; sbh_records_bam_sorted keeps returning SBH_E_STATE after
+ * this call.  sbh_records_bam_name_info: the summary of the last valid BAM scan when that was a
+ * name-order one (SBH_E_STATE otherwise): the groups of rows of one name and those of 1, 2 and
+ * more rows, the longest name in bytes, the 8-byte chunks and the 8-bit radix passes the sort ran,
+ * and already = 1 when the kept rows were in order as scanned (nothing ran, nothing was moved). */
+typedef struct { uint64_t n_names, n_single, n_pair, n_more;
+                 uint32_t max_name, chunks_run, passes_run; int32_t already; } sbh_bam_name_info;
+int sbh_records_bam_scan_names(sbh_shard *sh, const uint8_t *head, uint64_t head_bytes,
+                               const sbh_record_filter *filter, sbh_bam_sizes *out);
+int sbh_records_bam_name_info(sbh_shard *sh, sbh_bam_name_info *out);
+/* HOST ONLY, no context, no GPU: perm[k] = the row of starts[] that comes k-th in name order; info
+ * (may be NULL) gets the group counts, max_name and already -- chunks_run and passes_run stay 0.
+ * SBH_E_BAD_RECORD with *bad_row = the first invalid row (sbh_bam_gather_host's validation). */
+int sbh_bam_name_sort_host(const uint8_t *flat, uint64_t flat_size, const uint64_t *starts, uint64_t n,
+                           uint64_t *perm /*[n]*/, sbh_bam_name_info *info /* may be NULL */, uint64_t *bad_row);
 /* HOST ONLY: the BAM header bytes head[0, n) (magic, l_text, text, n_ref, references) with the
  * @HD line's SO: set to `so` -- an existing value replaced, "\tSO:<so>" appended to an @HD line
  * without one, "@HD\tVN:1.6\tSO:<so>\n" put in front of a text without @HD.  l_text follows, a

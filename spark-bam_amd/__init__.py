@@ -12,7 +12,8 @@ Import name: ``spark_bam_amd`` (the directory name contains a hyphen, so load it
   index:  build_bai / write_bai (the `.bai` samtools index writes, built on the GPU)
   text:   view (the records as SAM text, rendered on the GPU), sam_text_host
   subset: view_bam (filtered records as a BAM with its index, gathered on the GPU), bam_gather_host
-  sort:   sort_bam (the records coordinate-sorted on the GPU), bam_sort_host
+  sort:   sort_bam (the records sorted on the GPU, by coordinate or by read name), bam_sort_host,
+          bam_name_sort_host
   depth:  depth (per-base coverage accumulated and scanned on the GPU), depth_host
   pileup: pileup (per-base allele counts, call bytes and consensus on the GPU), pileup_host
   counts: flagstat, idxstats (flag and per-reference read counts, one pass on the GPU), tally_host
@@ -32,7 +33,7 @@ from .stats import SN_ROWS, StatsResult, stats_host, stats_text  # noqa: F401
 from .api import stats  # noqa: F401,E402  (after the submodule of the same name: the function is what the package exports)
 from .fastq import FastqResult, fastq_host, fastq_mode  # noqa: F401
 from .api import fastq  # noqa: F401,E402  (after the submodule of the same name: the function is what the package exports)
-from .records import Reads, bam_gather_host, bam_header_set_so, bam_sort_host, sam_text_host  # noqa: F401
+from .records import Reads, bam_gather_host, bam_header_set_so, bam_name_sort_host, bam_sort_host, sam_text_host  # noqa: F401
 from .coverage import DepthResult, depth_bedgraph, depth_host, depth_text  # noqa: F401
 from .pileup import PileupResult, consensus_fasta, pileup_host, pileup_text  # noqa: F401
 from .api import pileup  # noqa: F401,E402  (after the submodule of the same name: the function is what the package exports)
@@ -50,7 +51,7 @@ __all__ = [
     "read_bai", "parse_loci", "get_interval_chunks", "load_bam_intervals",
     "GpuWindow", "WindowedEagerChecker", "WindowedFullChecker",
     "build_bai", "write_bai", "view", "sam_text_host", "view_bam", "bam_gather_host",
-    "sort_bam", "bam_sort_host", "bam_header_set_so",
+    "sort_bam", "bam_sort_host", "bam_name_sort_host", "bam_header_set_so",
     "depth", "Depth", "DepthResult", "depth_host", "depth_text", "depth_bedgraph",
     "pileup", "Pileup", "PileupResult", "pileup_host", "pileup_text", "consensus_fasta",
     "flagstat", "idxstats", "Tally", "TallyResult", "tally_host", "flagstat_text", "idxstats_text",

@@ -48,6 +48,7 @@ EXPORTS = [
     "sbh_records_bam_scan", "sbh_records_bam_device_ptr", "sbh_records_bam_fetch", "sbh_records_bam_read",
     "sbh_bam_gather_host",
     "sbh_records_bam_scan_order", "sbh_records_bam_sorted", "sbh_bam_sort_host", "sbh_bam_header_set_so",
+    "sbh_records_bam_scan_names", "sbh_records_bam_name_info", "sbh_bam_name_sort_host",
     "sbh_depth_create", "sbh_depth_destroy", "sbh_depth_reset", "sbh_records_depth_add", "sbh_depth_finish",
     "sbh_depth_fetch", "sbh_depth_runs_fetch", "sbh_depth_device_ptr", "sbh_depth_slots", "sbh_depth_add_host",
     "sbh_depth_finish_host",
@@ -147,6 +148,12 @@ class SbhRecordFilter(C.Structure):
 
 class SbhBamSizes(C.Structure):
     _fields_ = [("n", C.c_uint64), ("n_kept", C.c_uint64), ("bytes", C.c_uint64)]
+
+
+class SbhBamNameInfo(C.Structure):  # sbh_bam_name_info
+    _fields_ = [("n_names", C.c_uint64), ("n_single", C.c_uint64), ("n_pair", C.c_uint64), ("n_more", C.c_uint64),
+                ("max_name", C.c_uint32), ("chunks_run", C.c_uint32), ("passes_run", C.c_uint32),
+                ("already", C.c_int32)]
 
 
 class SbhDepthAddResult(C.Structure):
@@ -320,6 +327,9 @@ def lib():
         "sbh_records_bam_scan_order": [P, P, U64, C.POINTER(SbhRecordFilter), C.c_int, C.POINTER(SbhBamSizes)],
         "sbh_records_bam_sorted": [P, C.POINTER(C.c_int)],
         "sbh_bam_sort_host": [P, U64, P, U64, P, PU64],
+        "sbh_records_bam_scan_names": [P, P, U64, C.POINTER(SbhRecordFilter), C.POINTER(SbhBamSizes)],
+        "sbh_records_bam_name_info": [P, C.POINTER(SbhBamNameInfo)],
+        "sbh_bam_name_sort_host": [P, U64, P, U64, P, C.POINTER(SbhBamNameInfo), PU64],
         "sbh_bam_header_set_so": [P, U64, C.c_char_p, P, U64, PU64],
         "sbh_records_bam_fetch": [P, P, P, P],
         "sbh_records_bam_read": [P, U64, U64, P],

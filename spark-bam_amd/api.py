@@ -343,15 +343,21 @@ def view_bam(path_or_bytes, out=None, flag_require=0, flag_exclude=0, min_mapq=0
     sort="coordinate": the kept records in stable coordinate order (Shard.records_bam's
     order="coordinate": reference, position, reverse strand, unplaced last), sorted on the GPU,
     behind a header whose @HD line says SO:coordinate.  Filters and `rows` apply before the sort.
-    The whole file must then fit one window: a second window raises SparkBamError(SBH_E_ARG)
+    sort="name": the kept records in stable read-name order (Shard.records_bam's order="name":
+    samtools sort -N's byte order, then READ1 / READ2, primary, secondary, supplementary), behind a
+    header whose @HD line says SO:queryname.  index=True is then a ValueError: a BAI needs
+    coordinate order.
+    Either way the whole file must fit one window: a second window raises SparkBamError(SBH_E_ARG)
     (merging sorted windows is not done here; pass a larger `window`), and so does `intervals`.
 
     Returns the file bytes; with `out` (a path or a binary file object) writes them and returns
     the byte count.  index=True: also the `.bai` of the result (bai.build_bai) -- returned as
     (bam, bai), written to out + ".bai" when out is a path, or returned as (count, bai) when out
     is a file object."""
-    if sort not in (None, "coordinate"):
-        raise ValueError("view_bam: sort is None or 'coordinate', not %r" % (sort,))
+    if sort not in (None, "coordinate", "name"):
+        raise ValueError("view_bam: sort is None, 'coordinate' or 'name', not %r" % (sort,))
+    if sort == "name" and index:
+        raise ValueError("view_bam: index=True needs coordinate order, not sort='name' (a BAI indexes by position)")
     if sort and intervals is not None:
         raise SparkBamError(SBH_E_ARG, "view_bam: sort needs the whole file in one window, not `intervals`")
     data = _file_array(path_or_bytes)
@@ -383,7 +389,7 @@ def view_bam(path_or_bytes, out=None, flag_require=0, flag_exclude=0, min_mapq=0
     with _context(ctx) as ctx:
         state["tail"] = _header_flat(ctx, data)
         if sort:
-            state["tail"] = bam_header_set_so(state["tail"], sort)
+            state["tail"] = bam_header_set_so(state["tail"], "queryname" if sort == "name" else sort)
         if intervals is None:
             def deliver(sh, f, E, names):
                 sh.records_scan(f, E)
@@ -423,14 +429,21 @@ def view_bam(path_or_bytes, out=None, flag_require=0, flag_exclude=0, min_mapq=0
     return (len(result), bai_bytes) if index else len(result)
 
 
-def sort_bam(path_or_bytes, out=None, level=5, index=False, ctx=None, reads_to_check=DEFAULT_READS_TO_CHECK):
+def sort_bam(path_or_bytes, out=None, level=5, index=False, ctx=None, reads_to_check=DEFAULT_READS_TO_CHECK,
+             order="coordinate"):
     """The file coordinate-sorted (what `samtools sort` writes, up to the compressed bytes): every
     record, in stable (reference, position, reverse strand) order with the unplaced ones last,
-    under a header that says SO:coordinate.  view_bam with sort="coordinate" and the whole file as
-    its one window; `out`, `level`, `index` and the return value as there."""
+    under a header that says SO:coordinate.  order="name": sorted by read name instead (`samtools
+    sort -N`'s byte order; the tie in view_bam's words) under SO:queryname; index=True is then a
+    ValueError.  view_bam with that `sort` and the whole file as its one window; `out`, `level`,
+    `index` and the return value as there."""
+    if order not in ("coordinate", "name"):
+        raise ValueError("sort_bam: order is 'coordinate' or 'name', not %r" % (order,))
+    if order == "name" and index:
+        raise ValueError("sort_bam: index=True needs coordinate order, not order='name' (a BAI indexes by position)")
     data = _file_array(path_or_bytes)
     return view_bam(data, out=out, level=level, index=index, ctx=ctx, reads_to_check=reads_to_check,
-                    window=max(int(data.size), 1), sort="coordinate")
+                    window=max(int(data.size), 1), sort=order)
 
 
 def depth(path_or_bytes, region=None, flag_require=0, flag_exclude=0x704, min_mapq=0, count_del=False, window=None,

@@ -15,6 +15,7 @@
 
 #define SBH_HD __host__ __device__
 #include "bam_gather_core.h"
+#include "bam_name_core.h"
 #include "bam_sort_core.h"
 #include "sbh_host.h"
 
@@ -227,15 +228,22 @@ int sbh_records_bam_scan(sbh_shard *sh, const uint8_t *head, uint64_t head_bytes
 // Otherwise the passes whose digit differs somewhere (OR & ~AND) run, k_sort_apply lays out the
 // permuted starts and lengths, and k_bam_heads, the scans and k_bam_index run over those -- every
 // entry kept -- before a second round trip for the run count.
-int sbh_records_bam_scan_order(sbh_shard *sh, const uint8_t *head, uint64_t head_bytes, const sbh_record_filter *filter,
-                               int order, sbh_bam_sizes *out) {
+//
+// ORDER_NAME (sbh_records_bam_scan_names; bam_name.hip): k_name_scan stands where k_sort_keys
+// stands and the same round trip brings its words (nacc::).  No descent: as above.  Otherwise the tie
+// stage, then the chunks from the last one the longest name reaches down to chunk 0 -- each k_name_keys
+// and the passes whose digit differs somewhere, skipped whole when the chunk is the same in every row
+// -- all enqueued with no host read between them; then k_sort_apply and the rest as in coordinate
+// order.  k_name_groups runs over the final row array either way, and its four words come back with
+// the call's last synchronisation.
+static int bam_scan(sbh_shard *sh, const uint8_t *head, uint64_t head_bytes, const sbh_record_filter *filter, int order,
+                    sbh_bam_sizes *out) {
   if (!sh || !out || (head_bytes && !head)) return SBH_E_ARG;
   sbh_ctx *ctx = sh->ctx;
   auto &R = sh->rec;
   auto &B = sh->bam;
-  if (order != SBH_ORDER_SCAN && order != SBH_ORDER_COORDINATE)
-    return fail(ctx, SBH_E_ARG, "records_bam_scan: order %d is neither SBH_ORDER_SCAN nor SBH_ORDER_COORDINATE", order);
-  const bool sorted = order == SBH_ORDER_COORDINATE;
+  const bool named = order == ORDER_NAME;
+  const bool sorted = order == SBH_ORDER_COORDINATE || named;
   if (!R.valid) return fail(ctx, SBH_E_STATE, "records_bam_scan without a records scan");
   sbh_bam::Filter F;
   int rc = row_filter(ctx, filter, &F);
@@ -256,8 +264,11 @@ int sbh_records_bam_scan_order(sbh_shard *sh, const uint8_t *head, uint64_t head
     for (auto *b : {&B.pos2, &B.len2}) HIPCHK(ctx, b->ensure(n + 1));
     HIPCHK(ctx, B.hist.ensure(2 * hist_words));
     HIPCHK(ctx, sh->tmp.ensure(scan_tmp_words(hist_words)));
+    if (named) HIPCHK(ctx, B.nacc.ensure(nacc::WORDS));
   }
   bool already = true;
+  sbh_bam_name_info info{};
+  unsigned long long *hn = sh->h_ctr + ctr::H_NAME;  // the name words' mirror
   if (n) {
     HIPCHK(ctx, stage_row_ranges(sh, &F));
     HIPCHK(ctx, sh->tmp.ensure(scan_tmp_words(n + 1)));
@@ -273,7 +284,12 @@ int sbh_records_bam_scan_order(sbh_shard *sh, const uint8_t *head, uint64_t head
                                  B.run_src.p, st));
     unsigned long long *acc = sh->ctr.p + ctr::SORT_DESC;
     static_assert(ctr::SORT_OR == ctr::SORT_DESC + 1 && ctr::SORT_AND == ctr::SORT_DESC + 2, "one copy");
-    if (sorted) {
+    if (named) {
+      HIPCHK(ctx, hipMemsetAsync(B.nacc.p, 0, 8 * nacc::ONES, st));
+      HIPCHK(ctx, hipMemsetAsync(B.nacc.p + nacc::ONES, 0xff, 8 * (nacc::WORDS - nacc::ONES), st));
+      HIPCHK(ctx, launch_name_scan(sh->U.p, R.pos.p, B.rows.p, B.khpre.p + n, n, B.srow[0].p, B.nacc.p, st));
+      HIPCHK(ctx, hipMemcpyAsync(hn, B.nacc.p, 8 * nacc::WORDS, hipMemcpyDeviceToHost, st));
+    } else if (sorted) {
       HIPCHK(ctx, hipMemsetAsync(acc, 0, 16, st));
       HIPCHK(ctx, hipMemsetAsync(acc + 2, 0xff, 8, st));
       HIPCHK(ctx, launch_sort_keys(sh->U.p, R.pos.p, B.rows.p, B.khpre.p + n, n, B.skey[0].p, B.srow[0].p, acc, st));
@@ -288,15 +304,43 @@ int sbh_records_bam_scan_order(sbh_shard *sh, const uint8_t *head, uint64_t head
     bytes += sh->h_ctr[ctr::H_BAM_BYTES];
     n_kept = sh->h_ctr[ctr::H_BAM_KH] & 0xffffffffull;
     n_runs = sh->h_ctr[ctr::H_BAM_KH] >> 32;
-    if (sorted && sh->h_ctr[ctr::SORT_DESC]) {
+    if (named) info.max_name = (uint32_t)hn[nacc::MAX_L];
+    if (sorted && (named ? hn[nacc::DESC] : sh->h_ctr[ctr::SORT_DESC])) {
       already = false;
-      const uint64_t m = n_kept, differ = sh->h_ctr[ctr::SORT_OR] & ~sh->h_ctr[ctr::SORT_AND];
+      const uint64_t m = n_kept;
       int cur = 0;
-      for (uint32_t shift = 0; shift < 64; shift += 8) {
-        if (!((differ >> shift) & 0xff)) continue;  // the same digit in every key: the pass would move nothing
-        HIPCHK(ctx, launch_sort_pass(B.skey[cur].p, B.srow[cur].p, m, shift, B.hist.p, sh->tmp.p, B.skey[cur ^ 1].p,
-                                     B.srow[cur ^ 1].p, st));
-        cur ^= 1;
+      // the passes of one key fill: every digit that differs somewhere (the same digit in every key:
+      // the pass would move nothing)
+      auto passes = [&](uint64_t differ) -> hipError_t {
+        for (uint32_t shift = 0; shift < 64; shift += 8) {
+          if (!((differ >> shift) & 0xff)) continue;
+          hipError_t e = launch_sort_pass(B.skey[cur].p, B.srow[cur].p, m, shift, B.hist.p, sh->tmp.p,
+                                          B.skey[cur ^ 1].p, B.srow[cur ^ 1].p, st);
+          if (e != hipSuccess) return e;
+          cur ^= 1;
+          ++info.passes_run;
+        }
+        return hipSuccess;
+      };
+      if (!named) {
+        HIPCHK(ctx, passes(sh->h_ctr[ctr::SORT_OR] & ~sh->h_ctr[ctr::SORT_AND]));
+      } else {
+        // a chunk the shortest name does not reach is 0 in some row, whatever the waves that reduced it saw
+        for (uint32_t c = 0; c < sbh_bam::NAME_CHUNKS; ++c)
+          if (8 * c >= hn[nacc::MIN_L]) hn[nacc::AND + c] = 0;
+        if (const uint64_t d = hn[nacc::TIE_OR] & ~hn[nacc::TIE_AND]) {
+          HIPCHK(ctx, launch_name_keys(sh->U.p, R.pos.p, B.srow[cur].p, m, sbh_bam::NAME_CHUNKS, B.skey[cur].p, st));
+          HIPCHK(ctx, passes(d));
+        }
+        for (uint32_t c = (info.max_name + 7) / 8; c-- > 0;) {
+          const uint64_t d = hn[nacc::OR + c] & ~hn[nacc::AND + c];
+          if (!d) continue;
+          HIPCHK(ctx, launch_name_keys(sh->U.p, R.pos.p, B.srow[cur].p, m, c, B.skey[cur].p, st));
+          HIPCHK(ctx, passes(d));
+          ++info.chunks_run;
+        }
+        HIPCHK(ctx, launch_name_groups(sh->U.p, R.pos.p, B.srow[cur].p, m, B.nacc.p + nacc::GROUPS, st));
+        HIPCHK(ctx, hipMemcpyAsync(hn + nacc::GROUPS, B.nacc.p + nacc::GROUPS, 32, hipMemcpyDeviceToHost, st));
       }
       HIPCHK(ctx, launch_sort_apply(R.pos.p, B.len.p, B.srow[cur].p, m, B.pos2.p, B.len2.p, B.kh.p, st));
       HIPCHK(ctx, launch_bam_heads(B.pos2.p, B.len2.p, m, B.kh.p, st));
@@ -308,6 +352,9 @@ int sbh_records_bam_scan_order(sbh_shard *sh, const uint8_t *head, uint64_t head
       HIPCHK(ctx, hipMemcpyAsync(sh->h_ctr + ctr::H_BAM_KH, B.khpre.p + m, 8, hipMemcpyDeviceToHost, st));
       HIPCHK(ctx, hipStreamSynchronize(st));
       n_runs = sh->h_ctr[ctr::H_BAM_KH] >> 32;
+    } else if (named) {  // in order as scanned: the groups of the kept rows as k_name_scan laid them out
+      HIPCHK(ctx, launch_name_groups(sh->U.p, R.pos.p, B.srow[0].p, n_kept, B.nacc.p + nacc::GROUPS, st));
+      HIPCHK(ctx, hipMemcpyAsync(hn + nacc::GROUPS, B.nacc.p + nacc::GROUPS, 32, hipMemcpyDeviceToHost, st));
     }
   } else {
     HIPCHK(ctx, hipMemcpyAsync(B.rec_off.p, &head_bytes, 8, hipMemcpyHostToDevice, st));
@@ -320,8 +367,36 @@ int sbh_records_bam_scan_order(sbh_shard *sh, const uint8_t *head, uint64_t head
   B.head_bytes = head_bytes;
   B.order = order;
   B.already = already;
+  if (named) {
+    if (n) info.n_names = hn[nacc::GROUPS], info.n_single = hn[nacc::GROUPS + 1], info.n_pair = hn[nacc::GROUPS + 2],
+           info.n_more = hn[nacc::GROUPS + 3];
+    info.already = already ? 1 : 0;
+    B.name_info = info;
+  }
   B.valid = true;
   *out = B.sz;
+  return SBH_OK;
+}
+
+int sbh_records_bam_scan_order(sbh_shard *sh, const uint8_t *head, uint64_t head_bytes, const sbh_record_filter *filter,
+                               int order, sbh_bam_sizes *out) {
+  if (!sh || !out || (head_bytes && !head)) return SBH_E_ARG;
+  if (order != SBH_ORDER_SCAN && order != SBH_ORDER_COORDINATE)
+    return fail(sh->ctx, SBH_E_ARG, "records_bam_scan: order %d is neither SBH_ORDER_SCAN nor SBH_ORDER_COORDINATE", order);
+  return bam_scan(sh, head, head_bytes, filter, order, out);
+}
+
+int sbh_records_bam_scan_names(sbh_shard *sh, const uint8_t *head, uint64_t head_bytes, const sbh_record_filter *filter,
+                               sbh_bam_sizes *out) {
+  return bam_scan(sh, head, head_bytes, filter, ORDER_NAME, out);
+}
+
+int sbh_records_bam_name_info(sbh_shard *sh, sbh_bam_name_info *out) {
+  if (!sh || !out) return SBH_E_ARG;
+  const auto &B = sh->bam;
+  if (!B.valid || B.order != ORDER_NAME)
+    return fail(sh->ctx, SBH_E_STATE, "records_bam_name_info without a name-order records_bam_scan");
+  *out = B.name_info;
   return SBH_OK;
 }
 
@@ -382,6 +457,20 @@ int sbh_bam_sort_host(const uint8_t *flat, uint64_t flat_size, const uint64_t *s
   if ((!flat && flat_size) || (!starts && n) || (!perm && n)) return SBH_E_ARG;
   uint64_t bad = sbh_bam::NO_ROW;
   const int rc = sbh_bam::sort_host(flat, flat_size, starts, n, perm, &bad);
+  if (bad_row) *bad_row = bad;
+  return rc == 0 ? SBH_OK : SBH_E_BAD_RECORD;
+}
+
+int sbh_bam_name_sort_host(const uint8_t *flat, uint64_t flat_size, const uint64_t *starts, uint64_t n, uint64_t *perm,
+                           sbh_bam_name_info *info, uint64_t *bad_row) {
+  if ((!flat && flat_size) || (!starts && n) || (!perm && n)) return SBH_E_ARG;
+  static_assert(sizeof(sbh_bam::NameInfo) == sizeof(sbh_bam_name_info), "bam_name_core.h restates the struct");
+  uint64_t bad = sbh_bam::NO_ROW;
+  sbh_bam::NameInfo ni{};
+  const int rc = sbh_bam::name_sort_host(flat, flat_size, starts, n, perm, info ? &ni : nullptr, &bad);
+  if (info)
+    *info = sbh_bam_name_info{ni.n_names, ni.n_single, ni.n_pair, ni.n_more, ni.max_name, ni.chunks_run, ni.passes_run,
+                              ni.already};
   if (bad_row) *bad_row = bad;
   return rc == 0 ? SBH_OK : SBH_E_BAD_RECORD;
 }

@@ -260,10 +260,14 @@ struct sbh_shard {
     // alternate between, the digit counts with their scan, the permuted starts and lengths
     sbh::DBuf<uint64_t> skey[2], hist, pos2, len2;
     sbh::DBuf<uint32_t> srow[2];
+    // read-name order (bam_name.hip) borrows all of those; its own: the words k_name_scan and
+    // k_name_groups reduce into (sbh::nacc) and the summary of the last name-order scan
+    sbh::DBuf<unsigned long long> nacc;
+    sbh_bam_name_info name_info{};
     sbh_bam_sizes sz{};
     uint64_t head_bytes = 0;
-    int order = SBH_ORDER_SCAN;
-    bool already = false;  // a coordinate-order scan found its kept rows in order (no pass ran)
+    int order = SBH_ORDER_SCAN;  // SBH_ORDER_SCAN, SBH_ORDER_COORDINATE or sbh::ORDER_NAME
+    bool already = false;  // a coordinate- or name-order scan found its kept rows in order (no pass ran)
     bool valid = false;
   } bam;
   // per-base depth and pileup (sbh_records_depth_add, sbh_records_pileup_add): the keep bits of the

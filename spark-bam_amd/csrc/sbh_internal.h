@@ -299,6 +299,26 @@ hipError_t launch_sort_pass(const uint64_t *key, const uint32_t *row, uint64_t m
 hipError_t launch_sort_apply(const uint64_t *pos, const uint64_t *len, const uint32_t *row, uint64_t m, uint64_t *pos2,
                              uint64_t *len2, uint64_t *kh, hipStream_t st);
 hipError_t launch_sort_rows(const uint32_t *row, uint64_t m, uint64_t *rows, hipStream_t st);
+// Read-name order of the kept rows (bam_name.hip; the order in bam_name_core.h).  The words k_name_scan
+// and k_name_groups reduce into -- a device array of the shard's (sbh_shard::Bam::nacc), not slots of
+// the counter buffer: the descents, the longest name, the tie's OR, each chunk's OR, the four group
+// counts (all preset 0), then the shortest name, the tie's AND and each chunk's AND (preset ~0).
+namespace nacc {
+constexpr uint32_t DESC = 0, MAX_L = 1, TIE_OR = 2, OR = 3, GROUPS = OR + 32, ONES = GROUPS + 4;
+constexpr uint32_t MIN_L = ONES, TIE_AND = ONES + 1, AND = ONES + 2, WORDS = AND + 32;
+}  // namespace nacc
+// sbh_shard::Bam::order after sbh_records_bam_scan_names: the library's own word, not a value of
+// sbh_records_bam_scan_order's argument (which keeps refusing it)
+constexpr int ORDER_NAME = 2;
+// launch_name_scan: row[] of the first khpre[n] & 0xffffffff entries of rows, acc = the nacc words
+// (preset).  launch_name_keys: key[k] of chunk c (c == 32: the tie) for row[k], k < m.
+// launch_name_groups: out = acc + nacc::GROUPS, over row[] in its final order.
+hipError_t launch_name_scan(const uint8_t *U, const uint64_t *pos, const uint64_t *rows, const uint64_t *kh_total,
+                            uint64_t n, uint32_t *row, unsigned long long *acc, hipStream_t st);
+hipError_t launch_name_keys(const uint8_t *U, const uint64_t *pos, const uint32_t *row, uint64_t m, uint32_t c,
+                            uint64_t *key, hipStream_t st);
+hipError_t launch_name_groups(const uint8_t *U, const uint64_t *pos, const uint32_t *row, uint64_t m,
+                              unsigned long long *out, hipStream_t st);
 // BGZF footer CRC32 of every inflated, non-truncated block (crc.hip).
 hipError_t launch_block_crc(const uint8_t *comp, DevBlocks bl, uint64_t nblocks, const uint8_t *U,
                             unsigned long long *n_bad, unsigned long long *first_bad, hipStream_t st);
@@ -426,6 +446,8 @@ constexpr uint32_t PILE_END = PILE_TOTALS + 8;
 constexpr uint32_t FIRST_BAD = 100;
 // h_ctr only: that block's status (u32), fetched after the run's copy of [0, CTR_RUN_WORDS)
 constexpr uint32_t H_BAD_STATUS = 101;
+// h_ctr only: where a name-order BAM scan's nacc:: words land (the device words are the shard's own array)
+constexpr uint32_t H_NAME = 128;
 // h_ctr only, host scratch under the full checker's mirror (each written and read within one
 // call): the 18 bytes at an index's start and its next18 words (sbh_index); the proof
 // counters' initial values, an H2D source, and the bitmap word of the proof's first position
@@ -449,6 +471,8 @@ static_assert(ctr::EAGER_END <= CTR_RUN_WORDS && ctr::FRS_BEST < CTR_RUN_WORDS &
 // ... and that copy must not land on the status word fetched after it
 static_assert(ctr::H_BAD_STATUS >= CTR_RUN_WORDS, "the bad block's status lies behind the run's copy");
 static_assert(ctr::H_RUN_TPL + CTR_RUN_WORDS <= CTR_WORDS, "the run template fits the mirror");
+static_assert(ctr::H_NAME > ctr::H_BAD_STATUS && ctr::H_NAME + nacc::WORDS <= ctr::H_INDEX_HDR18,
+              "the name words' mirror lies between the run's words and the index's host scratch");
 static_assert(ctr::H_INDEX_HDR18 + 3 <= ctr::H_INDEX_NEXT18 && ctr::H_INDEX_NEXT18 + 3 <= ctr::H_PROOF_INIT &&
                   ctr::H_PROOF_INIT + 4 <= ctr::H_PROOF_FIRST_WORD && ctr::H_PROOF_FIRST_WORD < ctr::H_RUN_TPL,
               "host scratch regions are disjoint");

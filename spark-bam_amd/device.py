@@ -8,7 +8,7 @@ import numpy as np
 from .coverage import DEPTH_DEL, DEPTH_RUN_DTYPE, DEPTH_SPAN_DTYPE, span_array
 from .records import pack_ref_names, record_columns, record_filter
 
-from ._lib import (ORDER_COORDINATE, SBH_OK, SbhBaiSizes, SbhBamSizes, SbhBatchSplit, SbhBlock, SbhCheckOpts, SbhCheckResult, SbhDepthAddResult, SbhPileupAddResult, SbhPileupSizes,
+from ._lib import (ORDER_COORDINATE, SBH_OK, SbhBaiSizes, SbhBamNameInfo, SbhBamSizes, SbhBatchSplit, SbhBlock, SbhCheckOpts, SbhCheckResult, SbhDepthAddResult, SbhPileupAddResult, SbhPileupSizes,
                    SbhDepthSizes, SbhFastqSizes, SbhRecordsOut,
                    SbhRecordsSizes, SbhSamSizes, SbhShardResult, SbhSplitBatchResult, SbhSplitRecordsResult,
                    SbhStatsAddResult, SbhStatsParams, SbhStreamOpts, SbhStreamResult, SbhTallyAddResult, SparkBamError, error_for, lib)
@@ -866,15 +866,22 @@ class Shard(_Owned):
         `self.bam_n` / `self.bam_n_kept`: rows scanned and kept.
         order="coordinate" (sbh_records_bam_scan_order): the kept records in stable coordinate
         order -- reference, position, reverse strand, unplaced last -- sorted on the GPU; `rows`
-        is then the permutation, and `self.bam_sorted` says whether they were in order already."""
-        if order not in ("scan", "coordinate"):
-            raise ValueError("records_bam: order is 'scan' or 'coordinate', not %r" % (order,))
+        is then the permutation, and `self.bam_sorted` says whether they were in order already.
+        order="name" (sbh_records_bam_scan_names): the kept records in stable read-name order --
+        names as unsigned bytes, a prefix first (samtools sort -N), then READ1 / READ2, then primary,
+        secondary, supplementary -- sorted on the GPU; `rows` is the permutation and
+        `self.bam_name_info` the summary of the name groups and of what the sort ran."""
+        if order not in ("scan", "coordinate", "name"):
+            raise ValueError("records_bam: order is 'scan', 'coordinate' or 'name', not %r" % (order,))
         hd = np.frombuffer(bytes(head), dtype=np.uint8)
         f, keep = record_filter(filter)
         sz = SbhBamSizes()
         if order == "scan":
             self._c(lib().sbh_records_bam_scan(self.h, _ptr(hd) if hd.size else None, int(hd.size),
                                                C.byref(f) if f is not None else None, C.byref(sz)))
+        elif order == "name":
+            self._c(lib().sbh_records_bam_scan_names(self.h, _ptr(hd) if hd.size else None, int(hd.size),
+                                                     C.byref(f) if f is not None else None, C.byref(sz)))
         else:
             self._c(lib().sbh_records_bam_scan_order(self.h, _ptr(hd) if hd.size else None, int(hd.size),
                                                      C.byref(f) if f is not None else None, ORDER_COORDINATE,
@@ -897,6 +904,18 @@ class Shard(_Owned):
         already = C.c_int()
         self._c(lib().sbh_records_bam_sorted(self.h, C.byref(already)))
         return bool(already.value)
+
+    @property
+    def bam_name_info(self):
+        """After records_bam(order="name"): a dict of sbh_bam_name_info -- n_names, n_single, n_pair,
+        n_more (the groups of rows of one name, and those of 1, 2 and more rows), max_name (bytes),
+        chunks_run, passes_run (the 8-byte chunks and 8-bit passes the sort ran) and already (the
+        kept rows were in name order as scanned).  SBH_E_STATE otherwise."""
+        info = SbhBamNameInfo()
+        self._c(lib().sbh_records_bam_name_info(self.h, C.byref(info)))
+        out = {k: int(getattr(info, k)) for k, _ in SbhBamNameInfo._fields_}
+        out["already"] = bool(out["already"])
+        return out
 
     def bam_ptr(self):
         """Device pointer of the last records_bam stream (sbh_records_bam_device_ptr; None when a

@@ -243,6 +243,29 @@ def bam_sort_host(flat, starts):
     return perm
 
 
+def bam_name_sort_host(flat, starts):
+    """The permutation Shard.records_bam(order="name") applies on the GPU, computed on the host by
+    the library (sbh_bam_name_sort_host: no GPU, the order the device path shares): (perm, info),
+    perm[k] = the index into starts[] of the record that comes k-th in stable read-name order (names
+    as unsigned bytes, a prefix first; then READ1 / READ2, primary, secondary, supplementary; ties
+    in starts[] order), info = Shard.bam_name_info's dict with chunks_run = passes_run = 0.  Raises
+    SparkBamError(SBH_E_BAD_RECORD) with `.fields = (row,)` for the first invalid record."""
+    import ctypes as C
+
+    from ._lib import SBH_OK, SbhBamNameInfo, SparkBamError, lib
+    flat = np.ascontiguousarray(np.frombuffer(flat, dtype=np.uint8) if not isinstance(flat, np.ndarray) else flat)
+    st = np.ascontiguousarray(starts, dtype=np.uint64)
+    perm = np.zeros(st.size, dtype=np.uint64)
+    bad, info = C.c_uint64(), SbhBamNameInfo()
+    p = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None  # noqa: E731
+    rc = lib().sbh_bam_name_sort_host(p(flat), flat.size, p(st), st.size, p(perm), C.byref(info), C.byref(bad))
+    if rc != SBH_OK:
+        raise SparkBamError(rc, "record %d is malformed" % bad.value if rc == 20 else "bam_name_sort_host", (bad.value,))
+    out = {k: int(getattr(info, k)) for k, _ in SbhBamNameInfo._fields_}
+    out["already"] = bool(out["already"])
+    return perm, out
+
+
 def bam_header_set_so(head, so):
     """The BAM header bytes (magic, l_text, text, references) with the @HD line's SO: set to `so`
     (sbh_bam_header_set_so, host only)."""
